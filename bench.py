@@ -40,16 +40,23 @@ def parse():
     ap.add_argument("--voxel-size", type=float, default=0.25)
     ap.add_argument("--sensor", default="os1-128")
     ap.add_argument("--map-warm-scans", type=int, default=96)
-    ap.add_argument("--cpu-baseline-scans", type=int, default=512, help="scans timed through the CPU oracle (0 disables); ~10 s of single-thread CPU work")
-    ap.add_argument("--no-profile-pass", action="store_true")
-    ap.add_argument("--loaded-tail-steps", type=int, default=40, help="steps of the loaded-tail leg (a scene with 12 floating targets: >= 50 detections per step); 0 disables")
-    ap.add_argument("--host-input-steps", type=int, default=12, help="steps of the host-resident input leg (pinned host columns, VOFOD_MEM_HOST: the nodelet's operating point); 0 disables")
+    ap.add_argument("--full", action="store_true", help="after the headline run, also every other leg: voxels per frame, configs[3] strong scaling and its per-GPU share, "
+                    "single stream, loaded tail, host-resident input, per-kernel profile pass + roofline, CPU baseline, ranks seen by the collective")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to its caller (rank 0: the detection records "
+                    "and per-frame counts of vofod_batch_collect) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-baseline-scans", type=int, default=512, help="--full: scans timed through the CPU oracle (0 disables); ~10 s of single-thread CPU work")
+    ap.add_argument("--no-profile-pass", action="store_true", help="--full: skip the per-kernel profile pass (roofline, kernels)")
+    ap.add_argument("--loaded-tail-steps", type=int, default=40, help="--full: steps of the loaded-tail leg (a scene with 12 floating targets: >= 50 detections per step); 0 disables")
+    ap.add_argument("--host-input-steps", type=int, default=12, help="--full: steps of the host-resident input leg (pinned host columns, VOFOD_MEM_HOST: the nodelet's operating point); 0 disables")
     ap.add_argument("--inflight", type=int, default=0, help="batches in flight (1..8; 0 = four for batches of 128 frames and more - the submission of batch k+1 then never waits for the tail of batch k-2, more gain nothing - and eight for smaller batches, whose whole chains run side by side); their kernel chains run on streams of their own and overlap on the device")
     ap.add_argument("--collective", choices=("torch", "cabi"), default="torch", help="N > 1: all-gather through torch.distributed (RCCL / gloo) or through the product's C-ABI (vofod_allgather_detections: RCCL from libvofod_hip.so)")
     ap.add_argument("--backend", default="nccl", help="process-group backend; gloo (CPU tensors) is for rehearsing the N>1 path on a 1-GPU box")
     ap.add_argument("--rehearse-one-gpu", action="store_true", help="every rank uses cuda:0 (only with --backend gloo)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak", help="weak: --frames per GPU per step; strong: --frames in total per step, split over the GPUs (configs[3]: 256 scans over 8 GPUs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def build_detector(lib, sensor, voxel_size, frames, device):
@@ -158,8 +165,17 @@ def main():
         args.inflight = 4 if F >= 128 else 8
     det = build_detector(lib, args.sensor, args.voxel_size, max(F, args.max_batch), local_rank)
     det.reserve(args.inflight)  # workspaces of the batches in flight: allocated here, not inside the first (warm-up) submits (7 ms each)
+    # The synthetic scans are numpy ray casts on the host (~0.1 s each, ~600 of them before the first step).  Each is a function
+    # of its seed alone: worker processes build them side by side, every one running the serial code (threads of this process
+    # building them at once gave other scans on a many-core host).  The workers are fresh interpreters that never touch
+    # the GPU, at most 16 in all, with one BLAS thread each (read when their numpy loads; this process's numpy has loaded).
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+
+    os.environ.setdefault("OPENBLAS_NUM_THREADS", "1")
+    pool = ProcessPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0)) // world)), mp_context=multiprocessing.get_context("spawn"))
     scene = synth.bench_scene()
-    synth.warm_map(det, scene, args.sensor, args.map_warm_scans)
+    synth.warm_map(det, scene, args.sensor, args.map_warm_scans, pmap=pool.map)
 
     # F independent frames per rank (seeds differ per rank), resident in HBM as packed SoA columns
     h, w, _, _ = synth.SENSORS[args.sensor]
@@ -174,12 +190,14 @@ def main():
         sc = [ScanData(x=c[f, 0].data_ptr(), y=c[f, 1].data_ptr(), z=c[f, 2].data_ptr(), width=w, height=h, stride_bytes=4, memspace=capi.MEM_DEVICE) for f in range(len(frames_))]
         return c, sc, np.stack([s.tf for s in frames_]).astype(np.float32)
 
-    host_scans = synth.bench_frames(scene, args.sensor, F, rank)
+    host_scans = synth.bench_frames(scene, args.sensor, F, rank, pmap=pool.map)
     cols, scans, tfs = resident(host_scans)
     # a second, different set of F frames (other poses, other noise): the timed loop alternates between the two, so that no step
     # finds its 402 MB of input in the 256 MB Infinity Cache from the step before
-    host_scans_b = synth.bench_frames(scene, args.sensor, F, rank + 5000)
+    host_scans_b = synth.bench_frames(scene, args.sensor, F, rank + 5000, pmap=pool.map)
     cols_b, scans_b, tfs_b = resident(host_scans_b)
+    if not args.full:
+        pool.shutdown()  # (no worker waits beside the timed steps; --full builds more scans for its legs)
     torch.cuda.synchronize()
     input_sets = [(scans, tfs), (scans_b, tfs_b)]
 
@@ -211,6 +229,8 @@ def main():
             b["local"].copy_(rec_host, non_blocking=True)
             vdist.allgather_detections(b["local"], b["all"])
 
+    last_step = {}  # what the last batch collected returned to its caller (--dump-outputs)
+
     def run_steps(k, scans=None, tfs=None):
         """k batches through the submit/collect pipeline: batch i+1 is enqueued before batch i is collected, so the host
         tail of one batch overlaps the device chain of the next.  Every batch is submitted and collected inside the call."""
@@ -228,6 +248,7 @@ def main():
                 dets, per = det.batch_collect(inflight.pop(0))
                 publish(dets, per)
                 n_det += len(dets)
+                last_step["dets"], last_step["per"] = dets, per
             t_sub += tb - ta
             t_col += time.perf_counter() - tb
             if step_log is not None:
@@ -238,6 +259,7 @@ def main():
             dets, per = det.batch_collect(inflight.pop(0))
             publish(dets, per)
             n_det += len(dets)
+            last_step["dets"], last_step["per"] = dets, per
         if step_log:
             d = np.diff(np.array([t for t, _ in step_log])) * 1e3
             print(f"[steps] k={k} ms between step completions (ms inside submit): " + " ".join(f"{x:.2f}({1e3 * sb:.2f})" for x, (_, sb) in zip(d, step_log[1:])), file=sys.stderr)
@@ -269,11 +291,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     gc.enable()  # the timed region is over: the legs below (and the CPU baseline) run with the collector as usual
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), last_step["dets"], last_step["per"])
+    # Everything below the headline line's own fields is --full: other configurations, other legs, the profile pass, the CPU
+    # baseline.  A plain run sets up, warms up, times its steps, dumps and prints.
 
     # configs[3] as written: 256 scans per step in total, split over the ranks (strong scaling), all-gather included.  On one
     # GPU this is the headline run itself; on N GPUs every rank takes the first 256 / N of its frames.
     strong = None
-    if world > 1 and args.scaling == "weak":
+    if args.full and world > 1 and args.scaling == "weak":
         Fs = max(4, min(F, 256 // world))
         s_scans, s_tfs = scans[:Fs], tfs[:Fs]
         gb["cur"] = gather_bufs(Fs)
@@ -292,9 +318,10 @@ def main():
     # proof that the collective saw every rank (the first real multi-GPU record should show N ranks over RCCL, not N replicas)
     ranks_seen, rccl_version = [0], None
     if world > 1:
-        rs = [torch.zeros(1, dtype=torch.int64, device=cdev) for _ in range(world)]
-        dist.all_gather(rs, torch.tensor([rank], dtype=torch.int64, device=cdev))
-        ranks_seen = [int(t.item()) for t in rs]
+        if args.full:
+            rs = [torch.zeros(1, dtype=torch.int64, device=cdev) for _ in range(world)]
+            dist.all_gather(rs, torch.tensor([rank], dtype=torch.int64, device=cdev))
+            ranks_seen = [int(t.item()) for t in rs]
         if args.backend == "nccl":
             try:
                 rccl_version = ".".join(str(v) for v in torch.cuda.nccl.version())
@@ -303,12 +330,13 @@ def main():
     out = None
     if rank == 0:
         frames = world * F * args.steps
-        # per-frame statistics for the algorithmic-bytes model B = 12*N + 40*V
-        _, dbg = det.process_scan(scans[0], tfs[0], flags=capi.SCAN_NO_MAP_UPDATE, debug=True)
-        V = len(dbg["weighted"])
-        # ... and for the bytes the close-first path really has to move: the voxels of the far clusters (the only ones clustered)
-        _, _, dbg_far = det.process_batch(scans[:4], tfs[:4], debug=True, far_only=True)
-        V_far = float(np.mean([int((g["labels"] != capi.LABEL_NONE).sum()) for g in dbg_far]))
+        if args.full:
+            # per-frame statistics for the algorithmic-bytes model B = 12*N + 40*V
+            _, dbg = det.process_scan(scans[0], tfs[0], flags=capi.SCAN_NO_MAP_UPDATE, debug=True)
+            V = len(dbg["weighted"])
+            # ... and for the bytes the close-first path really has to move: the voxels of the far clusters (the only ones clustered)
+            _, _, dbg_far = det.process_batch(scans[:4], tfs[:4], debug=True, far_only=True)
+            V_far = float(np.mean([int((g["labels"] != capi.LABEL_NONE).sum()) for g in dbg_far]))
         out = {
             "metric": "LiDAR frames/sec (131k-pt OS1-128) at 1/2/4/8 MI355X + HBM roofline %",
             "value": frames / dt,
@@ -326,7 +354,7 @@ def main():
                 "workload": f"{args.sensor} {h}x{w} scans, {args.voxel_size} m voxels, batched process_scan (configs[1] scan shape in configs[3]'s batched form)",
                 "frames_per_gpu_per_step": F,
                 "points_per_frame": n_pts,
-                "voxels_per_frame": V,
+                **({"voxels_per_frame": V} if args.full else {}),
                 "map_voxels": det.n_voxels,
                 "map_warm_scans": args.map_warm_scans,
                 "detections_per_step": n_det / args.steps,
@@ -335,31 +363,33 @@ def main():
             },
         }
         if world > 1:
-            out["ranks_seen"] = ranks_seen
+            if args.full:
+                out["ranks_seen"] = ranks_seen
             out["collective"] = {"caller": args.collective, "backend": args.backend, "rccl_version": rccl_version}
         if strong is not None:
             out["config3_strong"] = strong
-        elif world == 1 and F == 256 and args.scaling == "weak":
+        elif args.full and world == 1 and F == 256 and args.scaling == "weak":
             out["config3_strong"] = {"frames_total_per_step": F, "frames_per_gpu_per_step": F, "frames_per_s": frames / dt, "ms_per_step": 1e3 * dt / args.steps,
                                      "note": "configs[3] on one GPU is the headline run itself (256 scans per step)"}
-        # single-stream (stateful, sequential) latency of the same scan shape
-        seq = synth.scan_sequence(scene, args.sensor, 17, seed0=5000)
-        seq_dev = []
-        keep = []
-        for s in seq:
-            t = torch.from_numpy(np.stack([s.x, s.y, s.z])).to(dev)
-            keep.append(t)
-            seq_dev.append(ScanData(x=t[0].data_ptr(), y=t[1].data_ptr(), z=t[2].data_ptr(), width=w, height=h, stride_bytes=4, memspace=capi.MEM_DEVICE))
-        torch.cuda.synchronize()
-        det.process_scan(seq_dev[0], seq[0].tf)
-        t1 = time.perf_counter()
-        for s, sd in zip(seq[1:], seq_dev[1:]):
-            det.process_scan(sd, s.tf)
-        single_ms = 1e3 * (time.perf_counter() - t1) / (len(seq) - 1)
-        out["single_stream"] = {"ms_per_scan": single_ms, "frames_per_s": 1e3 / single_ms, "scans": len(seq) - 1,
-                                "note": "sequential vofod_process_scan with map update (the reference's own mode: one sensor stream), device-resident input, classification tail on the device"}
+        if args.full:
+            # single-stream (stateful, sequential) latency of the same scan shape
+            seq = synth.scan_sequence(scene, args.sensor, 17, seed0=5000, pmap=pool.map)
+            seq_dev = []
+            keep = []
+            for s in seq:
+                t = torch.from_numpy(np.stack([s.x, s.y, s.z])).to(dev)
+                keep.append(t)
+                seq_dev.append(ScanData(x=t[0].data_ptr(), y=t[1].data_ptr(), z=t[2].data_ptr(), width=w, height=h, stride_bytes=4, memspace=capi.MEM_DEVICE))
+            torch.cuda.synchronize()
+            det.process_scan(seq_dev[0], seq[0].tf)
+            t1 = time.perf_counter()
+            for s, sd in zip(seq[1:], seq_dev[1:]):
+                det.process_scan(sd, s.tf)
+            single_ms = 1e3 * (time.perf_counter() - t1) / (len(seq) - 1)
+            out["single_stream"] = {"ms_per_scan": single_ms, "frames_per_s": 1e3 / single_ms, "scans": len(seq) - 1,
+                                    "note": "sequential vofod_process_scan with map update (the reference's own mode: one sensor stream), device-resident input, classification tail on the device"}
 
-        if F > 32 and world == 1:
+        if args.full and F > 32 and world == 1:
             # configs[3] spreads 256 scans over 8 GPUs: 32 per GPU and step.  The same handle, batches of 32 frames.
             sub, sub_tfs = scans[:32], tfs[:32]
 
@@ -402,11 +432,11 @@ def main():
             out["config3_share"] = {"frames_per_gpu_per_step": 32, "frames_per_s": 32 * 100 / dt32, "ms_per_step": 1e3 * dt32 / 100, "kernel_us": k32,
                                     "batches_in_flight": depth32, **host_us,
                                     "note": "configs[3]'s per-GPU share (256 scans / 8 GPUs): 32-frame batches on this one GPU, eight in flight, each on a stream (and hardware queue) of its own with its own tail; a frame kernel of 32 workgroups leaves 7/8 of the CUs to the other batches in flight"}
-        if world == 1 and args.loaded_tail_steps > 0:
+        if args.full and world == 1 and args.loaded_tail_steps > 0:
             # the classification tail under load: twelve floating targets, nine of which appeared after the map was warmed
             # (the headline scene's three are part of the background by now: ~3 detections per step leave the tail nearly idle)
             busy = synth.make_scene(synth.BENCH_SCENE_SEED, n_targets=12)
-            _, scans_t, tfs_t = resident(synth.bench_frames(busy, args.sensor, F, rank))
+            _, scans_t, tfs_t = resident(synth.bench_frames(busy, args.sensor, F, rank, pmap=pool.map))
             run_steps(3, scans_t, tfs_t)
             sync()
             t1 = time.perf_counter()
@@ -416,10 +446,10 @@ def main():
             out["loaded_tail"] = {"frames_per_s": F * args.loaded_tail_steps / dtl, "ms_per_step": 1e3 * dtl / args.loaded_tail_steps, "steps": args.loaded_tail_steps,
                                   "detections_per_step": nd / args.loaded_tail_steps,
                                   "note": "the same pipeline on a scene with 12 floating targets (9 new since the warm-up): dozens of candidate clusters, flood fills and detections per batch"}
-        if world == 1 and args.host_input_steps > 0:
+        if args.full and world == 1 and args.host_input_steps > 0:
             out["host_input"] = host_input_leg(args, det, host_scans, tfs, torch, capi, ScanData, h, w)
             out["host_input_aos"] = host_input_aos_leg(args, det, host_scans, tfs, torch, capi, ScanData, h, w)
-        if not args.no_profile_pass:
+        if args.full and not args.no_profile_pass:
             out["roofline"], out["kernels"] = profile_pass(lib, det, scans, tfs, n_pts, V, F, V_far)
             # the same bytes over the pipelined step time of this rank (kernels of consecutive batches overlap: the step is
             # shorter than the sum of its kernels)
@@ -430,13 +460,28 @@ def main():
                     "GBps": pb / (1e-3 * out["ms_per_step"]) / 1e9,
                     "frac": pb / (1e-3 * out["ms_per_step"]) / 1e9 / HBM_PEAK_GBS,
                 }
-        if args.cpu_baseline_scans > 0:
+        if args.full and args.cpu_baseline_scans > 0:
             out["cpu_baseline"] = cpu_baseline(args, det, host_scans)
+    pool.shutdown()
     sync()
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir: Path, dets: np.ndarray, per: np.ndarray, max_bytes: int = 64 << 20):
+    """--dump-outputs: what the caller of the timed path received from its last step - every field of the detection records
+    of vofod_batch_collect (detections_<field>.npy, one row per detection) and the detections per frame - as float64 (ids,
+    frames and counts are exact).  More records than `max_bytes` holds: a fixed, seeded sample of them, in their order."""
+    per_rec = 8 * sum(int(np.prod(dets.dtype[k].shape)) for k in dets.dtype.names)
+    keep = max(0, (max_bytes - 8 * len(per)) // per_rec)
+    if len(dets) > keep:
+        dets = dets[np.sort(np.random.default_rng(0).choice(len(dets), keep, replace=False))]
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k in dets.dtype.names:
+        np.save(out_dir / f"detections_{k}.npy", np.ascontiguousarray(dets[k], dtype=np.float64))
+    np.save(out_dir / "detections_per_frame.npy", np.ascontiguousarray(per, dtype=np.float64))
 
 
 def host_input_leg(args, det, host_scans, tfs, torch, capi, ScanData, h, w):

@@ -7,6 +7,6 @@ ROUNDS=${2:-3}
 for i in $(seq $ROUNDS); do
   for v in $VARS; do
     cp ab_libs/$v.so vofod_amd/csrc/libvofod_hip.so
-    timeout -k 10 200 python bench.py --steps 40 --warmup 8 --cpu-baseline-scans 0 --host-input-steps 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']; print('$v', round(d['value']), round(d['ms_per_step'],3), {n.split('<')[0]: round(x['avg_us'],1) for n,x in k.items() if n.startswith(('k_key1','k_frame_lds'))})"
+    timeout -k 10 200 python bench.py --full --steps 40 --warmup 8 --cpu-baseline-scans 0 --host-input-steps 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']; print('$v', round(d['value']), round(d['ms_per_step'],3), {n.split('<')[0]: round(x['avg_us'],1) for n,x in k.items() if n.startswith(('k_key1','k_frame_lds'))})"
   done
 done

@@ -8,7 +8,7 @@ mkdir -p $OUT
 # before python starts - the variable has to come from this shell
 export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/p -- python3 $R/bench.py --frames 32 --steps 60 --warmup 10 --cpu-baseline-scans 0 --no-profile-pass --host-input-steps 0 > $OUT/p.log 2>&1 || { tail -5 $OUT/p.log; exit 1; }
+rocprofv3 --kernel-trace --output-format csv -d $OUT/p -- python3 $R/bench.py --full --frames 32 --steps 60 --warmup 10 --cpu-baseline-scans 0 --no-profile-pass --host-input-steps 0 > $OUT/p.log 2>&1 || { tail -5 $OUT/p.log; exit 1; }
 cd $R && python3 - $OUT <<'PY' > $OUT/timeline.txt
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/p/**/*kernel_trace.csv", recursive=True)[0]

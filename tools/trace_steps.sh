@@ -7,7 +7,7 @@ mkdir -p $OUT
 # before python starts - the variable has to come from this shell
 export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --steps 40 --warmup 5 --cpu-baseline-scans 0 --no-profile-pass ${BENCH_ARGS:-} > $OUT/log.txt 2>&1 || exit 1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --full --steps 40 --warmup 5 --cpu-baseline-scans 0 --no-profile-pass ${BENCH_ARGS:-} > $OUT/log.txt 2>&1 || exit 1
 cd $R && python3 - <<PY
 import csv,glob
 rows=sorted(csv.DictReader(open(glob.glob('$OUT/**/*kernel_trace.csv',recursive=True)[0])),key=lambda r:int(r['Start_Timestamp']))

@@ -11,6 +11,7 @@ beyond the sensor's max range) carry range 0 and xyz (0,0,0) as ouster_ros does.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from functools import partial
 
 import numpy as np
 
@@ -195,13 +196,14 @@ def seed_ground(det, xy=(0.0, 0.0), radius: float = 30.0, value: float = -185.0)
     det.write_map(capi.MAP_VOXELS, m)
 
 
-def scan_sequence(scene: Scene, sensor: str, n: int, seed0: int = 0, xy=(0.0, 0.0)):
-    """n scans of one scene from slowly varying poses (a hovering MAV)."""
-    out = []
-    for k in range(n):
-        tf = make_pose(seed0 + k, xy=xy)
-        out.append(make_scan(scene, tf, sensor, seed=seed0 + k))
-    return out
+def _sequence_scan(scene: Scene, sensor: str, seed0: int, xy, k: int) -> SynthScan:
+    return make_scan(scene, make_pose(seed0 + k, xy=xy), sensor, seed=seed0 + k)
+
+
+def scan_sequence(scene: Scene, sensor: str, n: int, seed0: int = 0, xy=(0.0, 0.0), pmap=map):
+    """n scans of one scene from slowly varying poses (a hovering MAV).  Every scan is a function of its seed alone: `pmap`
+    (e.g. a process pool's map) may build them side by side, the list is the same."""
+    return list(pmap(partial(_sequence_scan, scene, sensor, seed0, xy), range(n)))
 
 
 # ---------------------------------------------------------------------------- bench workload
@@ -215,18 +217,22 @@ def bench_scene() -> Scene:
     return make_scene(BENCH_SCENE_SEED, n_targets=3)
 
 
-def bench_frames(scene: Scene, sensor: str, n: int, rank: int = 0):
+def _bench_scan(scene: Scene, sensor: str, rank: int, f: int) -> SynthScan:
+    return make_scan(scene, make_pose(10_000 * rank + f), sensor, seed=10_000 * rank + f)
+
+
+def bench_frames(scene: Scene, sensor: str, n: int, rank: int = 0, pmap=map):
     """the n independent scans of one rank's batch in bench.py: independent poses and noise seeds 10 000*rank + f"""
-    return [make_scan(scene, make_pose(10_000 * rank + f), sensor, seed=10_000 * rank + f) for f in range(n)]
+    return list(pmap(partial(_bench_scan, scene, sensor, rank), range(n)))
 
 
-def warm_map(det, scene: Scene, sensor: str, n_scans: int, seed0: int = BENCH_WARM_SEED0):
+def warm_map(det, scene: Scene, sensor: str, n_scans: int, seed0: int = BENCH_WARM_SEED0, pmap=map):
     """config 2 of SURVEY 8d: map pre-warmed by n scans with the raycast and sepclusters roles interleaved.
     Works on any implementation of the C-ABI (bench.py warms the HIP detector, the tests hand the map to the oracle)."""
     from . import capi
 
     seed_ground(det)
-    for k, s in enumerate(scan_sequence(scene, sensor, n_scans, seed0=seed0)):
+    for k, s in enumerate(scan_sequence(scene, sensor, n_scans, seed0=seed0, pmap=pmap)):
         det.process_scan(s.scan, s.tf, flags=capi.SCAN_AUTO_RAYCAST)
         if k % 2 == 1:
             st, sure = det.sepclusters_begin(allow=(capi.ERR_EMPTY,))
