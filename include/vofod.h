@@ -51,7 +51,8 @@ typedef enum vofod_status {
   VOFOD_ERR_NOT_PENDING = 10,         /* *_finish without a matching *_begin */
   VOFOD_ERR_EMPTY = 11,               /* sepclusters: thresholded map cloud empty: :1155-1159 */
   VOFOD_ERR_MAP_RANGE = 12,           /* a weighted point fell outside the voxel map (vector::at would throw: voxel_map.cpp:116-117) */
-  VOFOD_ERR_BUSY = 13                 /* a submitted batch (vofod_batch_submit) still reads the state this call would overwrite: collect it first */
+  VOFOD_ERR_BUSY = 13,                /* a submitted batch (vofod_batch_submit) still reads the state this call would overwrite: collect it first */
+  VOFOD_ERR_DELTA_BASE = 14           /* map delta: does not follow the snapshot last applied (replica) / no chain for the maps mask (owner) */
 } vofod_status;
 
 typedef struct vofod_handle vofod_handle;
@@ -419,6 +420,54 @@ int vofod_unpack_detection_slots(const void* slots, size_t frames_total, size_t 
  * all_counts: n_ranks * frames_per_rank counts (a count above d_max tells that the slot was truncated). */
 int vofod_allgather_detections(vofod_comm* comm, const vofod_detection* local, const uint32_t* n_per_frame, size_t frames_per_rank, size_t d_max, vofod_detection* all,
                                uint32_t* all_counts);
+
+/* ------------------------------------------------- map snapshots and deltas (product library only)
+ *
+ * Moving a map between handles, processes and GPUs: checkpoints at shutdown / restore in onInit, and replicas of a live map
+ * for the batched mode.  The reference has no counterpart: it can reload only its a-priori cloud (:306-355).
+ *
+ * `maps` is a bitmask of (1 << VOFOD_MAP_VOXELS) | (1 << VOFOD_MAP_FLAGS) | (1 << VOFOD_MAP_RAYCAST).
+ *   VOFOD_SNAPSHOT_FULL   every voxel of each selected map whose 32-bit pattern differs from that map's init state (score_init
+ *                         for the voxel map, 0.0f for flags and raycast); applying it resets the selected maps to init first.
+ *                         Applies to any handle with the same map size, offset, voxel size and score_init; starts a chain.
+ *   VOFOD_SNAPSHOT_DELTA  the voxels whose bits differ from what this handle last exported with the same mask.  Applies only on
+ *                         a handle whose last applied snapshot (full or delta) has generation == the delta's base_gen and the
+ *                         same mask; otherwise VOFOD_ERR_DELTA_BASE and nothing is written.  Exporting a delta without a chain
+ *                         for the mask (one chain per handle: a full export of another mask replaces it) is VOFOD_ERR_DELTA_BASE.
+ *                         vofod_reset / vofod_write_map on the owner do not break the chain.
+ * Records are sorted by strictly ascending idx = ix + iy*sx + iz*sx*sy.  The export keeps a shadow copy of each exported map:
+ * 4 * M bytes per map (78 MB at 0.25 m, 1.2 GB at 0.1 m), allocated on its first export and freed by vofod_destroy.
+ *
+ * Wire format (little endian; the same bytes in memory, over RCCL and in a file): a 128-byte header
+ *   0 u32 magic 0x444D4656 ("VFMD") | 4 u32 version = 1 | 8 u32 maps | 12 u32 kind (0 delta, 1 full) | 16 i32[3] map size |
+ *   28 f32[3] map offset (as vofod_status_info) | 40 f32 voxel size | 44 f32 score_init | 48 u64 base_gen (0 for full) |
+ *   56 u64 new_gen | 64 i32 detection_its, u32 last_detection_id, i32 background_pts_sufficient, i32 sure_background_sufficient |
+ *   80 i32 raycast_pending, i32 raycast_start_its | 88 u64[3] records per map (voxels, flags, raycast; 0 when not selected) |
+ *   112 16 zero bytes
+ * followed, per selected map in that order, by u32 idx[n] and u32 bits[n].  Size = 128 + 8 * sum(n).
+ *
+ * Apply always restores detection_its, last_detection_id and both background latches; raycast_pending and raycast_start_its
+ * only when the snapshot holds both FLAGS and RAYCAST (the next vofod_raycast_finish then does what the owner's would).  A
+ * pending sepclusters pass is not carried (its cluster list lives in the owner's workspace) and the applying handle's own
+ * pending pass is dropped.  Derived state (occupancy images, nVoxelsOver) is rebuilt on next use, as after vofod_write_map.
+ * Apply checks everything before it writes: format (VOFOD_ERR_INVALID_ARG), geometry (VOFOD_ERR_SIZE_MISMATCH), chain
+ * (VOFOD_ERR_DELTA_BASE), record indices ascending and < M (VOFOD_ERR_INVALID_ARG, checked on the device); VOFOD_ERR_BUSY
+ * while a submitted batch is pending.  Export only reads the maps and may run beside batches in flight. */
+enum { VOFOD_SNAPSHOT_DELTA = 0, VOFOD_SNAPSHOT_FULL = 1 };
+/* buf == NULL && cap == 0: size query (*n_bytes set, nothing changes).  cap too small: VOFOD_ERR_CAPACITY with *n_bytes = the
+ * size, generation and shadow untouched.  memspace: VOFOD_MEM_HOST or VOFOD_MEM_DEVICE (4-byte aligned, the handle's device). */
+int vofod_map_export(vofod_handle* h, int32_t maps, int32_t kind, void* buf, size_t cap, int32_t memspace, size_t* n_bytes);
+int vofod_map_apply(vofod_handle* h, const void* buf, size_t n_bytes, int32_t memspace);
+/* Collective over comm (every rank calls it with the same arguments; comm and h on the same device): the root exports `kind`
+ * of `maps` into a device staging buffer of h, broadcasts a 16-byte control word (status, bytes) and then the payload with
+ * RCCL; the other ranks apply it from device memory.  *n_bytes = the snapshot's size on every rank.  The outcome is
+ * collective: every rank returns the same status - the root's when its export fails (nobody applies), otherwise the largest
+ * of the receiving ranks' statuses (staging allocation, VOFOD_ERR_BUSY, and the apply: VOFOD_ERR_DELTA_BASE when a replica
+ * missed a delta), VOFOD_OK when every rank applied.  So a recovery such as "on VOFOD_ERR_DELTA_BASE broadcast a full
+ * snapshot" runs on all ranks together.  Any other export by the root (vofod_map_export, a checkpoint) starts a new chain:
+ * the next delta broadcast then returns VOFOD_ERR_DELTA_BASE everywhere.  Only a failing HIP runtime or RCCL call
+ * (VOFOD_ERR_DEVICE) can end the call on one rank alone. */
+int vofod_broadcast_map(vofod_comm* comm, vofod_handle* h, int32_t root, int32_t maps, int32_t kind, size_t* n_bytes);
 
 #ifdef __cplusplus
 }

@@ -30,11 +30,14 @@ ERR_NOT_PENDING = 10
 ERR_EMPTY = 11
 ERR_MAP_RANGE = 12
 ERR_BUSY = 13
+ERR_DELTA_BASE = 14
 
 MEM_HOST, MEM_DEVICE = 0, 1
 MAP_VOXELS, MAP_FLAGS, MAP_RAYCAST = 0, 1, 2
 SCAN_DEFAULT, SCAN_NO_MAP_UPDATE, SCAN_AUTO_RAYCAST = 0, 1, 2
 CLASS_MAV, CLASS_UNKNOWN, CLASS_INVALID, CLASS_NONE = 0, 1, 2, -1
+SNAPSHOT_DELTA, SNAPSHOT_FULL = 0, 1
+MAPS_ALL = (1 << MAP_VOXELS) | (1 << MAP_FLAGS) | (1 << MAP_RAYCAST)
 
 
 class StaticParams(C.Structure):
@@ -265,12 +268,15 @@ _SIGS = {
     "sim_lut": (C.c_int, [C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "profile_read": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "map_export": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, _P(C.c_size_t)]),
+    "map_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
+    "broadcast_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_size_t)]),
 }
 
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
-                "serialize_profiling_info")
+                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map")
 
 
 class MsgHeader(C.Structure):

@@ -28,6 +28,8 @@ struct Api
   int (*CommInitRank)(Comm*, int, UniqueId, int) = nullptr;
   int (*CommDestroy)(Comm) = nullptr;
   int (*AllGather)(const void*, void*, size_t, int, Comm, hipStream_t) = nullptr;
+  int (*Broadcast)(const void*, void*, size_t, int, int, Comm, hipStream_t) = nullptr;  // (vofod_broadcast_map)
+  int (*AllReduce)(const void*, void*, size_t, int, int, Comm, hipStream_t) = nullptr;  // (vofod_broadcast_map: the ranks' statuses)
   const char* (*GetErrorString)(int) = nullptr;
   void* so = nullptr;
   std::string err;
@@ -47,8 +49,10 @@ struct Api
     CommInitRank = reinterpret_cast<decltype(CommInitRank)>(dlsym(so, "ncclCommInitRank"));
     CommDestroy = reinterpret_cast<decltype(CommDestroy)>(dlsym(so, "ncclCommDestroy"));
     AllGather = reinterpret_cast<decltype(AllGather)>(dlsym(so, "ncclAllGather"));
+    Broadcast = reinterpret_cast<decltype(Broadcast)>(dlsym(so, "ncclBroadcast"));
+    AllReduce = reinterpret_cast<decltype(AllReduce)>(dlsym(so, "ncclAllReduce"));
     GetErrorString = reinterpret_cast<decltype(GetErrorString)>(dlsym(so, "ncclGetErrorString"));
-    if (!GetUniqueId || !CommInitRank || !CommDestroy || !AllGather)
+    if (!GetUniqueId || !CommInitRank || !CommDestroy || !AllGather || !Broadcast || !AllReduce)
     {
       err = "RCCL library lacks an expected entry point";
       return false;
@@ -79,6 +83,7 @@ struct vofod_comm
   hipStream_t stream = nullptr;
   char *d_send = nullptr, *d_recv = nullptr, *h_stage = nullptr;  // h_stage: pinned, send slot followed by the receive area
   size_t cap_bytes = 0;  // per-rank payload the buffers are sized for
+  uint64_t *d_ctl = nullptr, *h_ctl = nullptr;  // vofod_broadcast_map's control words (device / pinned), allocated with the communicator
   std::mutex mtx;
   std::string err;
 };
@@ -125,14 +130,21 @@ int vofod_comm_create(const uint8_t id[VOFOD_COMM_ID_BYTES], int32_t rank, int32
   const bool comm_ok = vcoll::api().CommInitRank(&c->comm, n_ranks, u, rank) == 0;
   if (!comm_ok)
     c->comm = nullptr;
-  if (!comm_ok || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
+  bool stream_ok = comm_ok && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
+  if (!stream_ok)
+    c->stream = nullptr;
+  bool ctl_ok = stream_ok && hipMalloc(reinterpret_cast<void**>(&c->d_ctl), 4 * sizeof(uint64_t)) == hipSuccess;
+  if (!ctl_ok)
+    c->d_ctl = nullptr;
+  ctl_ok = ctl_ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_ctl), 4 * sizeof(uint64_t)) == hipSuccess;
+  if (!ctl_ok)
   {
+    c->h_ctl = nullptr;
     {
       std::scoped_lock lck(vcoll::load_mutex());
-      vcoll::api().err = comm_ok ? "hipStreamCreate failed" : "ncclCommInitRank failed";
+      vcoll::api().err = !comm_ok ? "ncclCommInitRank failed" : !stream_ok ? "hipStreamCreate failed" : "control word allocation failed";
     }
-    c->stream = nullptr;
-    vofod_comm_destroy(c);  // releases the communicator when only the stream failed
+    vofod_comm_destroy(c);  // releases the communicator when only the stream or the control words failed
     return VOFOD_ERR_DEVICE;
   }
   *out = c;
@@ -152,6 +164,10 @@ void vofod_comm_destroy(vofod_comm* c)
     (void)hipFree(c->d_recv);
   if (c->h_stage)
     (void)hipHostFree(c->h_stage);
+  if (c->d_ctl)
+    (void)hipFree(c->d_ctl);
+  if (c->h_ctl)
+    (void)hipHostFree(c->h_ctl);
   if (c->stream)
     (void)hipStreamDestroy(c->stream);
   delete c;

@@ -30,6 +30,7 @@
 #include "kernels_tail.h"
 #include "kernels_far.h"
 #include "kernels_voxelize.h"
+#include "mapsync.h"
 
 using namespace vk;
 
@@ -627,6 +628,7 @@ struct vofod_handle
   bool raycast_pending = false;
   int raycast_start_its = 0;
   vr::SepState sep;
+  MapSyncState msync;  // snapshots / deltas of the maps (mapsync.h, mapsync_host.h)
   bool sep_pending = false;
   int sep_start_its = 0;
 };
@@ -2954,3 +2956,4 @@ int process_frames(vofod_handle* h, Workspace& ws, FramesPhase phase, const vofo
 
 #include "driver_aux.h"
 #include "collective.h"
+#include "mapsync_host.h"

@@ -165,6 +165,38 @@ class VoFOD:
         a = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
         self._check(self.lib.write_map(self.h, which, capi.ptr(a), a.size), "vofod_write_map")
 
+    # ------------------------------------------------- snapshots and deltas
+    def export_map(self, maps: int = capi.MAPS_ALL, full: bool = True) -> np.ndarray:
+        """A full snapshot or a delta of the maps in `maps` (bitmask of 1 << capi.MAP_*) in the wire format of
+        vofod_amd.mapsync (uint8).  A delta follows the last export of the same mask (VofodError ERR_DELTA_BASE without one)."""
+        kind = capi.SNAPSHOT_FULL if full else capi.SNAPSHOT_DELTA
+        n = C.c_size_t(0)
+        self._check(self.lib.map_export(self.h, int(maps), kind, None, 0, capi.MEM_HOST, C.byref(n)), "vofod_map_export")
+        while True:
+            buf = np.empty(n.value, dtype=np.uint8)
+            st = self.lib.map_export(self.h, int(maps), kind, capi.ptr(buf), buf.size, capi.MEM_HOST, C.byref(n))
+            if st == capi.ERR_CAPACITY and n.value > buf.size:
+                continue  # (the map changed between the size query and the export: another thread's scan)
+            self._check(st, "vofod_map_export")
+            return buf[: n.value]
+
+    def apply_map(self, buf) -> None:
+        """apply a snapshot or delta (bytes / uint8 array from export_map, a file or another process)"""
+        b = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else buf, dtype=np.uint8).reshape(-1)
+        self._check(self.lib.map_apply(self.h, capi.ptr(b), b.size, capi.MEM_HOST), "vofod_map_apply")
+
+    def save_map(self, path, maps: int = capi.MAPS_ALL, full: bool = True) -> int:
+        """checkpoint: export_map written to `path`; returns its size in bytes"""
+        buf = self.export_map(maps, full)
+        with open(path, "wb") as f:
+            f.write(buf.tobytes())
+        return buf.size
+
+    def load_map(self, path) -> None:
+        """restore a checkpoint written by save_map (a full snapshot, or the next delta of the chain applied last)"""
+        with open(path, "rb") as f:
+            self.apply_map(f.read())
+
     # ------------------------------------------------------------- hot path
     def _mk_dbg(self, n_points: int, clusters_cap: int | None = None):
         """debug buffers of one frame; `clusters_cap` bounds the cluster table (default: one per point, the worst case)"""

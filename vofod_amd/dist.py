@@ -104,10 +104,105 @@ class CabiComm:
             raise RuntimeError(f"vofod_allgather_detections: status {st}: {self.lib.comm_last_error(self.h).decode()}")
         return out, cnt
 
+    def broadcast_map(self, det, root: int = 0, maps: int = capi.MAPS_ALL, full: bool = True) -> int:
+        """vofod_broadcast_map: `root`'s map (full snapshot or next delta) to every rank's `det` (a VoFOD on this
+        communicator's device), device-resident with RCCL.  Collective; returns the snapshot's size in bytes."""
+        import ctypes as C
+
+        from .detector import VofodError
+
+        n = C.c_size_t(0)
+        kind = capi.SNAPSHOT_FULL if full else capi.SNAPSHOT_DELTA
+        st = self.lib.broadcast_map(self.h, det.h, int(root), int(maps), kind, C.byref(n))
+        if st != capi.OK:
+            msg = self.lib.last_error_string(det.h)
+            raise VofodError(st, "vofod_broadcast_map", msg.decode() if msg else "")
+        return n.value
+
     def close(self):
         if self.h:
             self.lib.comm_destroy(self.h)
             self.h = None
+
+
+def broadcast_map_bytes(buf, root: int, status: int = capi.OK, device=None) -> np.ndarray:
+    """Ship a map snapshot (uint8 array from VoFOD.export_map) from `root` to every rank over torch.distributed: a control word
+    (status, size) first, then the payload.  The root passes its buffer (or None with a non-OK `status` when its export
+    failed), the other ranks None.  Returns the bytes on every rank; when the root's status is not OK every rank raises
+    VofodError with that status and no payload is sent.  `device`: where the tensors live (default: cpu for gloo, the current
+    GPU for nccl)."""
+    import torch
+    import torch.distributed as dist
+
+    from .detector import VofodError
+
+    device = _device(device)
+    me = dist.get_rank()
+    ctl = torch.zeros(2, dtype=torch.int64)
+    if me == root:
+        if status == capi.OK and buf is None:
+            raise ValueError("the root must pass its snapshot (or a non-OK status)")
+        ctl[0] = int(status)
+        ctl[1] = int(np.asarray(buf).size) if status == capi.OK else 0
+    ctl = ctl.to(device)
+    dist.broadcast(ctl, src=root)
+    st, n = (int(v) for v in ctl.cpu())
+    if st != capi.OK:
+        raise VofodError(st, "broadcast_map_bytes", f"the export on rank {root} failed")
+    if me == root:
+        payload = torch.from_numpy(np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1).copy()).to(device)
+    else:
+        payload = torch.empty(n, dtype=torch.uint8, device=device)
+    if n:
+        dist.broadcast(payload, src=root)
+    return payload.cpu().numpy()
+
+
+def _device(device):
+    import torch
+    import torch.distributed as dist
+
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    return device
+
+
+def agree_status(local: int, device=None) -> int:
+    """The largest of every rank's status (capi.OK = 0 when all are ok), on every rank: one all-reduce (max)."""
+    import torch
+    import torch.distributed as dist
+
+    t = torch.tensor([int(local)], dtype=torch.int64).to(_device(device))
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return int(t.cpu()[0])
+
+
+def broadcast_map(det, root: int, maps: int = capi.MAPS_ALL, full: bool = True, device=None) -> int:
+    """Refresh every rank's replica from `root`'s map over torch.distributed: the root exports (full snapshot or the next
+    delta of its chain), the other ranks apply.  Collective, with a collective outcome: when the root's export or any rank's
+    apply fails, every rank raises VofodError with the same status (the largest) - a replica that missed a delta
+    (ERR_DELTA_BASE) makes every rank see it, so all of them can go on with a full snapshot.  Returns the size in bytes."""
+    import torch.distributed as dist
+
+    from .detector import VofodError
+
+    buf, st = None, capi.OK
+    if dist.get_rank() == root:
+        try:
+            buf = det.export_map(maps, full)
+        except VofodError as e:
+            st = e.status
+    data = broadcast_map_bytes(buf, root, st, device)  # (raises on every rank when the export failed)
+    local, detail = capi.OK, ""
+    if dist.get_rank() != root:
+        try:
+            det.apply_map(data)
+        except VofodError as e:
+            local, detail = e.status, str(e)
+    st = agree_status(local, device)
+    if st != capi.OK:
+        raise VofodError(st, "broadcast_map", detail or "the apply failed on another rank")
+    return int(data.size)
 
 
 def torch_bootstrap(device):

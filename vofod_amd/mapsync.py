@@ -1,0 +1,146 @@
+"""The wire format of the map snapshots and deltas (include/vofod.h, vofod_map_export / vofod_map_apply) in plain numpy.
+
+Independent of the library: `encode` builds the bytes the library writes, `decode` reads and checks them.  Little endian: a
+128-byte header, then for each selected map (voxels, flags, raycast in that order) u32 idx[n] followed by u32 bits[n].
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+
+import numpy as np
+
+MAGIC = 0x444D4656  # "VFMD"
+VERSION = 1
+HEADER_BYTES = 128
+KIND_DELTA, KIND_FULL = 0, 1
+MAP_VOXELS, MAP_FLAGS, MAP_RAYCAST = 0, 1, 2
+MAPS_ALL = (1 << MAP_VOXELS) | (1 << MAP_FLAGS) | (1 << MAP_RAYCAST)
+
+HEADER = np.dtype(
+    {
+        "names": ["magic", "version", "maps", "kind", "map_size", "map_offset", "voxel_size", "score_init", "base_gen", "new_gen", "detection_its",
+                  "last_detection_id", "background_pts_sufficient", "sure_background_sufficient", "raycast_pending", "raycast_start_its", "n_records", "zero"],
+        "formats": ["<u4", "<u4", "<u4", "<u4", ("<i4", 3), ("<f4", 3), "<f4", "<f4", "<u8", "<u8", "<i4", "<u4", "<i4", "<i4", "<i4", "<i4", ("<u8", 3), ("u1", 16)],
+        "offsets": [0, 4, 8, 12, 16, 28, 40, 44, 48, 56, 64, 68, 72, 76, 80, 84, 88, 112],
+        "itemsize": HEADER_BYTES,
+    }
+)
+
+STATE_FIELDS = ("detection_its", "last_detection_id", "background_pts_sufficient", "sure_background_sufficient", "raycast_pending", "raycast_start_its")
+
+
+@dataclass
+class Snapshot:
+    maps: int
+    kind: int
+    map_size: tuple
+    map_offset: tuple
+    voxel_size: float
+    score_init: float
+    base_gen: int = 0
+    new_gen: int = 0
+    detection_its: int = 0
+    last_detection_id: int = 0
+    background_pts_sufficient: int = 0
+    sure_background_sufficient: int = 0
+    raycast_pending: int = 0
+    raycast_start_its: int = 0
+    records: dict = field(default_factory=dict)  # map -> (idx uint32[n], bits uint32[n]) for every selected map
+
+    @property
+    def n_voxels(self) -> int:
+        return int(np.prod(np.asarray(self.map_size, dtype=np.int64)))
+
+
+def nbytes(counts) -> int:
+    """size of a snapshot with these record counts"""
+    return HEADER_BYTES + 8 * int(sum(int(c) for c in counts))
+
+
+def init_bits(which: int, score_init: float) -> np.uint32:
+    """bit pattern of a map's init state: score_init for the voxel map, 0.0f for flags and raycast"""
+    v = np.float32(score_init if which == MAP_VOXELS else 0.0)
+    return v.view(np.uint32)
+
+
+def diff_records(cur: np.ndarray, base) -> tuple[np.ndarray, np.ndarray]:
+    """(idx, bits) of the voxels of float32 map `cur` whose bits differ from `base`: a float32 map of the same size, or the
+    uint32 bit pattern of an init state (init_bits)"""
+    c = np.ascontiguousarray(cur, dtype=np.float32).reshape(-1).view(np.uint32)
+    b = np.ascontiguousarray(base, dtype=np.float32).reshape(-1).view(np.uint32) if np.ndim(base) else np.uint32(base)
+    idx = np.flatnonzero(c != b).astype(np.uint32)
+    return idx, c[idx]
+
+
+def encode(s: Snapshot) -> np.ndarray:
+    """the bytes of snapshot `s` (uint8)"""
+    h = np.zeros(1, dtype=HEADER)
+    h["magic"], h["version"], h["maps"], h["kind"] = MAGIC, VERSION, s.maps, s.kind
+    h["map_size"], h["map_offset"] = np.asarray(s.map_size, dtype=np.int32), np.asarray(s.map_offset, dtype=np.float32)
+    h["voxel_size"], h["score_init"], h["base_gen"], h["new_gen"] = s.voxel_size, s.score_init, s.base_gen, s.new_gen
+    for k in STATE_FIELDS:
+        h[k] = getattr(s, k)
+    parts = []
+    counts = [0, 0, 0]
+    for m in range(3):
+        if not (s.maps >> m) & 1:
+            continue
+        idx, bits = s.records.get(m, (np.zeros(0, np.uint32), np.zeros(0, np.uint32)))
+        idx = np.ascontiguousarray(idx, dtype="<u4")
+        bits = np.ascontiguousarray(bits, dtype="<u4") if np.asarray(bits).dtype != np.float32 else np.ascontiguousarray(bits, dtype="<f4").view("<u4")
+        assert idx.shape == bits.shape
+        counts[m] = idx.size
+        parts += [idx.view(np.uint8), bits.view(np.uint8)]
+    h["n_records"] = counts
+    return np.concatenate([h.view(np.uint8).reshape(-1)] + parts)
+
+
+def decode(buf, check: bool = True) -> Snapshot:
+    """parse a snapshot; ValueError on a bad magic / version / length / mask, or (check) indices not strictly ascending or >= M"""
+    b = np.frombuffer(memoryview(buf), dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    if b.size < HEADER_BYTES:
+        raise ValueError(f"map snapshot: {b.size} bytes, shorter than the {HEADER_BYTES}-byte header")
+    h = b[:HEADER_BYTES].view(HEADER)[0]
+    if int(h["magic"]) != MAGIC:
+        raise ValueError(f"map snapshot: bad magic {int(h['magic']):#x}")
+    if int(h["version"]) != VERSION:
+        raise ValueError(f"map snapshot: unknown version {int(h['version'])}")
+    maps, kind = int(h["maps"]), int(h["kind"])
+    if maps == 0 or maps & ~MAPS_ALL or kind not in (KIND_DELTA, KIND_FULL):
+        raise ValueError(f"map snapshot: bad maps mask {maps} or kind {kind}")
+    counts = [int(c) for c in h["n_records"]]
+    if any(counts[m] and not (maps >> m) & 1 for m in range(3)):
+        raise ValueError("map snapshot: records for a map outside the mask")
+    if b.size != nbytes(counts):
+        raise ValueError(f"map snapshot: {b.size} bytes, the header asks for {nbytes(counts)}")
+    s = Snapshot(maps=maps, kind=kind, map_size=tuple(int(v) for v in h["map_size"]), map_offset=tuple(float(v) for v in h["map_offset"]),
+                 voxel_size=float(h["voxel_size"]), score_init=float(h["score_init"]), base_gen=int(h["base_gen"]), new_gen=int(h["new_gen"]))
+    for k in STATE_FIELDS:
+        setattr(s, k, int(h[k]))
+    off = HEADER_BYTES
+    n_vox = s.n_voxels
+    for m in range(3):
+        if not (maps >> m) & 1:
+            continue
+        n = counts[m]
+        idx = b[off : off + 4 * n].view("<u4").copy()
+        bits = b[off + 4 * n : off + 8 * n].view("<u4").copy()
+        off += 8 * n
+        if check and n and (np.any(idx[1:] <= idx[:-1]) or int(idx[-1]) >= n_vox):
+            raise ValueError(f"map snapshot: indices of map {m} not strictly ascending or outside the map")
+        s.records[m] = (idx, bits)
+    return s
+
+
+def apply_to(s: Snapshot, maps: dict) -> dict:
+    """what applying `s` does to plain arrays: `maps` {which: float32 array of M} -> the new arrays (numpy statement of the
+    library's apply; a full snapshot starts from the init state)"""
+    out = dict(maps)
+    for m, (idx, bits) in s.records.items():
+        if s.kind == KIND_FULL:
+            cur = np.full(s.n_voxels, init_bits(m, s.score_init), dtype=np.uint32)
+        else:
+            cur = np.ascontiguousarray(maps[m], dtype=np.float32).reshape(-1).view(np.uint32).copy()
+        cur[idx] = bits
+        out[m] = cur.view(np.float32)
+    return out
