@@ -263,8 +263,7 @@ int vofod_allgather_detections(vofod_comm* c, const vofod_detection* local, cons
     c->cap_bytes = bytes;
   }
   // pack: the frame's detections (in order) at the head of its slot, the count behind them
-  if (const int pr = vofod_pack_detection_slots(local, n_per_frame, frames_per_rank, d_max, c->h_stage); pr != VOFOD_OK)
-    return pr;
+  VCHK(vofod_pack_detection_slots(local, n_per_frame, frames_per_rank, d_max, c->h_stage));
   COLLCHK(hipMemcpyAsync(c->d_send, c->h_stage, bytes, hipMemcpyHostToDevice, c->stream));
   if (const int r = vcoll::api().AllGather(c->d_send, c->d_recv, bytes, 0 /* ncclChar */, c->comm, c->stream); r != 0)
   {
@@ -275,8 +274,7 @@ int vofod_allgather_detections(vofod_comm* c, const vofod_detection* local, cons
   COLLCHK(hipMemcpyAsync(h_recv, c->d_recv, bytes * c->n_ranks, hipMemcpyDeviceToHost, c->stream));
   COLLCHK(hipStreamSynchronize(c->stream));
 #undef COLLCHK
-  if (const int ur = vofod_unpack_detection_slots(h_recv, static_cast<size_t>(c->n_ranks) * frames_per_rank, d_max, all, all_counts); ur != VOFOD_OK)
-    return ur;
+  VCHK(vofod_unpack_detection_slots(h_recv, static_cast<size_t>(c->n_ranks) * frames_per_rank, d_max, all, all_counts));
   return VOFOD_OK;
 }
 

@@ -104,9 +104,7 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
   // m_voxel_raycast.clear() :1430 — the sweep leaves it zeroed; clear only if an earlier pass was abandoned
   if (h->ray_dirty)
   {
-    const int r = fill_map(h, h->d_ray, 0.0f);
-    if (r != VOFOD_OK)
-      return r;
+    VCHK(fill_map(h, h->d_ray, 0.0f));
   }
   h->ray_dirty = true;
   HIPCHK(hipMemsetAsync(h->d_counter + 1, 0, sizeof(unsigned long long), h->stream));
@@ -176,41 +174,40 @@ int raycast_finish_locked(vofod_handle* h)
 int counted_tail(vofod_handle* h, Workspace& ws, uint32_t V, uint32_t P, const uint32_t* d_sure_flags)
 {
   vr::SepState& s = h->sep;
-  int r = gscan(h, d_sure_flags, P, s.d_sure_pre, s.d_bsum, nullptr);
-  if (r != VOFOD_OK)
-    return r;
+  VCHK(gscan(h, d_sure_flags, P, s.d_sure_pre, s.d_bsum, nullptr));
   KLAUNCH(h, vr::k_voxel_counts, dim3((V + 255) / 256), dim3(256), ws.d_hdrs, ws.va.pts, s.d_vcnt);
-  r = gscan(h, s.d_vcnt, V, s.d_first, s.d_bsum, nullptr);
-  if (r != VOFOD_OK)
-    return r;
+  VCHK(gscan(h, s.d_vcnt, V, s.d_first, s.d_bsum, nullptr));
   KLAUNCH(h, vr::k_counted_range, dim3((V + 255) / 256), dim3(256), ws.d_hdrs, s.d_first, s.d_sure_pre, P, ws.va.pts);
   HIPCHK(hipGetLastError());
   return VOFOD_OK;
 }
 
+// grows a workspace (Workspace::ensure); a failed allocation becomes the handle's error text
+int grow_workspace(vofod_handle* h, Workspace& ws, const char* what, uint32_t F, uint32_t pt_cap, uint32_t vox_cap, uint32_t words_cap, uint32_t bricks_cap = 0)
+{
+  if (hipError_t e = ws.ensure(F, pt_cap, vox_cap, words_cap, bricks_cap); e != hipSuccess)
+  {
+    h->err = std::string(what) + hipGetErrorString(e);
+    return VOFOD_ERR_DEVICE;
+  }
+  return VOFOD_OK;
+}
+
 // voxelise one device/host cloud into `ws` (frame 0), growing the workspace to the lattice it needs
-int voxelize_cloud(vofod_handle* h, Workspace& ws, const vofod_cloud_view* in, GridParams& g, const float leaf[3], bool align, const float* align_center, FrameHdr& hdr)
+int voxelize_cloud(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const vofod_cloud_view* in, GridParams& g, const float leaf[3], bool align, const float* align_center, FrameHdr& hdr)
 {
   const uint32_t n = static_cast<uint32_t>(in->n);
   // Growth with headroom: a workspace grows by releasing and allocating its three dozen arrays (2.6 ms), and the cloud of
   // updateSeparatedBGClusters - the map's background voxels - gains a few thousand points from one call to the next while the map
   // warms: sized to the point, EVERY call of the role paid that (VOFOD_TRACE: 2.7 of the role's 2.9 ms).
   const uint32_t want = n > std::min(ws.pt_cap, ws.vox_cap) ? n + n / 2 + 4096u : std::max(n, 1u);
-  if (hipError_t e = ws.ensure(1, want, want, std::max(ws.words_cap, 1u << 16)); e != hipSuccess)
-  {
-    h->err = std::string("workspace allocation: ") + hipGetErrorString(e);
-    return VOFOD_ERR_DEVICE;
-  }
+  VCHK(grow_workspace(h, ws, "workspace allocation: ", 1, want, want, std::max(ws.words_cap, 1u << 16)));
   for (int attempt = 0; attempt < 2; attempt++)
   {
-    int r = stage_cloud(h, ws, 0, in->x, in->y, in->z, in->intensity, nullptr, in->stride_bytes, n, in->memspace, 0, nullptr);
-    if (r != VOFOD_OK)
-      return r;
+    VCHK(stage_cloud(h, ws, 0, in->x, in->y, in->z, in->intensity, nullptr, in->stride_bytes, n, in->memspace, 0, nullptr));
     const float zero[3] = {0, 0, 0};
     fill_grid_params(h, g, leaf, align, align ? align_center : zero, ws);
-    r = launch_voxelize(h, ws, g, 1, n, false, true);
-    if (r != VOFOD_OK)
-      return r;
+    VCHK(launch_voxelize(h, ws, lf, g, 1, n, false, true));
     HIPCHK(hipMemcpyAsync(&ws.h_packed[0].hdr, ws.d_hdrs, sizeof(FrameHdr), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     hdr = ws.h_packed[0].hdr;
@@ -218,11 +215,7 @@ int voxelize_cloud(vofod_handle* h, Workspace& ws, const vofod_cloud_view* in, G
         hdr.n_in ? static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>((hdr.div_b[0] + 3) / 4) * ((hdr.div_b[1] + 3) / 4) * ((hdr.div_b[2] + 3) / 4), 1u << 28)) : 0u;
     if ((hdr.status == VOFOD_ERR_CAPACITY || (hdr.status == VOFOD_OK && need_bricks > ws.bricks_cap)) && attempt == 0)
     {
-      if (hipError_t e = ws.ensure(1, n, n, hdr.need_words + hdr.need_words / 4 + 64, need_bricks + need_bricks / 4); e != hipSuccess)
-      {
-        h->err = std::string("workspace allocation: ") + hipGetErrorString(e);
-        return VOFOD_ERR_DEVICE;
-      }
+      VCHK(grow_workspace(h, ws, "workspace allocation: ", 1, n, n, hdr.need_words + hdr.need_words / 4 + 64, need_bricks + need_bricks / 4));
       continue;
     }
     break;
@@ -234,9 +227,7 @@ int voxelize_cloud(vofod_handle* h, Workspace& ws, const vofod_cloud_view* in, G
     hdr.V = 0;
     return VOFOD_OK;
   }
-  int r = launch_voxelize_rest(h, ws, g, 1, n, false);
-  if (r != VOFOD_OK)
-    return r;
+  VCHK(launch_voxelize_rest(h, ws, lf, g, 1, n, false));
   HIPCHK(hipMemcpyAsync(&ws.h_packed[0].hdr, ws.d_hdrs, sizeof(FrameHdr), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   hdr = ws.h_packed[0].hdr;
@@ -267,17 +258,12 @@ int sepclusters_begin_locked(vofod_handle* h, int* sure_out)
     return VOFOD_ERR_INVALID_ARG;
 
   // K16: thresholded voxels in x-outer / z-inner order (voxelsAsVoxelPC :1153)
-  int r = ensure_mapbits(h, thr_new);
-  if (r != VOFOD_OK)
-    return r;
+  VCHK(ensure_mapbits(h, thr_new));
   const uint32_t ncol = static_cast<uint32_t>(h->mg.sx) * h->mg.sy;
-  if ((r = sep_ensure_words(h, ncol + 2)) != VOFOD_OK)
-    return r;
-  if ((r = sep_ensure_pts(h, std::max<size_t>(1 << 16, ncol))) != VOFOD_OK)  // also sizes the scan's block sums
-    return r;
+  VCHK(sep_ensure_words(h, ncol + 2));
+  VCHK(sep_ensure_pts(h, std::max<size_t>(1 << 16, ncol)));  // also sizes the scan's block sums
   KLAUNCH(h, vr::k_col_count, dim3((ncol + 255) / 256), dim3(256), h->mg, h->d_mapbits, s.d_tpop);
-  if ((r = gscan(h, s.d_tpop, ncol, s.d_tprefix, s.d_bsum, s.d_small)) != VOFOD_OK)
-    return r;
+  VCHK(gscan(h, s.d_tpop, ncol, s.d_tprefix, s.d_bsum, s.d_small));
   HIPCHK(hipMemcpyAsync(s.h_small, s.d_small, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   const uint32_t P = s.h_small[0];
@@ -285,8 +271,7 @@ int sepclusters_begin_locked(vofod_handle* h, int* sure_out)
   tr[0] = ms_since(t0);
   if (P == 0)
     return VOFOD_ERR_EMPTY;  // :1155-1159
-  if ((r = sep_ensure_pts(h, P)) != VOFOD_OK)
-    return r;
+  VCHK(sep_ensure_pts(h, P));
   KLAUNCH(h, vr::k_col_emit, dim3((ncol + 255) / 256), dim3(256), h->mg, h->d_map, h->d_mapbits, s.d_tprefix, thr_sure, s.d_px, s.d_py, s.d_pz, s.d_pi, s.d_sure);
 
   // K6': VoxelGridCounted with leaf lsz on the index cloud (:1162-1167)
@@ -300,19 +285,16 @@ int sepclusters_begin_locked(vofod_handle* h, int* sure_out)
   view.memspace = VOFOD_MEM_DEVICE;
   const float leaf[3] = {lsz, lsz, lsz};
   FrameHdr hdr;
-  r = voxelize_cloud(h, h->sepws, &view, s.g, leaf, false, nullptr, hdr);
-  if (r != VOFOD_OK)
-    return r;
+  LaunchFlags lf;  // (of this role's one launch: voxelisation, then the clustering below)
+  VCHK(voxelize_cloud(h, h->sepws, lf, &view, s.g, leaf, false, nullptr, hdr));
   Workspace& ws = h->sepws;
   tr[1] = ms_since(t0);
-  if ((r = counted_tail(h, ws, hdr.V, P, s.d_sure)) != VOFOD_OK)
-    return r;
+  VCHK(counted_tail(h, ws, hdr.V, P, s.d_sure));
   tr[2] = ms_since(t0);
 
   // clusterCloud(vmap_pc_ds, max_voxel_dist) :1171
   const float cmax = static_cast<float>(std::max({h->mg.sx, h->mg.sy, h->mg.sz})) + 2 * lsz;
-  if ((r = launch_cluster(h, ws, s.g, 1, static_cast<float>(max_voxel_dist), cmax)) != VOFOD_OK)
-    return r;
+  VCHK(launch_cluster(h, ws, lf, s.g, 1, static_cast<float>(max_voxel_dist), cmax));
   tr[3] = ms_since(t0);
   // sure voxels per cluster :1175-1183 and the latch :1188-1206
   HIPCHK(hipMemsetAsync(s.d_nsure, 0, sizeof(uint32_t) * std::max(hdr.V, 1u), h->stream));
@@ -766,7 +748,7 @@ int vofod_create(const vofod_static_params* sp, const vofod_dyn_params* dp, vofo
     if (const char* e = std::getenv("VOFOD_TAIL_PRIO"))  // (diagnostics) hi | mid | lo
       prio_tail = e[0] == 'l' ? prio_lo : e[0] == 'm' ? (prio_lo + prio_hi) / 2 : prio_hi;
     CREATE_CHK(hipStreamCreateWithPriority(&h->stream_tail, hipStreamNonBlocking, prio_tail));
-    // staged pipeline of submitted batches (process_frames): streaming kernels below the frame kernels
+    // staged pipeline of submitted batches (launch_frames): streaming kernels below the frame kernels
     CREATE_CHK(hipStreamCreateWithPriority(&h->stream_key, hipStreamNonBlocking, prio_lo));
     // (VOFOD_FRAME_STREAMS: diagnostics - the number of frame streams, 1..8)
     h->n_frame_streams = 2;  // (more streams cost more than they bring: 811 k / 763 k / 656 k frames/s with 2 / 4 / 8 of them, 32-frame batches 435 k / 268 k / 216 k)
@@ -893,8 +875,7 @@ int vofod_reset(vofod_handle* h)
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, true); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, true));
   const int r = do_reset(h);
   h->sure_background_sufficient = false;
   h->background_pts_sufficient = false;
@@ -938,8 +919,7 @@ int vofod_load_apriori(vofod_handle* h, const float* xyz, size_t n)
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, true); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, true));
   if (n)
   {
     float* d = nullptr;
@@ -993,12 +973,10 @@ int vofod_voxels_as_pc(vofod_handle* h, int which, float threshold, int greater_
   *n_out = 0;
   vr::SepState& s = h->sep;
   const uint32_t ncol = static_cast<uint32_t>(h->mg.sx) * h->mg.sy;
-  int r;
-  if ((r = sep_ensure_words(h, ncol + 2)) != VOFOD_OK || (r = sep_ensure_pts(h, std::max<size_t>(1 << 16, ncol))) != VOFOD_OK)
-    return r;
+  VCHK(sep_ensure_words(h, ncol + 2));
+  VCHK(sep_ensure_pts(h, std::max<size_t>(1 << 16, ncol)));
   KLAUNCH(h, vr::k_col_count_thr, dim3((ncol + 255) / 256), dim3(256), h->mg, m, threshold, greater_than, s.d_tpop);
-  if ((r = gscan(h, s.d_tpop, ncol, s.d_tprefix, s.d_bsum, s.d_small)) != VOFOD_OK)
-    return r;
+  VCHK(gscan(h, s.d_tpop, ncol, s.d_tprefix, s.d_bsum, s.d_small));
   HIPCHK(hipMemcpyAsync(s.h_small, s.d_small, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   const uint32_t P = s.h_small[0];
@@ -1007,8 +985,7 @@ int vofod_voxels_as_pc(vofod_handle* h, int which, float threshold, int greater_
     return VOFOD_ERR_CAPACITY;  // n_out holds the required size
   if (P == 0)
     return VOFOD_OK;
-  if ((r = ensure_boxstage(h, static_cast<size_t>(P) * 4)) != VOFOD_OK)
-    return r;
+  VCHK(ensure_boxstage(h, static_cast<size_t>(P) * 4));
   KLAUNCH(h, vr::k_col_emit_xyzi, dim3((ncol + 255) / 256), dim3(256), h->mg, m, threshold, greater_than, s.d_tprefix, P, reinterpret_cast<float4*>(h->d_boxstage));
   HIPCHK(hipMemcpyAsync(out, h->d_boxstage, sizeof(vofod_point_xyzi) * P, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1021,8 +998,7 @@ int vofod_update_ground(vofod_handle* h, float range, float min_range, float max
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, false, true); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, false, true));
   if (range <= min_range && range >= max_range)  // vofod_nodelet.cpp:585, as written
     return VOFOD_OK;
   // one voxel at the range-finder's rate: read, blend on the host in the reference's double expression, write back
@@ -1047,8 +1023,7 @@ int vofod_write_map(vofod_handle* h, int which, const float* src, size_t n)
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, false, true); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, false, true));
   float* m = pick_map(h, which);
   if (!m || n != h->mg.n)
     return VOFOD_ERR_SIZE_MISMATCH;
@@ -1064,15 +1039,11 @@ int vofod_process_scan(vofod_handle* h, const vofod_scan* scan, const float tf[1
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, !(flags & VOFOD_SCAN_NO_MAP_UPDATE)); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, !(flags & VOFOD_SCAN_NO_MAP_UPDATE)));
   *n_out = 0;
-  int r = process_frames(h, h->ws, FRAMES_SYNC, scan, tf, 1, flags, out, cap, nullptr, n_out, dbg);
-  // (a cold map: more far voxels than the close-first path of a single scan takes - nothing of the scan was applied; once more,
-  // through the full clustering)
-  if (r == CCL_RETRY_STATUS)
-    r = process_frames(h, h->ws, FRAMES_SYNC, scan, tf, 1, flags, out, cap, nullptr, n_out, dbg);
-  return r;
+  // (a cold map: more far voxels than the close-first path of a single scan takes - nothing of the scan was applied; it runs once
+  // more, through the full clustering)
+  return process_frames(h, scan, tf, 1, flags, out, cap, nullptr, n_out, dbg);
 }
 
 int vofod_process_batch(vofod_handle* h, const vofod_scan* scans, const float* tfs, size_t n, vofod_detection* out, size_t cap, uint32_t* n_out_per_frame, size_t* n_out,
@@ -1082,8 +1053,7 @@ int vofod_process_batch(vofod_handle* h, const vofod_scan* scans, const float* t
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, false); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, false));
   *n_out = 0;
   int ret = VOFOD_OK;
   size_t total = 0;
@@ -1091,13 +1061,8 @@ int vofod_process_batch(vofod_handle* h, const vofod_scan* scans, const float* t
   {
     const uint32_t m = static_cast<uint32_t>(std::min<size_t>(h->ws.F, n - base));
     size_t got = 0;
-    int r = process_frames(h, h->ws, FRAMES_SYNC, scans + base, tfs + 12 * base, m, VOFOD_SCAN_NO_MAP_UPDATE, out ? out + total : nullptr, total < cap ? cap - total : 0,
-                           n_out_per_frame ? n_out_per_frame + base : nullptr, &got, dbg ? dbg + base : nullptr);
-    // a frame beyond the capacities of the frame kernel: this batch once more - with the full clustering when the close-first
-    // kernel gave up (a cold map), on the global kernels when the LDS image did; the two can follow each other
-    for (int attempt = 0; attempt < 2 && r == CCL_RETRY_STATUS; attempt++)
-      r = process_frames(h, h->ws, FRAMES_SYNC, scans + base, tfs + 12 * base, m, VOFOD_SCAN_NO_MAP_UPDATE, out ? out + total : nullptr, total < cap ? cap - total : 0,
-                         n_out_per_frame ? n_out_per_frame + base : nullptr, &got, dbg ? dbg + base : nullptr);
+    const int r = process_frames(h, scans + base, tfs + 12 * base, m, VOFOD_SCAN_NO_MAP_UPDATE, out ? out + total : nullptr, total < cap ? cap - total : 0,
+                                 n_out_per_frame ? n_out_per_frame + base : nullptr, &got, dbg ? dbg + base : nullptr);
     for (size_t i = total; i < std::min(total + got, cap); i++)
       out[i].frame += static_cast<uint32_t>(base);
     total += got;
@@ -1143,14 +1108,9 @@ int vofod_batch_submit(vofod_handle* h, const vofod_scan* scans, const float* tf
   }
   Workspace* w = h->slot(t);
   if (w->F == 0)
-  {
-    if (hipError_t e = w->ensure(h->ws.F, h->ws.pt_cap, h->ws.vox_cap, h->ws.words_cap, h->ws.bricks_cap); e != hipSuccess)
-    {
-      h->err = std::string("extra workspace: ") + hipGetErrorString(e);
-      return VOFOD_ERR_DEVICE;
-    }
-  }
-  const int r = process_frames(h, *w, FRAMES_LAUNCH, scans, tfs, static_cast<uint32_t>(n), VOFOD_SCAN_NO_MAP_UPDATE, nullptr, 0, nullptr, nullptr, nullptr);
+    VCHK(grow_workspace(h, *w, "extra workspace: ", h->ws.F, h->ws.pt_cap, h->ws.vox_cap, h->ws.words_cap, h->ws.bricks_cap));
+  FrameCall call{true, scans, tfs, static_cast<uint32_t>(n), VOFOD_SCAN_NO_MAP_UPDATE, nullptr};
+  const int r = launch_frames(h, *w, call);
   if (r == VOFOD_OK)
     *ticket = t;
   return r;
@@ -1166,22 +1126,16 @@ int vofod_reserve(vofod_handle* h, int tickets)
   {
     Workspace* w = h->slot(t);
     if (w->F == 0)
-      if (hipError_t e = w->ensure(h->ws.F, h->ws.pt_cap, h->ws.vox_cap, h->ws.words_cap, h->ws.bricks_cap); e != hipSuccess)
-      {
-        h->err = std::string("extra workspace: ") + hipGetErrorString(e);
-        return VOFOD_ERR_DEVICE;
-      }
+      VCHK(grow_workspace(h, *w, "extra workspace: ", h->ws.F, h->ws.pt_cap, h->ws.vox_cap, h->ws.words_cap, h->ws.bricks_cap));
     if (t > 0 && !h->chain_stream[t])
       HIPCHK(hipStreamCreateWithFlags(&h->chain_stream[t], hipStreamNonBlocking));
   }
   // the device tail's flood-fill buffers: shared by the batches of 128 frames and more (their tails take turns on the tail
-  // stream), per ticket for smaller batches (process_frames sizes those by the batch; reserved here for full workspaces)
-  if (const int r = ensure_explore(h, h->explore, h->ws.F, static_cast<size_t>(h->ws.F) * vtd::TP_MAXC, static_cast<size_t>(h->ws.F) * vtd::TP_MAXM); r != VOFOD_OK)
-    return r;
+  // stream), per ticket for smaller batches (launch_device_tail sizes those by the batch; reserved here for full workspaces)
+  VCHK(ensure_explore(h, h->explore, h->ws.F, static_cast<size_t>(h->ws.F) * vtd::TP_MAXC, static_cast<size_t>(h->ws.F) * vtd::TP_MAXM));
   if (h->ws.F < 128u)
     for (int t = 0; t < tickets; t++)
-      if (const int r = ensure_explore(h, h->explore_slot[t], h->ws.F, static_cast<size_t>(h->ws.F) * vtd::TP_MAXC, static_cast<size_t>(h->ws.F) * vtd::TP_MAXM); r != VOFOD_OK)
-        return r;
+      VCHK(ensure_explore(h, h->explore_slot[t], h->ws.F, static_cast<size_t>(h->ws.F) * vtd::TP_MAXC, static_cast<size_t>(h->ws.F) * vtd::TP_MAXM));
   return VOFOD_OK;
 }
 
@@ -1195,16 +1149,17 @@ int vofod_batch_collect(vofod_handle* h, int ticket, vofod_detection* out, size_
   if (!w.pending)
     return VOFOD_ERR_NOT_PENDING;
   *n_out = 0;
-  int r = process_frames(h, w, FRAMES_COLLECT, nullptr, nullptr, 0, VOFOD_SCAN_NO_MAP_UPDATE, out, cap, n_out_per_frame, n_out, nullptr);
-  for (int attempt = 0; attempt < 2 && r == CCL_RETRY_STATUS; attempt++)
-  {
-    // a frame beyond the capacities of the frame kernel: the batch is enqueued again from the submitted descriptors - with the
-    // full clustering when the close-first kernel gave up (a cold map), with the global-memory clustering when the LDS image did
-    r = process_frames(h, w, FRAMES_LAUNCH, w.job_scans.data(), w.job_tfs.data(), w.job_n, VOFOD_SCAN_NO_MAP_UPDATE, nullptr, 0, nullptr, nullptr, nullptr);
-    if (r == VOFOD_OK)
-      r = process_frames(h, w, FRAMES_COLLECT, nullptr, nullptr, 0, VOFOD_SCAN_NO_MAP_UPDATE, out, cap, n_out_per_frame, n_out, nullptr);
-  }
-  return r;
+  auto collect = [&] {  // (the inputs as the launch half left them in the workspace)
+    FrameCall call{true, nullptr, w.job_tfs.data(), w.job_n, VOFOD_SCAN_NO_MAP_UPDATE, nullptr, &w.job_dp, w.job_g};
+    return collect_frames(h, w, call, out, cap, n_out_per_frame, n_out);
+  };
+  // (a batch that has to run again is enqueued from the submitted descriptors)
+  auto again = [&] {
+    FrameCall call{true, w.job_scans.data(), w.job_tfs.data(), w.job_n, VOFOD_SCAN_NO_MAP_UPDATE, nullptr};
+    const int r = launch_frames(h, w, call);
+    return r != VOFOD_OK ? r : collect();
+  };
+  return with_reruns(collect, again);
 }
 
 int vofod_raycast_begin(vofod_handle* h, const vofod_scan* scan, const float tf[12])
@@ -1213,8 +1168,7 @@ int vofod_raycast_begin(vofod_handle* h, const vofod_scan* scan, const float tf[
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, false); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, false));
   return raycast_begin_locked(h, scan, tf);
 }
 
@@ -1224,8 +1178,7 @@ int vofod_raycast_finish(vofod_handle* h)
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, false, true); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, false, true));
   return raycast_finish_locked(h);
 }
 
@@ -1235,8 +1188,7 @@ int vofod_sepclusters_begin(vofod_handle* h, int* sure)
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, false); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, false));
   return sepclusters_begin_locked(h, sure);
 }
 
@@ -1246,8 +1198,7 @@ int vofod_sepclusters_finish(vofod_handle* h)
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, true); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, true));
   return sepclusters_finish_locked(h);
 }
 
@@ -1258,8 +1209,7 @@ int vofod_voxel_grid_weighted(vofod_handle* h, const vofod_cloud_view* in, float
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, false); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, false));
   GridParams g;
   FrameHdr hdr{};
   const float l[3] = {leaf, leaf, leaf};
@@ -1271,7 +1221,8 @@ int vofod_voxel_grid_weighted(vofod_handle* h, const vofod_cloud_view* in, float
       *grid = vofod_grid_desc{{leaf, leaf, leaf}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
     return VOFOD_OK;
   }
-  const int r = voxelize_cloud(h, h->aux, in, g, l, align != 0, align_center, hdr);
+  LaunchFlags lf;
+  const int r = voxelize_cloud(h, h->aux, lf, in, g, l, align != 0, align_center, hdr);
   if (r != VOFOD_OK)
   {
     if (n_out)
@@ -1288,8 +1239,7 @@ int vofod_voxel_grid_counted(vofod_handle* h, const vofod_cloud_view* in, float 
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, false); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, false));
   GridParams g;
   FrameHdr hdr{};
   const float l[3] = {leaf, leaf, leaf};
@@ -1299,7 +1249,8 @@ int vofod_voxel_grid_counted(vofod_handle* h, const vofod_cloud_view* in, float 
       *n_out = 0;
     return VOFOD_OK;
   }
-  int r = voxelize_cloud(h, h->aux, in, g, l, false, nullptr, hdr);
+  LaunchFlags lf;
+  int r = voxelize_cloud(h, h->aux, lf, in, g, l, false, nullptr, hdr);
   if (r != VOFOD_OK)
   {
     if (n_out)
@@ -1307,12 +1258,11 @@ int vofod_voxel_grid_counted(vofod_handle* h, const vofod_cloud_view* in, float 
     return r;
   }
   const uint32_t P = static_cast<uint32_t>(in->n);
-  if ((r = sep_ensure_words(h, 1)) != VOFOD_OK || (r = sep_ensure_pts(h, P)) != VOFOD_OK)
-    return r;
+  VCHK(sep_ensure_words(h, 1));
+  VCHK(sep_ensure_pts(h, P));
   const FrameArgs& a = h->aux.h_args[0];
   KLAUNCH(h, vr::k_flag_over, dim3((P + 255) / 256), dim3(256), a.intensity, a.stride, P, threshold, h->sep.d_sure);
-  if ((r = counted_tail(h, h->aux, hdr.V, P, h->sep.d_sure)) != VOFOD_OK)
-    return r;
+  VCHK(counted_tail(h, h->aux, hdr.V, P, h->sep.d_sure));
   HIPCHK(hipStreamSynchronize(h->stream));
   return copy_grid_out(h, h->aux, g, hdr, out, keys, cap, n_out, grid);
 }
@@ -1324,8 +1274,7 @@ int vofod_cluster(vofod_handle* h, const vofod_point_xyzr* pts, const uint32_t* 
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, true, false); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, true, false));
   if (n_clusters)
     *n_clusters = 0;
   if (n == 0)
@@ -1342,11 +1291,7 @@ int vofod_cluster(vofod_handle* h, const vofod_point_xyzr* pts, const uint32_t* 
   Workspace& ws = h->aux;
   const uint32_t words = static_cast<uint32_t>((cells + 63) / 64);
   const uint32_t need_bricks = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>((grid->div_b[0] + 3) / 4) * ((grid->div_b[1] + 3) / 4) * ((grid->div_b[2] + 3) / 4), 1u << 28));
-  if (hipError_t e = ws.ensure(1, static_cast<uint32_t>(n), static_cast<uint32_t>(n), words + 64, need_bricks); e != hipSuccess)
-  {
-    h->err = std::string("workspace allocation: ") + hipGetErrorString(e);
-    return VOFOD_ERR_DEVICE;
-  }
+  VCHK(grow_workspace(h, ws, "workspace allocation: ", 1, static_cast<uint32_t>(n), static_cast<uint32_t>(n), words + 64, need_bricks));
   // rebuild the frame state the clustering kernels consume: header, bitmap, word prefix, voxel arrays
   GridParams g;
   const float zero[3] = {0, 0, 0};
@@ -1395,9 +1340,8 @@ int vofod_cluster(vofod_handle* h, const vofod_point_xyzr* pts, const uint32_t* 
   float cmax = 0;
   for (int a = 0; a < 3; a++)
     cmax = std::max({cmax, std::fabs(grid->offset[a]), std::fabs(grid->offset[a] + grid->leaf[a] * (grid->div_b[a] + 1))});
-  const int r = launch_cluster(h, ws, g, 1, tolerance, cmax);
-  if (r != VOFOD_OK)
-    return r;
+  LaunchFlags lf;  // (the voxel records came from the caller: no voxelisation stage has left anything for the clustering)
+  VCHK(launch_cluster(h, ws, lf, g, 1, tolerance, cmax));
   HIPCHK(hipMemcpyAsync(labels, ws.d_labels, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (n_clusters)

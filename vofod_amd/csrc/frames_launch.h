@@ -1,0 +1,564 @@
+// Launch half of the per-scan entry points (included by vofod_hip.hip): the body of processMsg (vofod_nodelet.cpp:926-965)
+// for n frames up to the point where the host has to wait - inputs staged, kernel chain and read-back enqueued.
+#pragma once
+
+namespace
+{
+
+// One call of a per-scan entry point: its inputs, and what the launch half leaves for the collect half of the SAME call and
+// nobody else needs.  Owned by the entry point, which fills the inputs; vofod_batch_collect fills one from the ticket.
+struct FrameCall
+{
+  bool submitted;  // vofod_batch_submit / vofod_batch_collect: the two halves run in different API calls
+  const vofod_scan* scans;
+  const float* tfs;
+  uint32_t n;
+  int flags;
+  vofod_scan_debug* dbg;
+  // A submitted batch is classified with the dynamic parameters of its submission: vofod_set_dynamic_params may be called
+  // between submit and collect (DetectionParams.cfg semantics: "between any two calls"), and the collect half (position sigma,
+  // min_points, the host fall-back tail) as well as the re-run of an overflowed batch must not mix the two parameter sets.
+  const vofod_dyn_params* dp = nullptr;
+  GridParams g{};
+  bool rc_done = false;     // ++its and the raycast role of VOFOD_SCAN_AUTO_RAYCAST have run ahead of the device tail
+  bool far_single = false;  // a single map-updating scan clustered close first on the general path (kernels_far.h)
+  hipStream_t tail_stream_used = nullptr;  // where the device tail's last operation was enqueued
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // debug output: stage boundaries on the chain's stream
+  clk::time_point t0 = clk::now();
+  double tr_launch = 0, tr_sync1 = 0;  // VOFOD_TRACE
+  ~FrameCall()  // (the events are destroyed on every return path)
+  {
+    for (auto& x : ev)
+      if (x)
+        (void)hipEventDestroy(x);
+  }
+};
+
+// How a launch is routed.  What differs between a submitted and a synchronous launch is decided here, once.
+struct LaunchRoute
+{
+  bool no_update = false;
+  bool use_dilated = false;       // read-only batches: the map's dilated image answers hasCloseTo with one bit per voxel
+  bool staged = false;            // submitted, 128 frames and more: three-stage pipeline on the streaming / frame / tail streams
+  hipStream_t chain = nullptr;    // submitted: the stream of the chain (the ticket's own, or the streaming stage's); nullptr: the handle's
+  int own_tail = -1;              // submitted small batch: the ticket whose stream and flood-fill buffers the device tail takes
+  bool single_update = false;     // one map-updating scan, synchronous: the reference's own mode
+  bool dtail = false, lite = false;  // device tail / lite read-back (neither: the full tables come back)
+};
+
+// h->stream names the stream every KLAUNCH goes to.  A scope that sends the launches elsewhere (or moves h->stream itself
+// further down) puts it back on every return path.
+struct StreamScope
+{
+  vofod_handle* h;
+  hipStream_t saved;
+  explicit StreamScope(vofod_handle* h_, hipStream_t st = nullptr) : h(h_), saved(h_->stream)
+  {
+    if (st)
+      h->stream = st;
+  }
+  ~StreamScope() { h->stream = saved; }
+};
+
+// which in-flight slot is `ws` (-1: not a ticket's workspace)
+int slot_index(vofod_handle* h, const Workspace& ws)
+{
+  for (int t = 0; t < vofod_handle::MAX_INFLIGHT; t++)
+    if (&ws == h->slot(t))
+      return t;
+  return -1;
+}
+
+inline bool trace_on()
+{
+  static const bool v = std::getenv("VOFOD_TRACE") != nullptr;
+  return v;
+}
+
+// nVoxelsOver as findCloseFarClusters saw it (:715) and the background latch (:716-721).  (n_bg_voxels is the count of the map
+// BEFORE this call's update; counters patched by this very call - bgcount_stale - belong to the next one and are not fetched here)
+int latch_background(vofod_handle* h)
+{
+  if (h->bgcount_fresh)
+  {
+    if (h->ev_bgcount)
+      HIPCHK(hipEventSynchronize(h->ev_bgcount));  // the copy may have been enqueued on another chain's stream
+    uint64_t t = 0;
+    for (int i = 0; i < MB_SLOTS; i++)
+      t += h->h_bgcount[8 * i];
+    h->n_bg_voxels = t;
+    h->bgcount_fresh = false;
+  }
+  if (h->n_bg_voxels > h->background_min_sufficient_pts)
+    h->background_pts_sufficient = true;
+  return VOFOD_OK;
+}
+
+vc::ExploreParams explore_params(const vofod_dyn_params& dp, float thr_new, bool no_update)
+{
+  vc::ExploreParams ep{};
+  ep.thr_unknown = static_cast<float>(dp.voxel_map__thresholds__frontiers);
+  ep.thr_ground = thr_new;
+  ep.frontier_value = static_cast<float>(dp.voxel_map__thresholds__frontiers);
+  ep.ray_score = dp.voxel_map__scores__ray;
+  ep.no_update = no_update ? 1 : 0;
+  ep.stack_cap = vc::EX_CELLS;
+  return ep;
+}
+
+// read-back of the full tables: header, speculative cluster records and candidate members of every frame
+int read_back_full(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t n)
+{
+  KLAUNCH(h, k_pack, fgrid(g, (std::max(SPEC_C, SPEC_M) + 255) / 256), dim3(256), g, ws.d_hdrs, ws.d_table, ws.d_cand, ws.va, ws.d_packed);
+  HIPCHK(hipMemcpyAsync(ws.h_packed, ws.d_packed, sizeof(PackedFrame) * n, hipMemcpyDeviceToHost, h->stream));
+  return VOFOD_OK;
+}
+
+// ---- routing of a submitted launch: which stream its chain takes, where its tail goes
+// In-flight batches on streams of their own overlap their kernel chains: a gain while a batch leaves CUs idle (32 / 64 /
+// 128 frames: +31 / +56 / +16 %), a loss once one batch's kernels fill the chip (256 frames: -6 %, co-running chains only
+// slow each other down).
+// Round 2: the chains are staggered.  A batch's streaming kernels (bounding box, brick codes: HBM bound, a few waves per CU)
+// start when the previous batch's have finished, i.e. while that batch's frame kernel (LDS bound, one workgroup per CU)
+// runs: the two phases of consecutive batches share the chip instead of taking turns.
+// (Rounds 2-3 kept VOFOD_TWO_CHAINS / VOFOD_STAGGER / VOFOD_PIPE / VOFOD_FRAME_STREAMS to switch these schemes off: lost
+// experiments, removed in round 4 with their code paths - DESIGN 5.3 has the measurements.)
+// Submitted batches run as a three-stage pipeline on three streams: the streaming kernels (bounding box + brick codes:
+// vector-instruction bound, a few waves per CU) of every batch on a low-priority stream, the frame kernels (one 156 KB
+// workgroup per CU, latency bound) on a second one, the classification tails on a third (high priority).  The streaming
+// kernels of batch k+1 then fill the issue slots the frame kernel of batch k leaves idle, and when both are ready at the
+// same moment the frame kernel's workgroups are placed first (a CU full of streaming waves has no room for one).
+int route_submitted(vofod_handle* h, const Workspace& ws, uint32_t n, LaunchRoute& rt)
+{
+  // (a batch that leaves most CUs idle - fewer frames than half the CUs - gains more from whole chains running side by
+  // side: its frame kernel shares the chip with the frame kernels of the other batches in flight)
+  if (!h->stream_key || !h->stream_frame || n < 128u)
+  {
+    const int t = slot_index(h, ws);
+    if (t >= 1)
+    {
+      if (!h->chain_stream[t])
+        HIPCHK(hipStreamCreateWithFlags(&h->chain_stream[t], hipStreamNonBlocking));
+      rt.chain = h->chain_stream[t];
+    }
+    // A small submitted batch (fewer frames than half the CUs: its whole chain runs on the ticket's stream) keeps flood-fill
+    // buffers of its own and its tail on that stream: the tails of the batches in flight overlap.  On the shared tail stream
+    // they took turns - k_tail_prep + k_explore + k_tail_finish last 250-280 us in the company of other batches' frame kernels
+    // (120 us alone), and that turn WAS the pace of 32-frame batches (device timeline, tools/trace32.sh).
+    if (n < 128u)
+      rt.own_tail = t;
+  }
+  else
+  {
+    rt.chain = h->stream_key;
+    rt.staged = true;
+  }
+  return VOFOD_OK;
+}
+
+// ---- stage inputs (filterAndTransform :621-684 reads them)
+// (the re-run of a batch that overflowed the LDS kernels keeps the frame arguments and the staged columns of its first
+// launch: the caller's host buffers need not outlive vofod_batch_submit)
+// Host-resident batches whose frames are packed x | y | z columns at a constant pitch (one pcl / numpy block per batch, or
+// per-frame blocks of one arena) cross PCIe with ONE 2-D copy command instead of three per frame: at 256 frames the 768
+// copy calls alone cost more host time than the whole device chain.  The copy is enqueued on the streaming stage's stream:
+// it overlaps the frame kernel and the tail of the batches in front.  (Pinned memory makes it asynchronous; a pageable
+// source is staged by the runtime and blocks the call.)
+// host_copies: some column came from host memory.
+int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const float* tfs, uint32_t n, size_t npts, bool& host_copies)
+{
+  bool staged_2d = false;
+  if (n >= 2 && scans[0].memspace == VOFOD_MEM_HOST)
+  {
+    const char* x0 = static_cast<const char*>(scans[0].x);
+    const ptrdiff_t pitch = static_cast<const char*>(scans[1].x) - x0;
+    bool ok = pitch >= static_cast<ptrdiff_t>(npts * 12);
+    for (uint32_t f = 0; f < n && ok; f++)
+    {
+      const vofod_scan& s = scans[f];
+      const char* xf = x0 + static_cast<ptrdiff_t>(f) * pitch;
+      ok = s.memspace == VOFOD_MEM_HOST && s.stride_bytes == 4 && static_cast<const char*>(s.x) == xf && static_cast<const char*>(s.y) == xf + npts * 4 &&
+           static_cast<const char*>(s.z) == xf + npts * 8;
+    }
+    if (ok && ws.pt_cap == npts)
+    {
+      HIPCHK(hipMemcpy2DAsync(ws.d_stage, sizeof(float) * 5 * ws.pt_cap, x0, static_cast<size_t>(pitch), npts * 12, n, hipMemcpyHostToDevice, h->stream));
+      for (uint32_t f = 0; f < n; f++)
+      {
+        float* base = ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5;
+        VCHK(stage_cloud(h, ws, f, base, base + ws.pt_cap, base + 2 * static_cast<size_t>(ws.pt_cap), nullptr, nullptr, 4, npts, VOFOD_MEM_DEVICE, FA_SCAN, tfs + 12 * f));
+      }
+      staged_2d = true;
+    }
+  }
+  host_copies = staged_2d;
+  for (uint32_t f = 0; f < n && !staged_2d; f++)
+  {
+    const vofod_scan& s = scans[f];
+    host_copies |= s.memspace != VOFOD_MEM_DEVICE;
+    VCHK(stage_cloud(h, ws, f, s.x, s.y, s.z, nullptr, nullptr, s.stride_bytes, npts, s.memspace, FA_SCAN, tfs + 12 * f));
+  }
+  return VOFOD_OK;
+}
+
+// an error return of the launch half must not leave copies from the caller's buffers in flight
+struct H2DGuard
+{
+  hipEvent_t ev;
+  bool armed;
+  ~H2DGuard()
+  {
+    if (armed)
+      (void)hipEventSynchronize(ev);
+  }
+};
+
+// ---- tables and map images of K8/K9 (findCloseFarClusters :703-750): independent of the frames, prepared first
+int prepare_map_images(vofod_handle* h, const vofod_dyn_params& dp, float thr_new, bool use_dilated, bool want_bgcount, CloseParams& cpar)
+{
+  VCHK(ensure_mapbits(h, thr_new));
+  // (a sensor stream's patched nVoxelsOver counters - k_finalize_far of the PREVIOUS scan - are fetched here, before this scan's
+  // own update is enqueued, and only while the count can still change something: the background latch, the debug output)
+  if (want_bgcount)
+    VCHK(refresh_bgcount(h));
+  if (!h->closetab.valid || h->closetab.max_dist != static_cast<float>(dp.ground_points_max_distance))
+  {
+    std::vector<CloseRow> crows;
+    if (const int r = build_close_rows(static_cast<float>(dp.ground_points_max_distance), h->mg.vs_inv, crows); r != VOFOD_OK)
+    {
+      h->err = "ground_points_max_distance / voxel_size exceeds the 63-bit window";
+      return r;
+    }
+    HIPCHK(hipMemcpy(h->d_crows, crows.data(), sizeof(CloseRow) * crows.size(), hipMemcpyHostToDevice));
+    h->closetab.valid = true;
+    h->closetab.max_dist = static_cast<float>(dp.ground_points_max_distance);
+    h->closetab.n_rows = static_cast<int>(crows.size());
+  }
+  cpar = CloseParams{h->closetab.n_rows, thr_new};
+  if (use_dilated)
+    return ensure_mapclose(h, cpar);
+  return VOFOD_OK;
+}
+
+// ---- K1-K6 (filterAndTransform :621-684) - or only the plan of the frame kernel, which reads the input itself
+int voxelize_frames(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams& g, uint32_t n, size_t npts, const vofod_dyn_params& dp, bool no_update, vofod_handle::ClusterTables*& ct)
+{
+  // the clustering family is known up front, so the emission kernel can register the voxels in their bricks
+  VCHK(cluster_tables(h, g, static_cast<float>(dp.ground_points_max_distance), map_cmax(h), &ct));
+  g.sparse_prefix = want_bricks(ct, ws) ? 1u : 0u;
+  // (Fusing the brick registration into k_emit was measured slower - 194 us vs 96 + 50 us for 32 frames: the returning
+  // atomicOr sits inside the load-balanced emission loop - so it stays a kernel of its own.)
+  const bool lds_plan = plan_lds_ccl(h, ct, ws, no_update && n >= 4);
+  h->lds_ccl_off = false;  // one-shot: only the re-run of the batch that overflowed stays off the LDS kernels
+  return launch_voxelize(h, ws, lf, g, n, static_cast<uint32_t>(npts), false, false, nullptr, lds_plan);
+}
+
+// staged pipeline: the chain moves from the streaming stage's stream to a frame stream
+int enter_frame_stream(vofod_handle* h, Workspace& ws)
+{
+  HIPCHK(hipEventRecord(ws.ev_key, h->stream));
+  // Consecutive frame kernels alternate between two streams: frame kernel k+1 waits neither for the LAST workgroup of frame
+  // kernel k (its workgroups take the CUs as those of k retire: frames last 260-350 us) nor for the 14 us launch hand-off
+  // behind it.  Measured +2..4 % (541 / 533 / 533 k against 519 / 510 / 534 k frames/s, alternating runs on one box).
+  // (Measured in rounds 2-4, when a streaming kernel in front of the frame kernel set the pipeline's pace as a guest of the
+  // frame kernels: one wave per SIMD beside a frame workgroup, ~440 us per batch.  The frame kernel reads the input itself now.)
+  h->frame_toggle = (h->frame_toggle + 1) % std::max(h->n_frame_streams, 1);
+  h->stream = h->stream_frames[h->frame_toggle];
+  HIPCHK(hipStreamWaitEvent(h->stream, ws.ev_key, 0));
+  return VOFOD_OK;
+}
+
+// A single map-updating scan without debug output (the reference's own mode) clusters close first on the general path
+// (kernels_far.h): close bits from hasCloseTo's stencil with every voxel as its own cluster, then edges and unions around the
+// far voxels only - instead of the six brick kernels over the whole frame.
+int cluster_far_single(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridParams& g, const vofod_handle::ClusterTables* ct, const vofod_dyn_params& dp, const CloseParams& cpar,
+                       const UpdateParams& up, float thr_new)
+{
+  const uint32_t gv = (ws.vox_cap + 255u) / 256u;
+  uint32_t* far_list = ws.d_labels;  // (labels are not written on this path)
+  KLAUNCH(h, k_closefar, fgrid(g, gv), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, static_cast<const uint32_t*>(nullptr), static_cast<const unsigned long long*>(nullptr), ws.d_cand,
+          ws.d_hdrs);
+  KLAUNCH(h, k_closefar_sweep, fgrid(g, (ws.vox_cap * 16u + 255u) / 256u), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_cand, far_list, ws.d_hdrs, ws.vox_cap);
+  const uint32_t items = FAR_MAX * 2u * static_cast<uint32_t>(ct->n_rows);
+  KLAUNCH(h, k_far_edges, dim3((items + 255u) / 256u), dim3(256), g, ct->cp, ct->d_rows, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va, far_list);
+  KLAUNCH(h, k_far_final, dim3(1), dim3(1024), g, ws.d_hdrs, ws.va, far_list, up, ws.d_table, ws.d_cand);
+  // The occupancy image is patched where the update flips a bit (valid while one voxel of the scan falls into one map cell -
+  // the aligned lattice - and the flood fills' frontier value is no background value: their writes then flip nothing).
+  ws.mapbits_patched = g.align && static_cast<float>(dp.voxel_map__thresholds__frontiers) <= thr_new;
+  KLAUNCH(h, k_finalize_far, dim3(gv), dim3(256), g, h->mg, up, ws.d_hdrs, ws.va, h->d_map, h->d_flags, ws.d_bitmaps, ws.mapbits_patched ? h->d_mapbits : nullptr, h->d_bgcount, thr_new);
+  lf.closefar_fused = true;
+  lf.finalize_fused = true;
+  return VOFOD_OK;
+}
+
+// ---- K8/K9 findCloseFarClusters :703-750 (tables and images were prepared before the chain was enqueued) and
+// ---- K10 updateVMaps :943-950 + cluster table + candidate members: whatever the clustering has not done already
+int closefar_and_finalize(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, const GridParams& g, uint32_t n, const CloseParams& cpar, const UpdateParams& up, bool use_dilated, bool keep_dirty,
+                          vofod_scan_debug* dbg, hipEvent_t* ev)
+{
+  const uint32_t gv = (ws.vox_cap + 255u) / 256u;
+  if (!lf.closefar_fused)
+  {
+    // few frames: the undecided voxels go through a list to a sweep kernel with 16 lanes per voxel (ws.d_cand is free until
+    // k_finalize); many frames: swept in place
+    const bool split = n < 8 && !use_dilated;
+    KLAUNCH(h, k_closefar, fgrid(g, gv), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_labels, use_dilated ? h->d_mapclose : nullptr,
+            split ? ws.d_cand : nullptr, ws.d_hdrs);
+    if (split)
+      KLAUNCH(h, k_closefar_sweep, fgrid(g, (ws.vox_cap * 16u + 255u) / 256u), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_cand);
+  }
+  if (dbg)
+    HIPCHK(hipEventRecord(ev[3], h->stream));
+  if (!lf.finalize_fused)
+    KLAUNCH(h, k_finalize, fgrid(g, gv), dim3(256), g, h->mg, up, ws.d_hdrs, ws.va, ws.d_labels, h->d_map, h->d_flags, ws.d_table, ws.d_cand, keep_dirty ? nullptr : ws.d_bitmaps);
+  return VOFOD_OK;
+}
+
+// VOFOD_SCAN_AUTO_RAYCAST applies the pending raycast update (or starts a pass) between ++its and the classification
+// (:949-963), i.e. between the kernels enqueued so far and the device tail: the scan's status comes back first (a scan that has
+// to run again, or failed, must not have moved the raycast state), then the raycast role, then the tail kernels.
+int raycast_ahead_of_tail(vofod_handle* h, Workspace& ws, FrameCall& call)
+{
+  HIPCHK(hipMemcpyAsync(&ws.h_packed[0].hdr, ws.d_hdrs, sizeof(FrameHdr), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (ws.h_packed[0].hdr.status == VOFOD_OK)
+  {
+    h->detection_its++;  // :949
+    if (h->raycast_pending)
+      raycast_finish_locked(h);
+    else
+      raycast_begin_locked(h, &call.scans[0], call.tfs);
+    call.rc_done = true;
+  }
+  return VOFOD_OK;
+}
+
+// Classification tail on the device (kernels_tail.h): boxes + gates, flood fills, detection records; nothing comes back
+// but the records.
+// (round 4: a single map-updating scan - the reference's own mode - takes the device tail too: no cluster table down, explore
+// jobs up, results down between the kernels; the flood fills then write their frontiers to the map itself, vofod_nodelet.cpp:1712-1715)
+int launch_device_tail(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, const LaunchRoute& rt, FrameCall& call)
+{
+  const uint32_t n = call.n;
+  const GridParams& g = call.g;
+  const vofod_dyn_params& dp = *call.dp;
+  // the background latch (:716-721) is needed now, not at collect time
+  VCHK(latch_background(h));
+  ExploreBufs& eb = rt.own_tail >= 0 ? h->explore_slot[rt.own_tail] : h->explore;
+  const uint32_t ebF = rt.own_tail >= 0 ? std::max<uint32_t>(eb.F, (n + 31u) & ~31u) : h->ws.F;
+  VCHK(ensure_explore(h, eb, ebF, static_cast<size_t>(ebF) * vtd::TP_MAXC, static_cast<size_t>(ebF) * vtd::TP_MAXM));
+  // A submitted batch runs its tail on the handle's tail stream: one wave per frame does the flood
+  // fills (latency bound, ~0.1 ms), which overlaps with the streaming kernels of the next batch instead of delaying them.
+  // The tail stream also serialises the tails of the batches in flight on the shared flood-fill buffers.
+  hipStream_t chain_stream = h->stream;
+  StreamScope tail_scope(h);
+  if (!h->ev_explore)
+    HIPCHK(hipEventCreateWithFlags(&h->ev_explore, hipEventDisableTiming));
+  // (large batches: the tails take turns on the tail stream, underneath the frame kernel of the next batch)
+  if (rt.own_tail >= 0)
+    ;  // (own buffers, own stream: nothing to wait for)
+  else if (call.submitted && h->stream_tail)
+  {
+    HIPCHK(hipEventRecord(ws.ev_packed, chain_stream));  // the cluster tables of this batch are complete
+    h->stream = h->stream_tail;
+    HIPCHK(hipStreamWaitEvent(h->stream, ws.ev_packed, 0));
+  }
+  else
+    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_explore, 0));  // (a synchronous call: wait for the tails of batches in flight)
+  vtd::TailParams tp{};
+  tp.min_points = dp.classification__min_points;
+  tp.max_distance = dp.classification__max_distance;
+  tp.max_size = dp.classification__max_size;
+  tp.max_explore = dp.classification__max_explore_distance;
+  tp.voxel_size = h->sp.voxel_size;
+  tp.latches = (h->background_pts_sufficient && h->sure_background_sufficient) ? 1 : 0;
+  const vc::ExploreParams ep = explore_params(dp, static_cast<float>(dp.voxel_map__thresholds__new_obstacles), rt.no_update);
+  // the records (135 KB) go straight into the pinned host slots from the last tail kernel: no copy command on any stream (see k_tail_finish)
+  static const bool diag_no_tail = std::getenv("VOFOD_DIAG_NO_TAIL") != nullptr;  // (diagnostics: timing of the pipeline without the tail kernel - results are wrong)
+  if (diag_no_tail && n >= 128u)
+    ;
+  else if ((lf.far_ran && ws.close_first == 1) || call.far_single)
+    // close-first frames: ordered lists from the frame kernel (or k_far_final), the whole tail in one kernel of one wave per frame
+    KLAUNCH(h, vtd::k_tail_far, dim3((n + vtd::TAIL_WPB - 1) / vtd::TAIL_WPB), dim3(64 * vtd::TAIL_WPB), g, ws.d_hdrs, ws.d_args, ws.d_table, ws.d_cand, ws.va, h->mg, tp, ep, eb.d_jobs, eb.d_members, h->d_map, eb.d_overlay, eb.d_stack, eb.d_explored, eb.d_touched,
+            eb.d_ovl_list, eb.d_ovl_count, eb.d_results, eb.d_visited, ws.d_dets, ws.h_dets_dev, call.far_single ? ws.d_tailc : static_cast<vtd::TailCluster*>(nullptr),
+            (ws.prof_deferred && h->d_prof_ccl && !call.far_single) ? h->d_prof_ccl + 32 * static_cast<size_t>(ws.prof_slot0) : static_cast<unsigned long long*>(nullptr));
+  else
+  {
+    KLAUNCH(h, vtd::k_tail_prep, dim3(n), dim3(vtd::TP_THREADS), g, ws.d_hdrs, ws.d_args, ws.d_table, ws.d_cand, ws.va, h->mg, tp, eb.d_jobs, ws.d_job_be, ws.d_job_be + ws.F, eb.d_members, ws.d_tailc,
+            ws.d_dets);
+    KLAUNCH(h, vc::k_explore, dim3(n), dim3(64), ep, h->mg, eb.d_jobs, ws.d_job_be, ws.d_job_be + ws.F, eb.d_members, h->d_map, eb.d_overlay, eb.d_stack, eb.d_explored, eb.d_touched, eb.d_ovl_list,
+            eb.d_ovl_count, eb.d_results, eb.d_visited);
+    KLAUNCH(h, vtd::k_tail_finish, dim3(n), dim3(64), ws.d_tailc, eb.d_results, ws.d_dets, ws.h_dets_dev);
+  }
+  if (rt.own_tail < 0)
+    HIPCHK(hipEventRecord(h->ev_explore, h->stream));  // the shared flood-fill buffers are free again
+  call.tail_stream_used = h->stream;
+  return VOFOD_OK;
+}
+
+// Read-back of a batch nobody debugs whose tail runs on the host: the lite slots, on the copy stream when nobody waits in this call
+int read_back_lite(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t n, bool submitted)
+{
+  KLAUNCH(h, k_pack_lite, dim3(n), dim3(256), g, ws.d_hdrs, ws.d_table, ws.d_cand, ws.va, ws.d_lite);
+  if (submitted)
+  {
+    HIPCHK(hipEventRecord(ws.ev_packed, h->stream));
+    HIPCHK(hipStreamWaitEvent(ws.copy_stream, ws.ev_packed, 0));
+  }
+  HIPCHK(hipMemcpyAsync(ws.h_lite, ws.d_lite, sizeof(PackedLite) * n, hipMemcpyDeviceToHost, submitted ? ws.copy_stream : h->stream));
+  return VOFOD_OK;
+}
+
+// The launch half.  `call` is filled for the collect half of a synchronous call; a submitted batch leaves what its collect
+// half needs in the workspace (pending, job_n, job_g, job_tfs, job_scans, job_dp, dtail, lite, ev_done).
+int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
+{
+  const vofod_static_params& sp = h->sp;
+  const bool submitted = call.submitted;
+  const uint32_t n = call.n;
+  vofod_scan_debug* dbg = call.dbg;
+  if (submitted && !ws.rerun)
+    ws.job_dp = h->dp;
+  call.dp = submitted ? &ws.job_dp : &h->dp;
+  const vofod_dyn_params& dp = *call.dp;
+  if (n == 0)
+    return VOFOD_OK;
+  if (n > ws.F)
+  {
+    h->err = "batch larger than max_batch_frames";
+    return VOFOD_ERR_CAPACITY;
+  }
+  const size_t npts = static_cast<size_t>(sp.sensor_hrays) * sp.sensor_vrays;
+  for (uint32_t f = 0; f < n; f++)
+  {
+    const vofod_scan& s = call.scans[f];
+    if (!s.x || !s.y || !s.z)
+      return VOFOD_ERR_INVALID_ARG;
+    if (static_cast<size_t>(s.width) * s.height != npts)  // :895-899
+      return VOFOD_ERR_SIZE_MISMATCH;
+  }
+  // re-run of the batch that overflowed the LDS kernels: the flag is consumed here, whatever path this call takes (an early
+  // error return must not leave it standing for a different batch), and only a launch of the very same job reuses its inputs
+  const bool rerun = ws.rerun && ws.job_n == n;
+  ws.rerun = false;
+  hipEvent_t* ev = call.ev;
+  if (dbg)
+    for (int i = 0; i < 5; i++)
+      HIPCHK(hipEventCreate(&ev[i]));
+  const float thr_new = static_cast<float>(dp.voxel_map__thresholds__new_obstacles);
+
+  // ---- the routing decisions that do not depend on the frames
+  LaunchRoute rt;
+  const bool no_update = rt.no_update = call.flags & VOFOD_SCAN_NO_MAP_UPDATE;
+  rt.use_dilated = !switch_off("VOFOD_DILATE") && no_update && n >= 4;  // (VOFOD_DILATE=0: stencil sweep)
+  rt.single_update = !no_update && n == 1 && !submitted;
+  const bool dtail_on = !switch_off("VOFOD_DEVICE_TAIL");
+  rt.dtail = dtail_on && !dbg && ((n >= 4 && no_update) || rt.single_update);
+  rt.lite = !rt.dtail && !switch_off("VOFOD_LITE") && !dbg && n >= 4 && no_update;
+  if (submitted)
+    VCHK(route_submitted(h, ws, n, rt));
+  StreamScope chain_scope(h, rt.chain);
+  if (submitted && h->ev_stagger_set)
+    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_stagger, 0));  // the previous batch's streaming kernels are through
+  if (submitted && !(h->mapbits_valid && h->mapbits_thr == thr_new))
+  {
+    // the occupancy image is shared by both chains: make sure it is complete before a second stream reads it
+    VCHK(ensure_mapbits(h, thr_new));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+
+  bool host_copies = false;
+  if (!rerun)
+    VCHK(stage_inputs(h, ws, call.scans, call.tfs, n, npts, host_copies));
+  // include/vofod.h promises that the scans' host buffers need not outlive vofod_batch_submit.  A copy from page-locked memory
+  // is truly asynchronous - and on the streaming stage's stream it is queued behind the previous batch's streaming kernels:
+  // it may start long after the call has returned, when a caller that refills its arena has already overwritten it.
+  // The event marks the end of the batch's copies; the submitting call returns behind it (below).
+  if (host_copies && submitted && ws.ev_h2d)
+    HIPCHK(hipEventRecord(ws.ev_h2d, h->stream));
+  else
+    host_copies = false;
+  H2DGuard h2d_guard{ws.ev_h2d, host_copies};
+
+  GridParams& g = call.g;
+  const float leaf[3] = {sp.voxel_size, sp.voxel_size, sp.voxel_size};
+  const int zero[3] = {0, 0, 0};
+  float align_center[3];
+  h->hg.idxToCoord(zero, align_center);  // :664
+  fill_grid_params(h, g, leaf, true, align_center, ws);
+  CloseParams cpar{};
+  VCHK(prepare_map_images(h, dp, thr_new, rt.use_dilated, !h->background_pts_sufficient || dbg, cpar));
+  if (dbg)
+    HIPCHK(hipEventRecord(ev[0], h->stream));
+  LaunchFlags lf;
+  vofod_handle::ClusterTables* ct = nullptr;
+  VCHK(voxelize_frames(h, ws, lf, g, n, npts, dp, no_update, ct));
+  if (dbg)
+    HIPCHK(hipEventRecord(ev[1], h->stream));
+  if (rt.staged)
+    VCHK(enter_frame_stream(h, ws));
+
+  // ---- K7 clusterCloud :932
+  UpdateParams up{};
+  up.score_point = static_cast<float>(dp.voxel_map__scores__point);
+  up.score_unknown = static_cast<float>(dp.voxel_map__scores__unknown);
+  up.min_points = dp.classification__min_points;
+  up.cand_max_extent = static_cast<float>(dp.classification__max_size * (1.0 + 1e-4) + 1e-3 * sp.voxel_size);
+  up.no_update = no_update;
+  // k_slab rewrites the bitmap densely and the brick clustering reads it at set bits only: no need to clean it after use;
+  // then the LDS clustering kernel can write the cluster table and the candidate list itself (nothing left for k_finalize)
+  const bool frame_path = lf.frame_fused;  // brick-first frame kernel: the global occupancy bitmaps are not touched at all
+  const bool bitmap_was_clean = ws.bitmap_clean;
+  const bool keep_dirty = frame_path || (lf.slab_bitmap && g.sparse_prefix);
+  // Read-only batches cluster close first (k_frame_lds): only the far clusters are ever used (vofod_nodelet.cpp:946-963).  The
+  // debug view of ALL clusters keeps the full clustering; dbg[0].far_only asks for the production path's view instead.
+  // VOFOD_CLOSE_FIRST=0: the full clustering everywhere.
+  const bool close_first_on = !switch_off("VOFOD_CLOSE_FIRST");
+  const bool dbg_far_only = dbg && dbg[0].far_only;
+  if (h->cf_off && (h->n_bg_voxels > h->cf_off_bg + h->cf_off_bg / 4 + 1000 || h->n_bg_voxels < h->cf_off_bg))
+    h->cf_off = false;  // the map has changed a lot since: try the close-first kernel again
+  ws.close_first = (close_first_on && rt.use_dilated && !h->cf_off) ? (dbg ? (dbg_far_only ? 2 : 0) : 1) : 0;
+  call.far_single = close_first_on && !h->cf_off && !dbg && rt.single_update && dtail_on && !frame_path && !keep_dirty && ct->n_rows > 0 && ws.vox_cap >= FAR_MAX;
+  if (call.far_single)
+    VCHK(cluster_far_single(h, ws, lf, g, ct, dp, cpar, up, thr_new));
+  else
+    VCHK(launch_cluster(h, ws, lf, g, n, static_cast<float>(dp.ground_points_max_distance), map_cmax(h), rt.use_dilated ? h->d_mapclose : nullptr,
+                        (keep_dirty && no_update) ? &up : nullptr));
+  if (dbg)
+    HIPCHK(hipEventRecord(ev[2], h->stream));
+  VCHK(closefar_and_finalize(h, ws, lf, g, n, cpar, up, rt.use_dilated, keep_dirty, dbg, ev));
+  ws.bitmap_clean = frame_path ? bitmap_was_clean : !keep_dirty;
+
+  // ---- the tail on the device, or the read-back of what the host tail needs
+  ws.dtail = rt.dtail;
+  ws.lite = rt.lite;
+  call.tail_stream_used = h->stream;
+  if (rt.dtail && rt.single_update && (call.flags & VOFOD_SCAN_AUTO_RAYCAST))
+    VCHK(raycast_ahead_of_tail(h, ws, call));
+  if (rt.dtail)
+    VCHK(launch_device_tail(h, ws, lf, rt, call));
+  else if (rt.lite)
+    VCHK(read_back_lite(h, ws, g, n, submitted));
+  else
+    VCHK(read_back_full(h, ws, g, n));
+  if (dbg)
+    HIPCHK(hipEventRecord(ev[4], h->stream));
+  call.tr_launch = ms_since(call.t0);
+  if (!submitted)
+    return VOFOD_OK;  // (the collect half follows in the same call)
+
+  h2d_guard.armed = false;
+  if (host_copies)
+    HIPCHK(hipEventSynchronize(ws.ev_h2d));  // (the whole chain is enqueued by now: the device works while the host waits for the link)
+  HIPCHK(hipEventRecord(ws.ev_done, rt.dtail ? call.tail_stream_used : rt.lite ? ws.copy_stream : h->stream));
+  ws.pending = true;
+  ws.job_n = n;
+  ws.job_g = g;
+  if (call.tfs != ws.job_tfs.data())
+    ws.job_tfs.assign(call.tfs, call.tfs + 12 * static_cast<size_t>(n));
+  if (call.scans != ws.job_scans.data())
+    ws.job_scans.assign(call.scans, call.scans + n);
+  return VOFOD_OK;
+}
+
+}  // namespace

@@ -367,4 +367,28 @@ inline void ingest_apriori_points(const std::vector<float>& xyz_in, const float 
   }
 }
 
+// The record extractDetections builds for a detected cluster (vofod_nodelet.cpp:848-877) seen from the sensor pose tf (3 x 4).
+// The results are compared bit for bit with the oracle: float differences, double distance, 1.0 / std::exp(u) stay as they are.
+inline vofod_detection make_detection(uint32_t id, const float tf[12], const float center[3], uint64_t n_points, double conf_sum, uint32_t frame, const vofod_static_params& sp,
+                                      const vofod_dyn_params& dp)
+{
+  vofod_detection det{};
+  const float d[3] = {tf[3] - center[0], tf[7] - center[1], tf[11] - center[2]};
+  const double det_dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  det.id = id;
+  det.frame = frame;
+  det.n_points = n_points;
+  const float cov = static_cast<float>(std::sqrt(det_dist) * dp.output__position_sigma);
+  for (int q = 0; q < 3; q++)
+    det.covariance[4 * q] = cov;
+  const double u = conf_sum / n_points;  // :860-865
+  det.confidence = static_cast<float>(1.0 / std::exp(u));
+  const double vray_res = sp.sensor_vfov / static_cast<double>(sp.sensor_vrays);
+  const double hray_res = 2 * M_PI / static_cast<double>(sp.sensor_hrays);
+  det.detection_probability = std::min(std::atan(1.0 / det_dist) / (vray_res * dp.classification__min_points), 1.0) * std::min(std::atan(1.0 / det_dist) / hray_res, 1.0);
+  for (int a = 0; a < 3; a++)
+    det.position[a] = center[a];
+  return det;
+}
+
 }  // namespace vt

@@ -6,7 +6,7 @@
 // per brick, 64 times fewer bits) is not large: a whole frame's brick bitmap fits LDS next to its occupied bricks.
 // So voxelisation (voxel_grid_weighted.cpp:122-188) runs brick-first and the clustering (vofod_nodelet.cpp:689-698)
 // continues on the very same LDS image:
-//   k_key2      one pass over the input columns: crops + transform (vofod_nodelet.cpp:625-655), cell of every
+//   input pass  (inside k_frame_lds since round 5; rounds 2-4: a kernel k_key2 in front) one pass over the input columns: crops + transform (vofod_nodelet.cpp:625-655), cell of every
 //               surviving point (voxel_grid_weighted.cpp:131-136) as a *brick code* (brick coordinates 9 + 9 + 6 bits, then
 //               the bit inside the brick: 6 bits), appended in point order (8 consecutive points per thread: points of one ring that fall into
 //               one voxel / brick stay neighbours in the list);
@@ -384,7 +384,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   uint32_t* s_bits = reinterpret_cast<uint32_t*>(s_bits64);
   uint16_t* s_vbase = reinterpret_cast<uint16_t*>(s_x2);  // node -> index of its first voxel in brick order (counting / rank phases)
   uint16_t* s_par = reinterpret_cast<uint16_t*>(s_x2);
-  // the classification tails of the batches in front run beside this kernel (process_frames' pipeline): this kernel's waves go
+  // the classification tails of the batches in front run beside this kernel (launch_frames' pipeline): this kernel's waves go
   // first wherever both want to issue
   __builtin_amdgcn_s_setprio(FR_WAVE_PRIO);
   const uint32_t FRAME = blockIdx.x;

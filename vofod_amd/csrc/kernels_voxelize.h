@@ -132,7 +132,7 @@ __global__ void k_init_hdr(FrameHdr* hdrs, uint32_t* counts2)
 {
   FrameHdr& h = hdrs[blockIdx.x];
   if (counts2 && threadIdx.x < 2)
-    counts2[2 * blockIdx.x + threadIdx.x] = 0;  // the frame's two list counters of k_key1 (one kernel less in the chain than a memset)
+    counts2[2 * blockIdx.x + threadIdx.x] = 0;  // two per-frame list counters (of k_key1, the streaming kernel of rounds 2-4: every caller passes nullptr now)
   if (threadIdx.x == 0)
   {
     for (int a = 0; a < 3; a++)

@@ -112,12 +112,9 @@ int ms_export_locked(vofod_handle* h, int maps, int kind, uint8_t* d_dst, size_t
     h->err = "map export: the map has more voxels than 32-bit record indices reach";
     return VOFOD_ERR_INDEX_OVERFLOW;
   }
-  int r;
-  if ((r = ms_ensure(h)) != VOFOD_OK)
-    return r;
+  VCHK(ms_ensure(h));
   uint64_t nrec[3];
-  if ((r = ms_count(h, maps, full, nrec)) != VOFOD_OK)
-    return r;
+  VCHK(ms_count(h, maps, full, nrec));
   const size_t bytes = sizeof(vms::WireHeader) + 8 * (nrec[0] + nrec[1] + nrec[2]);
   *n_bytes = bytes;
   if (size_only)
@@ -129,8 +126,7 @@ int ms_export_locked(vofod_handle* h, int maps, int kind, uint8_t* d_dst, size_t
   }
   if (!d_dst)
   {
-    if ((r = ms_ensure_wire(h, bytes)) != VOFOD_OK)
-      return r;
+    VCHK(ms_ensure_wire(h, bytes));
     d_dst = s.d_wire;
   }
   if (full)  // the shadows are allocated on the first export of their map (4 * M bytes each)
@@ -190,8 +186,7 @@ int ms_apply_locked(vofod_handle* h, const vms::WireHeader& hd, const uint8_t* d
   const int maps = static_cast<int>(hd.maps);
   const bool full = hd.kind == VOFOD_SNAPSHOT_FULL;
   int r;
-  if ((r = ms_ensure(h)) != VOFOD_OK)
-    return r;
+  VCHK(ms_ensure(h));
   // records: strictly ascending and inside the map, checked on the device before anything is written
   HIPCHK(hipMemsetAsync(s.d_small + 3, 0, sizeof(uint32_t), h->stream));
   size_t off = sizeof(vms::WireHeader);
@@ -245,8 +240,7 @@ int ms_apply_locked(vofod_handle* h, const vms::WireHeader& hd, const uint8_t* d
       }
       else
       {
-        if ((r = ms_count_map(h, VOFOD_MAP_RAYCAST, true, reinterpret_cast<const uint32_t*>(h->d_ray), 4)) != VOFOD_OK)
-          return r;
+        VCHK(ms_count_map(h, VOFOD_MAP_RAYCAST, true, reinterpret_cast<const uint32_t*>(h->d_ray), 4));
         HIPCHK(hipMemcpyAsync(h->d_counter + 1, s.d_small + 4, sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
       }
     }
@@ -324,9 +318,7 @@ int vofod_map_export(vofod_handle* h, int32_t maps, int32_t kind, void* buf, siz
   if (size_only || memspace == VOFOD_MEM_DEVICE)
     return ms_export_locked(h, maps, kind, static_cast<uint8_t*>(buf), cap, size_only, n_bytes);
   // host buffer: emitted into the staging buffer, then copied out
-  int r = ms_export_locked(h, maps, kind, nullptr, cap, false, n_bytes);
-  if (r != VOFOD_OK)
-    return r;
+  VCHK(ms_export_locked(h, maps, kind, nullptr, cap, false, n_bytes));
   HIPCHK(hipMemcpy(buf, h->msync.d_wire, *n_bytes, hipMemcpyDeviceToHost));
   return VOFOD_OK;
 }
@@ -339,8 +331,7 @@ int vofod_map_apply(vofod_handle* h, const void* buf, size_t n_bytes, int32_t me
     return VOFOD_ERR_INVALID_ARG;
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
-  if (const int b = busy_check(h, false, true); b != VOFOD_OK)
-    return b;
+  VCHK(busy_check(h, false, true));
   vms::WireHeader hd;
   if (memspace == VOFOD_MEM_HOST)
     std::memcpy(&hd, buf, sizeof(hd));
@@ -349,14 +340,11 @@ int vofod_map_apply(vofod_handle* h, const void* buf, size_t n_bytes, int32_t me
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(&hd, buf, sizeof(hd), hipMemcpyDeviceToHost));
   }
-  if (const int c = ms_check_header(h, hd, n_bytes); c != VOFOD_OK)
-    return c;
+  VCHK(ms_check_header(h, hd, n_bytes));
   const uint8_t* d_buf = static_cast<const uint8_t*>(buf);
   if (memspace == VOFOD_MEM_HOST)
   {
-    int r;
-    if ((r = ms_ensure_wire(h, n_bytes)) != VOFOD_OK)
-      return r;
+    VCHK(ms_ensure_wire(h, n_bytes));
     HIPCHK(hipMemcpyAsync(h->msync.d_wire, buf, n_bytes, hipMemcpyHostToDevice, h->stream));
     d_buf = h->msync.d_wire;
   }
@@ -434,9 +422,8 @@ int vofod_broadcast_map(vofod_comm* c, vofod_handle* h, int32_t root, int32_t ma
     local = ms_ensure_wire(h, bytes);
   if (!is_root && local == VOFOD_OK)
     local = busy_check(h, false, true);
-  int st = VOFOD_OK, r;
-  if ((r = agree(local, &st)) != VOFOD_OK)
-    return r;
+  int st = VOFOD_OK;
+  VCHK(agree(local, &st));
   if (st != VOFOD_OK)
     return st;
   // 3. the payload
@@ -452,8 +439,7 @@ int vofod_broadcast_map(vofod_comm* c, vofod_handle* h, int32_t root, int32_t ma
     if (local == VOFOD_OK)
       local = ms_apply_locked(h, hd, s.d_wire, bytes);
   }
-  if ((r = agree(local, &st)) != VOFOD_OK)
-    return r;
+  VCHK(agree(local, &st));
   return st;
 }
 

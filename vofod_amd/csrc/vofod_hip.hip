@@ -210,6 +210,14 @@ struct SlowCall
     }                                                                                                        \
   } while (0)
 
+// (the same for the driver's own functions: a status other than VOFOD_OK ends the caller with it)
+#define VCHK(expr)                             \
+  do                                           \
+  {                                            \
+    if (const int r_ = (expr); r_ != VOFOD_OK) \
+      return r_;                               \
+  } while (0)
+
 // ---- optional per-kernel timing with HIP events on the handle's stream (vofod_profile_*) ----------
 struct Prof
 {
@@ -235,25 +243,8 @@ struct Prof
   }
 };
 
-#define KLAUNCH(h, kern, grid, block, ...)                                   \
-  do                                                                         \
-  {                                                                          \
-    if ((h)->prof.on)                                                        \
-    {                                                                        \
-      Prof::Rec r_{#kern, (h)->prof.get(), (h)->prof.get()};                 \
-      (void)hipEventRecord(r_.a, (h)->stream);                               \
-      hipLaunchKernelGGL(kern, grid, block, 0, (h)->stream, __VA_ARGS__);    \
-      (void)hipEventRecord(r_.b, (h)->stream);                               \
-      (h)->prof.recs.push_back(r_);                                          \
-    }                                                                        \
-    else                                                                     \
-    {                                                                        \
-      SlowCall sc_(#kern, __LINE__);                                         \
-      hipLaunchKernelGGL(kern, grid, block, 0, (h)->stream, __VA_ARGS__);    \
-    }                                                                        \
-  } while (0)
-
-// (the same under another name in the profile: the instantiations of one kernel share their algorithmic name)
+// One kernel launch on the handle's stream: timed between two events when the profile is on (under `label`: the instantiations
+// of one kernel share their algorithmic name), watched by VOFOD_CALLTRACE otherwise.
 #define KLAUNCH_AS(h, label, kern, grid, block, ...)                        \
   do                                                                         \
   {                                                                          \
@@ -271,22 +262,7 @@ struct Prof
       hipLaunchKernelGGL(kern, grid, block, 0, (h)->stream, __VA_ARGS__);    \
     }                                                                        \
   } while (0)
-
-// (the same with dynamic LDS)
-#define KLAUNCH_LDS(h, kern, grid, block, lds, ...)                                   \
-  do                                                                         \
-  {                                                                          \
-    if ((h)->prof.on)                                                        \
-    {                                                                        \
-      Prof::Rec r_{#kern, (h)->prof.get(), (h)->prof.get()};                 \
-      (void)hipEventRecord(r_.a, (h)->stream);                               \
-      hipLaunchKernelGGL(kern, grid, block, lds, (h)->stream, __VA_ARGS__);    \
-      (void)hipEventRecord(r_.b, (h)->stream);                               \
-      (h)->prof.recs.push_back(r_);                                          \
-    }                                                                        \
-    else                                                                     \
-      hipLaunchKernelGGL(kern, grid, block, lds, (h)->stream, __VA_ARGS__);    \
-  } while (0)
+#define KLAUNCH(h, kern, grid, block, ...) KLAUNCH_AS(h, #kern, kern, grid, block, __VA_ARGS__)
 
 // VOFOD_<NAME>=0 switches a fast path off (README "Environment switches").  Read on every call, not cached: a dozen getenv per
 // batch cost ~1 us, and the tests flip the fallbacks inside one process (a `static const` here made every switch stick to
@@ -296,6 +272,21 @@ inline bool switch_off(const char* name)
   const char* v = std::getenv(name);
   return v && std::atoi(v) == 0;
 }
+
+// What the stages of ONE launch tell each other: created by the caller of launch_voxelize, handed on to launch_cluster and the
+// tail launch, dropped with the call.  Nothing here outlives a launch - the state of a pending ticket lives in Workspace.
+struct LaunchFlags
+{
+  RefLattice ref_lattice{};     // frame kernel: the reference lattice its bricks and cell codes refer to (on = 0: general kernels)
+  bool frame_fused = false;     // launch_voxelize planned the frame kernel: launch_cluster runs k_frame_lds (input pass, voxel records and clustering in one kernel)
+  bool in_packed = false;       // the batch's columns are packed, 16-byte aligned floats, a multiple of 4 points each: the frame kernel's input pass uses 16-byte loads
+  bool lean_emit = false;       // the per-root slots were left alone: launch_cluster must run the LDS clustering kernel
+  bool bricks_preset = false;   // k_emit already registered the voxels in their bricks (fused brick_set)
+  bool slab_bitmap = false;     // the current bitmaps were written by k_slab (dense, zeros included)
+  bool far_ran = false;         // launch_cluster ran k_frame_lds_far: the cluster table and the member list are in the order k_tail_far reads
+  bool finalize_fused = false;  // the clustering wrote the cluster table / candidate list too (nothing left for k_finalize)
+  bool closefar_fused = false;  // the clustering answered hasCloseTo as well (dilated image inside k_flatten / the frame kernel)
+};
 
 struct Workspace
 {
@@ -314,8 +305,6 @@ struct Workspace
   uint32_t* d_ptrank = nullptr;
   SlabArrays sa{};  // key list / extras of the LDS-slab voxelisation (keys share d_ptrank's storage)
   FrameScratch fs{};  // row tables of the brick-first frame kernel (kernels_frame.h)
-  RefLattice ref_lattice{};  // single-pass input: the reference lattice the list's cells refer to (on = 0: brick codes from k_key2)
-  bool frame_fused = false;  // k_key2 ran: launch_cluster runs k_frame_lds (voxel records + clustering in one kernel)
   float* d_stage = nullptr;  // F * pt_cap * 5 words: x, y, z, intensity, range of host-resident inputs
   char* d_stage_aos = nullptr;  // host-resident array-of-structs clouds (the nodelet's 48-byte ouster_ros::Point) cross the link as they are:
   size_t stage_aos_bytes = 0;   // F * aos_pitch bytes, allocated on first use; the kernels read x / y / z in place at the struct's stride
@@ -328,8 +317,6 @@ struct Workspace
   bool mapbits_patched = false;  // k_finalize_far kept the map's occupancy image and counters up to date with this scan's update
   bool prof_deferred = false;  // VOFOD_LDS_PROF=2: the frame kernel's stamps of this batch are printed when it is collected
   uint32_t prof_slot0 = 0;
-  bool in_packed = false;  // the batch's columns are packed, 16-byte aligned floats, a multiple of 4 points each: the frame kernel's input pass uses 16-byte loads
-  bool far_ran = false;  // launch_cluster ran k_frame_lds_far: the cluster table and the member list are in the order k_tail_far reads
   int close_first = 0;  // k_frame_lds: 1 = cluster the far voxels only (read-only batches), 2 = the same with labels for the far-only debug view
   bool dtail = false;  // ... or its classification tail ran on the device (kernels_tail.h): only detection records come back
   vtd::TailCluster* d_tailc = nullptr;
@@ -359,12 +346,7 @@ struct Workspace
       return hipSuccess;
     }
   } h_args;
-  bool bricks_preset = false;  // k_emit already registered the voxels in their bricks (fused brick_set)
   std::vector<vofod_scan> job_scans;  // the submitted batch (re-run when the LDS clustering kernel overflows)
-  bool slab_bitmap = false;     // the current bitmaps were written by k_slab (dense, zeros included)
-  bool lean_emit = false;       // k_emit skipped the per-root slots: launch_cluster must run the LDS clustering kernel
-  bool finalize_fused = false;  // ... and the cluster table / candidate list too
-  bool closefar_fused = false;  // launch_cluster answered hasCloseTo as well (dilated image inside k_flatten)
   bool bitmap_clean = false;   // the occupancy bitmaps are all-zero (k_finalize clears the words it used)
   vofod_dyn_params job_dp{};   // the dynamic parameters the pending batch was submitted with
   bool rerun = false;          // the next launch repeats this workspace's batch (LDS overflow): frame arguments and staged columns are kept
@@ -938,9 +920,7 @@ int read_box(vofod_handle* h, const float* d_map, int lo[3], int hi[3], vt::Box&
   box.v.resize(n);
   if (n == 0)
     return VOFOD_OK;
-  const int r = ensure_boxstage(h, n);
-  if (r != VOFOD_OK)
-    return r;
+  VCHK(ensure_boxstage(h, n));
   KLAUNCH(h, k_read_box, dim3((n + 255) / 256), dim3(256), d_map, h->mg, lo[0], lo[1], lo[2], box.n[0], box.n[1], box.n[2], h->d_boxstage);
   HIPCHK(hipMemcpyAsync(box.v.data(), h->d_boxstage, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -974,13 +954,9 @@ int fill_map(vofod_handle* h, float* p, float v)
 // reset() vofod_nodelet.cpp:1610-1632
 int do_reset(vofod_handle* h)
 {
-  int r;
-  if ((r = fill_map(h, h->d_map, h->sp.score_init)) != VOFOD_OK)
-    return r;
-  if ((r = fill_map(h, h->d_flags, 0.0f)) != VOFOD_OK)
-    return r;
-  if ((r = fill_map(h, h->d_ray, 0.0f)) != VOFOD_OK)
-    return r;
+  VCHK(fill_map(h, h->d_map, h->sp.score_init));
+  VCHK(fill_map(h, h->d_flags, 0.0f));
+  VCHK(fill_map(h, h->d_ray, 0.0f));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->detection_its = 0;
   h->raycast_pending = false;
@@ -1010,7 +986,7 @@ int stage_cloud(vofod_handle* h, Workspace& ws, uint32_t f, const void* x, const
   }
   // An array of structs in host memory (stride > 4, the three coordinates inside one struct: pcl::PointCloud<ouster_ros::Point>,
   // 48 bytes per point, what the nodelet holds - include/vofod/point_types.h) crosses the link with ONE copy of the whole block;
-  // the kernels then read the columns in place at the struct's stride (k_key1<false>).  Round 3 gathered every column on the
+  // the kernels then read the columns in place at the struct's stride (the frame kernel's strided input pass, k_bbox / k_setbits / k_count).  Round 3 gathered every column on the
   // host (three passes over the cloud and a synchronisation per column: ~1 ms per frame).  4 x the bytes of packed columns over
   // PCIe: the link's ceiling for this layout is ~8 k frames/s of OS1-128.
   // The kernels dereference floats in place: only structs whose stride and member offsets are multiples of 4 take this path, a
@@ -1083,7 +1059,7 @@ int stage_cloud(vofod_handle* h, Workspace& ws, uint32_t f, const void* x, const
 inline dim3 fgrid(const GridParams& g, uint32_t gx) { return dim3(g.n_frames * gx); }
 inline uint32_t emit_split(uint32_t n_frames) { return n_frames <= 16 ? EMIT_SPLIT : 1u; }
 
-// Reference lattice of the single-pass input (kernels_frame.h, k_key1): what voxel_grid_weighted.cpp:72-106 yields for a cloud
+// Reference lattice of the frame kernel's input pass (kernels_frame.h): what voxel_grid_weighted.cpp:72-106 yields for a cloud
 // whose minimum is the operation area's corner, and the band around cell boundaries inside which the frame's own offset may
 // round a point into the neighbouring cell.  Bound: |q - O| <= 2c (c = largest |coordinate|), the subtraction and the product
 // each round by 2^-24 relative -> 2 * 2c * inv * 2^-23 cells per offset; the two offsets differ from whole cells by their own
@@ -1119,37 +1095,34 @@ RefLattice fill_ref_lattice(const GridParams& g)
 }
 
 // kernel chain K1-K6 over frames [0,n): bbox -> lattice -> occupancy bitmap -> ranks -> weighted cloud
-int launch_voxelize(vofod_handle* h, Workspace& ws, GridParams& g, uint32_t n, uint32_t max_pts, bool want_ptrank, bool two_phase, const BrickParams* bricks = nullptr,
+int launch_voxelize(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams& g, uint32_t n, uint32_t max_pts, bool want_ptrank, bool two_phase, const BrickParams* bricks = nullptr,
                     bool lean_hint = false)
 {
   BrickParams bpv{};
   if (bricks)
     bpv = *bricks;
   bpv.bricks_cap = ws.bricks_cap;
-  ws.bricks_preset = bricks != nullptr;
+  lf.bricks_preset = bricks != nullptr;
   g.n_frames = n;
   // lean emission: the LDS clustering kernel will follow and initialises the per-root slots itself (see plan_lds_ccl)
-  ws.lean_emit = lean_hint && !bricks && !two_phase;
-  ws.slab_bitmap = false;
+  lf.lean_emit = lean_hint && !bricks && !two_phase;
   HIPCHK(hipMemcpyAsync(ws.d_args, ws.h_args.data(), sizeof(FrameArgs) * n, hipMemcpyHostToDevice, h->stream));
   const uint32_t gx = std::max(1u, std::min((max_pts + 255u) / 256u, 1024u));
   const uint32_t gb = std::max(1u, std::min((max_pts + 2047u) / 2048u, 1024u));  // 8 points per thread: few header atomics
   // Batches whose clustering will run inside LDS (plan_lds_ccl): the brick-first frame kernel (kernels_frame.h) reads the input
-  // itself (round 5; rounds 2-4: a streaming kernel k_key1 in front), builds the voxel records and clusters them on the same LDS
+  // itself (round 5; rounds 2-4 had a streaming kernel in front, k_key1, which is gone), builds the voxel records and clusters them on the same LDS
   // image - launched by launch_cluster.  It needs the batch's reference lattice (bricks of the operation area's lattice in the
   // LDS bitmap); where that does not fit, the general kernels below take the batch.
-  ws.ref_lattice = RefLattice{};
-  bool frame_plan = ws.lean_emit && n >= 4 && !want_ptrank && !two_phase;
+  bool frame_plan = lf.lean_emit && n >= 4 && !want_ptrank && !two_phase;
   if (frame_plan)
   {
-    ws.ref_lattice = fill_ref_lattice(g);
-    frame_plan = ws.ref_lattice.on != 0;
+    lf.ref_lattice = fill_ref_lattice(g);
+    frame_plan = lf.ref_lattice.on != 0;
   }
   if (!frame_plan)
-    ws.lean_emit = false;  // the general emission kernels initialise every per-voxel slot; the global clustering kernels follow
-  const uint32_t lean_bit = ws.lean_emit ? 0x80000000u : 0u;
+    lf.lean_emit = false;  // the general emission kernels initialise every per-voxel slot; the global clustering kernels follow
+  const uint32_t lean_bit = lf.lean_emit ? 0x80000000u : 0u;
   KLAUNCH(h, k_init_hdr, dim3(n), dim3(64), ws.d_hdrs, static_cast<uint32_t*>(nullptr));
-  ws.frame_fused = false;
   if (frame_plan)
   {
     bool packed = true;
@@ -1158,12 +1131,12 @@ int launch_voxelize(vofod_handle* h, Workspace& ws, GridParams& g, uint32_t n, u
       const FrameArgs& a = ws.h_args[f];
       packed = a.stride == 4 && (a.n & 3u) == 0 && a.n >= 4 && ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.z)) & 15u) == 0;
     }
-    ws.in_packed = packed;
+    lf.in_packed = packed;
     if (!h->ev_stagger)
       HIPCHK(hipEventCreateWithFlags(&h->ev_stagger, hipEventDisableTiming));
     HIPCHK(hipEventRecord(h->ev_stagger, h->stream));  // the next batch's chain may start now
     h->ev_stagger_set = true;
-    ws.frame_fused = true;
+    lf.frame_fused = true;
     HIPCHK(hipGetLastError());
     return VOFOD_OK;
   }
@@ -1178,7 +1151,7 @@ int launch_voxelize(vofod_handle* h, Workspace& ws, GridParams& g, uint32_t n, u
   const uint32_t n_slabs = (ws.words_cap + SLAB_WORDS64 - 1) / SLAB_WORDS64;
   if (slabs_on && n >= 4 && !want_ptrank && !bricks && n_slabs <= SLAB_MAX)  // a single frame is served faster by the whole chip through the global bitmap
   {
-    ws.slab_bitmap = true;
+    lf.slab_bitmap = true;
     if (!ws.bitmap_clean && !g.sparse_prefix)  // voxel-level clustering: neighbour windows run into the words past the lattice, they must read as zero
       HIPCHK(hipMemsetAsync(ws.d_bitmaps, 0, sizeof(unsigned long long) * ws.F * (static_cast<size_t>(ws.words_cap) + 2), h->stream));
     HIPCHK(hipMemsetAsync(ws.sa.counts, 0, sizeof(uint32_t) * 2 * n, h->stream));
@@ -1257,12 +1230,12 @@ int launch_voxelize(vofod_handle* h, Workspace& ws, GridParams& g, uint32_t n, u
   return VOFOD_OK;
 }
 
-int launch_voxelize_rest(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t n, uint32_t max_pts, bool want_ptrank)
+int launch_voxelize_rest(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridParams& g, uint32_t n, uint32_t max_pts, bool want_ptrank)
 {
   BrickParams bpv{};
   bpv.bricks_cap = ws.bricks_cap;
   const BrickParams* bricks = nullptr;
-  ws.bricks_preset = false;
+  lf.bricks_preset = false;  // (two-phase voxelisation never registers bricks in k_emit)
   const uint32_t gx = std::max(1u, std::min((max_pts + 255u) / 256u, 1024u));
   HIPCHK(hipMemsetAsync(ws.d_bitmaps, 0, sizeof(unsigned long long) * ws.F * (static_cast<size_t>(ws.words_cap) + 2), h->stream));
   ws.bitmap_clean = false;
@@ -1533,16 +1506,11 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
   }
 
 // K7: Euclidean clustering of the frames in `ws`
-int launch_cluster(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t n, float tol, float cmax, bool allow_lds = false, const unsigned long long* mapclose = nullptr,
+int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridParams& g, uint32_t n, float tol, float cmax, const unsigned long long* mapclose = nullptr,
                    const UpdateParams* up_tables = nullptr)
 {
-  ws.finalize_fused = false;
-  ws.closefar_fused = false;
-  ws.far_ran = false;
   vofod_handle::ClusterTables* ct = nullptr;
-  const int rt = cluster_tables(h, g, tol, cmax, &ct);
-  if (rt != VOFOD_OK)
-    return rt;
+  VCHK(cluster_tables(h, g, tol, cmax, &ct));
   const uint32_t gv = (ws.vox_cap + 255u) / 256u;
   if (want_bricks(ct, ws))
   {
@@ -1551,10 +1519,8 @@ int launch_cluster(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t
     // Batches of independent frames: the whole brick graph of a frame is clustered inside one workgroup's LDS
     // (kernels_brick_lds.h).  VOFOD_BRICK_LDS=0 keeps the global-memory kernels.
     const uint32_t lb_limit = std::getenv("VOFOD_LDS_MAX_BRICKS") ? std::min<uint32_t>(LB_MAX, std::atoi(std::getenv("VOFOD_LDS_MAX_BRICKS"))) : LB_MAX;
-    if (ws.lean_emit)
+    if (lf.lean_emit)
     {
-      (void)allow_lds;
-      ws.lean_emit = false;
       unsigned long long*& d_prof_all = h->d_prof_ccl;
       if (!d_prof_all && std::getenv("VOFOD_LDS_PROF"))
       {
@@ -1574,36 +1540,34 @@ int launch_cluster(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t
           }
       ws.prof_slot0 = prof_slot0;
       unsigned long long* d_prof = d_prof_all ? d_prof_all + 32 * static_cast<size_t>(prof_slot0) : nullptr;
-      if (ws.frame_fused)
+      if (lf.frame_fused)
       {
-        ws.frame_fused = false;
-        ws.far_ran = up_tables && mapclose && ws.close_first;
+        lf.far_ran = up_tables && mapclose && ws.close_first;
         // (four instantiations: close first or not, packed 16-byte column loads or strided ones; the profile names the algorithmic
         // variant only: k_frame_lds_far / k_frame_lds_full)
 #define VOFOD_FRAME_LAUNCH(label, kern, UP, WT, CF)                                                                                                                                          \
   KLAUNCH_AS(h, label, kern, dim3(n), dim3(FR_THREADS), g, bp, ct->d_lbtab, ws.d_hdrs, ws.sa, ws.pt_cap, ws.va, ws.d_labels, lb_limit, reinterpret_cast<uint32_t*>(ws.d_table), ws.fs, h->mg, mapclose, \
-          h->d_mapbits, h->d_crows, h->closetab.n_rows, UP, ws.d_table, ws.d_cand, WT, d_prof, ws.ref_lattice, ws.d_args, CF)
+          h->d_mapbits, h->d_crows, h->closetab.n_rows, UP, ws.d_table, ws.d_cand, WT, d_prof, lf.ref_lattice, ws.d_args, CF)
         const UpdateParams up_none{};
-        if (ws.far_ran)  // read-only batches: cluster the far voxels only (the close-first instantiation)
+        if (lf.far_ran)  // read-only batches: cluster the far voxels only (the close-first instantiation)
         {
-          if (ws.in_packed)
+          if (lf.in_packed)
             VOFOD_FRAME_LAUNCH("k_frame_lds_far", k_frame_lds_far_p, *up_tables, 1, ws.close_first);
           else
             VOFOD_FRAME_LAUNCH("k_frame_lds_far", k_frame_lds_far, *up_tables, 1, ws.close_first);
         }
         else
         {
-          if (ws.in_packed)
+          if (lf.in_packed)
             VOFOD_FRAME_LAUNCH("k_frame_lds_full", k_frame_lds_full_p, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0);
           else
             VOFOD_FRAME_LAUNCH("k_frame_lds_full", k_frame_lds_full, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0);
         }
 #undef VOFOD_FRAME_LAUNCH
-        ws.finalize_fused = up_tables && mapclose;
+        lf.finalize_fused = up_tables && mapclose;
         if (d_prof && !ws.prof_deferred)
-          if (const int pr = print_frame_prof(h, 0, n, true); pr != VOFOD_OK)
-            return pr;
-        ws.closefar_fused = mapclose != nullptr;
+          VCHK(print_frame_prof(h, 0, n, true));
+        lf.closefar_fused = mapclose != nullptr;
         HIPCHK(hipGetLastError());
         return VOFOD_OK;
       }
@@ -1611,9 +1575,8 @@ int launch_cluster(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t
       h->err = "internal: lean emission without the frame kernel";
       return VOFOD_ERR_DEVICE;
     }
-    if (!ws.bricks_preset)
+    if (!lf.bricks_preset)
       KLAUNCH(h, k_brick_set, fgrid(g, gv), dim3(256), g, bp, ws.d_hdrs, ws.va, ws.ba);
-    ws.bricks_preset = false;
     // the stencil's pairs as per-brick connectivity masks + transitive reduction; a stencil beyond 64 offsets (or without the
     // pair tables) takes the fused probe + union kernel.  (Round 1 also had "masks + batched hooking" behind VOFOD_BRICK_MODE=2:
     // CAS storms, 470 us against 206 us - removed in round 4.)
@@ -1635,7 +1598,7 @@ int launch_cluster(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t
     KLAUNCH(h, k_union<2>, fgrid(g, gv), dim3(256), g, ct->cp, ct->d_rows, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va);
     KLAUNCH(h, k_flatten<0>, fgrid(g, gv), dim3(256), g, ws.d_hdrs, ws.va, ws.d_labels, ws.ba, 0u, h->mg, mapclose, h->d_mapbits, h->d_crows, h->closetab.n_rows);
   }
-  ws.closefar_fused = mapclose != nullptr;  // k_flatten answered hasCloseTo through the dilated image
+  lf.closefar_fused = mapclose != nullptr;  // k_flatten answered hasCloseTo through the dilated image
   HIPCHK(hipGetLastError());
   return VOFOD_OK;
 }
@@ -1788,9 +1751,7 @@ int host_explore_frame(vofod_handle* h, std::vector<HostCluster>& cl, const vt::
       }
     }
     vt::Box box;
-    int r = read_box(h, h->d_map, lo, hi, box);
-    if (r != VOFOD_OK)
-      return r;
+    VCHK(read_box(h, h->d_map, lo, hi, box));
     for (const uint64_t li : pending)
     {
       int i3[3];
@@ -1819,9 +1780,7 @@ int host_explore_frame(vofod_handle* h, std::vector<HostCluster>& cl, const vt::
   }
   if (!no_update && !pending.empty())
   {
-    const int r = scatter_set(h, h->d_map, pending, thr_frontiers);
-    if (r != VOFOD_OK)
-      return r;
+    VCHK(scatter_set(h, h->d_map, pending, thr_frontiers));
     h->mapbits_valid = false;
   }
   // uncertainty sums (:851-865) after every frontier write of the frame
@@ -1834,9 +1793,7 @@ int host_explore_frame(vofod_handle* h, std::vector<HostCluster>& cl, const vt::
     const vt::MemberSpan mem = by_root.of(cl[ci].rec.root);
     int mn[3] = {job.box_lo[0], job.box_lo[1], job.box_lo[2]}, mx[3] = {job.box_hi[0], job.box_hi[1], job.box_hi[2]};
     vt::Box sub;
-    const int r = read_box(h, h->d_map, mn, mx, sub);
-    if (r != VOFOD_OK)
-      return r;
+    VCHK(read_box(h, h->d_map, mn, mx, sub));
     if (no_update)
       for (const uint64_t li : pending)
       {
@@ -1861,1099 +1818,10 @@ int host_explore_frame(vofod_handle* h, std::vector<HostCluster>& cl, const vt::
   return VOFOD_OK;
 }
 
-// The body of processMsg (vofod_nodelet.cpp:926-965) for n frames.
-enum FramesPhase { FRAMES_SYNC = 0, FRAMES_LAUNCH = 1, FRAMES_COLLECT = 2 };
-
-int process_frames(vofod_handle* h, Workspace& ws, FramesPhase phase, const vofod_scan* scans, const float* tfs, uint32_t n, int flags, vofod_detection* out, size_t cap,
-                   uint32_t* n_out_per_frame, size_t* n_out, vofod_scan_debug* dbg)
-{
-  const vofod_static_params& sp = h->sp;
-  // A submitted batch is classified with the dynamic parameters of its submission: vofod_set_dynamic_params may be called
-  // between submit and collect (DetectionParams.cfg semantics: "between any two calls"), and the collect half (position sigma,
-  // min_points, the host fall-back tail) as well as the re-run of an overflowed batch must not mix the two parameter sets.
-  if (phase == FRAMES_LAUNCH && !ws.rerun)
-    ws.job_dp = h->dp;
-  const vofod_dyn_params& dp = (phase == FRAMES_SYNC) ? h->dp : ws.job_dp;
-  if (phase == FRAMES_COLLECT)
-  {
-    n = ws.job_n;
-    tfs = ws.job_tfs.data();
-    flags = VOFOD_SCAN_NO_MAP_UPDATE;
-  }
-  if (n == 0)
-  {
-    if (n_out)
-      *n_out = 0;
-    return VOFOD_OK;
-  }
-  if (n > ws.F)
-  {
-    h->err = "batch larger than max_batch_frames";
-    return VOFOD_ERR_CAPACITY;
-  }
-  const size_t npts = static_cast<size_t>(sp.sensor_hrays) * sp.sensor_vrays;
-  if (phase != FRAMES_COLLECT)
-    for (uint32_t f = 0; f < n; f++)
-    {
-      const vofod_scan& s = scans[f];
-      if (!s.x || !s.y || !s.z)
-        return VOFOD_ERR_INVALID_ARG;
-      if (static_cast<size_t>(s.width) * s.height != npts)  // :895-899
-        return VOFOD_ERR_SIZE_MISMATCH;
-    }
-  const bool no_update = flags & VOFOD_SCAN_NO_MAP_UPDATE;
-  // re-run of the batch that overflowed the LDS kernels: the flag is consumed here, whatever path this call takes (an early
-  // error return must not leave it standing for a different batch), and only a launch of the very same job reuses its inputs
-  bool rerun = false;
-  if (phase != FRAMES_COLLECT)
-  {
-    rerun = ws.rerun && ws.job_n == n;
-    ws.rerun = false;
-  }
-  int ret = VOFOD_OK;
-  bool rc_done = false;  // ++its and the raycast role of VOFOD_SCAN_AUTO_RAYCAST have run ahead of the device tail
-  auto t0 = clk::now();
-  static const bool trace = std::getenv("VOFOD_TRACE") != nullptr;
-  double tr_launch = 0, tr_sync1 = 0, tr_prep = 0, tr_explore = 0, tr_a = 0, tr_b = 0, tr_c = 0;
-  struct DbgEvents  // destroyed on every return path
-  {
-    hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~DbgEvents()
-    {
-      for (auto& x : e)
-        if (x)
-          (void)hipEventDestroy(x);
-    }
-  } dbg_events;
-  hipEvent_t* ev = dbg_events.e;
-  if (dbg)
-    for (int i = 0; i < 5; i++)
-      HIPCHK(hipEventCreate(&ev[i]));
-
-  GridParams g;
-  int r = VOFOD_OK;
-  const float thr_new = static_cast<float>(dp.voxel_map__thresholds__new_obstacles);
-  struct ChainStream
-  {
-    vofod_handle* h;
-    hipStream_t saved;
-    ChainStream(vofod_handle* h_, hipStream_t st) : h(h_), saved(h_->stream)
-    {
-      if (st)
-        h->stream = st;
-    }
-    ~ChainStream() { h->stream = saved; }
-  };
-  // In-flight batches on streams of their own overlap their kernel chains: a gain while a batch leaves CUs idle (32 / 64 /
-  // 128 frames: +31 / +56 / +16 %), a loss once one batch's kernels fill the chip (256 frames: -6 %, co-running chains only
-  // slow each other down).
-  // Round 2: the chains are staggered.  A batch's streaming kernels (bounding box, brick codes: HBM bound, a few waves per CU)
-  // start when the previous batch's have finished, i.e. while that batch's frame kernel (LDS bound, one workgroup per CU)
-  // runs: the two phases of consecutive batches share the chip instead of taking turns.
-  // (Rounds 2-3 kept VOFOD_TWO_CHAINS / VOFOD_STAGGER / VOFOD_PIPE / VOFOD_FRAME_STREAMS to switch these schemes off: lost
-  // experiments, removed in round 4 with their code paths - DESIGN 5.3 has the measurements.)
-  constexpr bool two_chains = true, stagger_on = true;
-  // Submitted batches run as a three-stage pipeline on three streams: the streaming kernels (bounding box + brick codes:
-  // vector-instruction bound, a few waves per CU) of every batch on a low-priority stream, the frame kernels (one 156 KB
-  // workgroup per CU, latency bound) on a second one, the classification tails on a third (high priority).  The streaming
-  // kernels of batch k+1 then fill the issue slots the frame kernel of batch k leaves idle, and when both are ready at the
-  // same moment the frame kernel's workgroups are placed first (a CU full of streaming waves has no room for one).
-  hipStream_t my_stream = nullptr;
-  bool staged = false;
-  if (two_chains && phase == FRAMES_LAUNCH)
-  {
-    // (a batch that leaves most CUs idle - fewer frames than half the CUs - gains more from whole chains running side by
-    // side: its frame kernel shares the chip with the frame kernels of the other batches in flight)
-    if (!h->stream_key || !h->stream_frame || n < 128u)
-    {
-      for (int t = 1; t < vofod_handle::MAX_INFLIGHT; t++)
-        if (&ws == h->slot(t))
-        {
-          if (!h->chain_stream[t])
-            HIPCHK(hipStreamCreateWithFlags(&h->chain_stream[t], hipStreamNonBlocking));
-          my_stream = h->chain_stream[t];
-        }
-    }
-    else
-    {
-      my_stream = h->stream_key;
-      staged = true;
-    }
-  }
-  if (phase != FRAMES_COLLECT)
-  {
-  ChainStream chain_guard(h, my_stream);
-  if (two_chains && stagger_on && phase == FRAMES_LAUNCH && h->ev_stagger_set)
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_stagger, 0));  // the previous batch's streaming kernels are through
-  if (two_chains && phase == FRAMES_LAUNCH && !(h->mapbits_valid && h->mapbits_thr == thr_new))
-  {
-    // the occupancy image is shared by both chains: make sure it is complete before a second stream reads it
-    r = ensure_mapbits(h, thr_new);
-    if (r != VOFOD_OK)
-      return r;
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  // ---- stage inputs, K1-K6 (filterAndTransform :621-684)
-  // (the re-run of a batch that overflowed the LDS kernels keeps the frame arguments and the staged columns of its first
-  // launch: the caller's host buffers need not outlive vofod_batch_submit)
-  // Host-resident batches whose frames are packed x | y | z columns at a constant pitch (one pcl / numpy block per batch, or
-  // per-frame blocks of one arena) cross PCIe with ONE 2-D copy command instead of three per frame: at 256 frames the 768
-  // copy calls alone cost more host time than the whole device chain.  The copy is enqueued on the streaming stage's stream:
-  // it overlaps the frame kernel and the tail of the batches in front.  (Pinned memory makes it asynchronous; a pageable
-  // source is staged by the runtime and blocks the call.)
-  bool staged_2d = false;
-  if (!rerun && n >= 2 && scans[0].memspace == VOFOD_MEM_HOST)
-  {
-    const char* x0 = static_cast<const char*>(scans[0].x);
-    const ptrdiff_t pitch = static_cast<const char*>(scans[1].x) - x0;
-    bool ok = pitch >= static_cast<ptrdiff_t>(npts * 12);
-    for (uint32_t f = 0; f < n && ok; f++)
-    {
-      const vofod_scan& s = scans[f];
-      const char* xf = x0 + static_cast<ptrdiff_t>(f) * pitch;
-      ok = s.memspace == VOFOD_MEM_HOST && s.stride_bytes == 4 && static_cast<const char*>(s.x) == xf && static_cast<const char*>(s.y) == xf + npts * 4 &&
-           static_cast<const char*>(s.z) == xf + npts * 8;
-    }
-    if (ok && ws.pt_cap == npts)
-    {
-      HIPCHK(hipMemcpy2DAsync(ws.d_stage, sizeof(float) * 5 * ws.pt_cap, x0, static_cast<size_t>(pitch), npts * 12, n, hipMemcpyHostToDevice, h->stream));
-      for (uint32_t f = 0; f < n; f++)
-      {
-        float* base = ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5;
-        const int r = stage_cloud(h, ws, f, base, base + ws.pt_cap, base + 2 * static_cast<size_t>(ws.pt_cap), nullptr, nullptr, 4, npts, VOFOD_MEM_DEVICE, FA_SCAN, tfs + 12 * f);
-        if (r != VOFOD_OK)
-          return r;
-      }
-      staged_2d = true;
-    }
-  }
-  bool host_copies = staged_2d;
-  for (uint32_t f = 0; f < n && !rerun && !staged_2d; f++)
-  {
-    const vofod_scan& s = scans[f];
-    host_copies |= s.memspace != VOFOD_MEM_DEVICE;
-    const int r = stage_cloud(h, ws, f, s.x, s.y, s.z, nullptr, nullptr, s.stride_bytes, npts, s.memspace, FA_SCAN, tfs + 12 * f);
-    if (r != VOFOD_OK)
-      return r;
-  }
-  // include/vofod.h promises that the scans' host buffers need not outlive vofod_batch_submit.  A copy from page-locked memory
-  // is truly asynchronous - and on the streaming stage's stream it is queued behind the previous batch's streaming kernels:
-  // it may start long after the call has returned, when a caller that refills its arena has already overwritten it.
-  // The event marks the end of the batch's copies; the submitting call returns behind it (below).
-  if (host_copies && phase == FRAMES_LAUNCH && ws.ev_h2d)
-    HIPCHK(hipEventRecord(ws.ev_h2d, h->stream));
-  else
-    host_copies = false;
-  // an error return between here and the wait below must not leave copies from the caller's buffers in flight
-  struct H2DGuard
-  {
-    hipEvent_t ev;
-    bool armed;
-    ~H2DGuard()
-    {
-      if (armed)
-        (void)hipEventSynchronize(ev);
-    }
-  } h2d_guard{ws.ev_h2d, host_copies};
-  const float leaf[3] = {sp.voxel_size, sp.voxel_size, sp.voxel_size};
-  const int zero[3] = {0, 0, 0};
-  float align_center[3];
-  h->hg.idxToCoord(zero, align_center);  // :664
-  fill_grid_params(h, g, leaf, true, align_center, ws);
-  // ---- tables and map images of K8/K9 (findCloseFarClusters :703-750): independent of the frames, prepared first
-  r = ensure_mapbits(h, thr_new);
-  if (r != VOFOD_OK)
-    return r;
-  // (a sensor stream's patched nVoxelsOver counters - k_finalize_far of the PREVIOUS scan - are fetched here, before this scan's
-  // own update is enqueued, and only while the count can still change something: the background latch, the debug output)
-  if (!h->background_pts_sufficient || dbg)
-    if (const int rb = refresh_bgcount(h); rb != VOFOD_OK)
-      return rb;
-  if (!h->closetab.valid || h->closetab.max_dist != static_cast<float>(dp.ground_points_max_distance))
-  {
-    std::vector<CloseRow> crows;
-    r = build_close_rows(static_cast<float>(dp.ground_points_max_distance), h->mg.vs_inv, crows);
-    if (r != VOFOD_OK)
-    {
-      h->err = "ground_points_max_distance / voxel_size exceeds the 63-bit window";
-      return r;
-    }
-    HIPCHK(hipMemcpy(h->d_crows, crows.data(), sizeof(CloseRow) * crows.size(), hipMemcpyHostToDevice));
-    h->closetab.valid = true;
-    h->closetab.max_dist = static_cast<float>(dp.ground_points_max_distance);
-    h->closetab.n_rows = static_cast<int>(crows.size());
-  }
-  CloseParams cpar{h->closetab.n_rows, thr_new};
-  // read-only batches: the map's dilated image answers hasCloseTo with one bit per voxel (VOFOD_DILATE=0: stencil sweep)
-  const bool dilate_on = !switch_off("VOFOD_DILATE");
-  const bool use_dilated = dilate_on && no_update && n >= 4;
-  if (use_dilated)
-  {
-    r = ensure_mapclose(h, cpar);
-    if (r != VOFOD_OK)
-      return r;
-  }
-  if (dbg)
-    HIPCHK(hipEventRecord(ev[0], h->stream));
-  {
-    // the clustering family is known up front, so the emission kernel can register the voxels in their bricks
-    vofod_handle::ClusterTables* ct = nullptr;
-    r = cluster_tables(h, g, static_cast<float>(dp.ground_points_max_distance), map_cmax(h), &ct);
-    if (r != VOFOD_OK)
-      return r;
-    g.sparse_prefix = want_bricks(ct, ws) ? 1u : 0u;
-    // (Fusing the brick registration into k_emit was measured slower - 194 us vs 96 + 50 us for 32 frames: the returning
-    // atomicOr sits inside the load-balanced emission loop - so it stays a kernel of its own.)
-    const bool lds_plan = plan_lds_ccl(h, ct, ws, no_update && n >= 4);
-    h->lds_ccl_off = false;  // one-shot: only the re-run of the batch that overflowed stays off the LDS kernels
-    r = launch_voxelize(h, ws, g, n, static_cast<uint32_t>(npts), false, false, nullptr, lds_plan);
-  }
-  if (r != VOFOD_OK)
-    return r;
-  if (dbg)
-    HIPCHK(hipEventRecord(ev[1], h->stream));
-  if (staged)
-  {
-    HIPCHK(hipEventRecord(ws.ev_key, h->stream));
-    // Consecutive frame kernels alternate between two streams: frame kernel k+1 waits neither for the LAST workgroup of frame
-    // kernel k (its workgroups take the CUs as those of k retire: frames last 260-350 us) nor for the 14 us launch hand-off
-    // behind it.  Measured +2..4 % (541 / 533 / 533 k against 519 / 510 / 534 k frames/s, alternating runs on one box); the
-    // pipeline's pace is then set by k_key1, which runs as a guest of the frame kernels all the time (one wave per SIMD beside a
-    // frame workgroup: ~440 us per batch).
-    h->frame_toggle = (h->frame_toggle + 1) % std::max(h->n_frame_streams, 1);
-    h->stream = h->stream_frames[h->frame_toggle];
-    HIPCHK(hipStreamWaitEvent(h->stream, ws.ev_key, 0));
-  }
-
-  // ---- K7 clusterCloud :932
-  UpdateParams up{};
-  up.score_point = static_cast<float>(dp.voxel_map__scores__point);
-  up.score_unknown = static_cast<float>(dp.voxel_map__scores__unknown);
-  up.min_points = dp.classification__min_points;
-  up.cand_max_extent = static_cast<float>(dp.classification__max_size * (1.0 + 1e-4) + 1e-3 * sp.voxel_size);
-  up.no_update = no_update;
-  // k_slab rewrites the bitmap densely and the brick clustering reads it at set bits only: no need to clean it after use;
-  // then the LDS clustering kernel can write the cluster table and the candidate list itself (nothing left for k_finalize)
-  const bool frame_path = ws.frame_fused;  // brick-first frame kernel: the global occupancy bitmaps are not touched at all
-  const bool bitmap_was_clean = ws.bitmap_clean;
-  const bool keep_dirty = frame_path || (ws.slab_bitmap && g.sparse_prefix);
-  // Read-only batches cluster close first (k_frame_lds): only the far clusters are ever used (vofod_nodelet.cpp:946-963).  The
-  // debug view of ALL clusters keeps the full clustering; dbg[0].far_only asks for the production path's view instead.
-  // VOFOD_CLOSE_FIRST=0: the full clustering everywhere.
-  const bool close_first_on = !switch_off("VOFOD_CLOSE_FIRST");
-  const bool dbg_far_only = dbg && dbg[0].far_only;
-  if (h->cf_off && (h->n_bg_voxels > h->cf_off_bg + h->cf_off_bg / 4 + 1000 || h->n_bg_voxels < h->cf_off_bg))
-    h->cf_off = false;  // the map has changed a lot since: try the close-first kernel again
-  ws.close_first = (close_first_on && use_dilated && !h->cf_off) ? (dbg ? (dbg_far_only ? 2 : 0) : 1) : 0;
-  const uint32_t gv = (ws.vox_cap + 255u) / 256u;
-  // A single map-updating scan without debug output (the reference's own mode) clusters close first on the general path
-  // (kernels_far.h): close bits from hasCloseTo's stencil with every voxel as its own cluster, then edges and unions around the
-  // far voxels only - instead of the six brick kernels over the whole frame.
-  const bool dtail_wanted = !switch_off("VOFOD_DEVICE_TAIL");
-  bool far_single = close_first_on && !h->cf_off && !dbg && !no_update && n == 1 && phase == FRAMES_SYNC && dtail_wanted && !frame_path && !keep_dirty;
-  if (far_single)
-  {
-    vofod_handle::ClusterTables* ct = nullptr;
-    r = cluster_tables(h, g, static_cast<float>(dp.ground_points_max_distance), map_cmax(h), &ct);
-    if (r != VOFOD_OK)
-      return r;
-    far_single = ct->n_rows > 0 && ws.vox_cap >= FAR_MAX;
-    if (far_single)
-    {
-      uint32_t* far_list = ws.d_labels;  // (labels are not written on this path)
-      KLAUNCH(h, k_closefar, fgrid(g, gv), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, static_cast<const uint32_t*>(nullptr), static_cast<const unsigned long long*>(nullptr), ws.d_cand,
-              ws.d_hdrs);
-      KLAUNCH(h, k_closefar_sweep, fgrid(g, (ws.vox_cap * 16u + 255u) / 256u), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_cand, far_list, ws.d_hdrs, ws.vox_cap);
-      const uint32_t items = FAR_MAX * 2u * static_cast<uint32_t>(ct->n_rows);
-      KLAUNCH(h, k_far_edges, dim3((items + 255u) / 256u), dim3(256), g, ct->cp, ct->d_rows, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va, far_list);
-      KLAUNCH(h, k_far_final, dim3(1), dim3(1024), g, ws.d_hdrs, ws.va, far_list, up, ws.d_table, ws.d_cand);
-      // The occupancy image is patched where the update flips a bit (valid while one voxel of the scan falls into one map cell -
-      // the aligned lattice - and the flood fills' frontier value is no background value: their writes then flip nothing).
-      ws.mapbits_patched = g.align && static_cast<float>(dp.voxel_map__thresholds__frontiers) <= thr_new;
-      KLAUNCH(h, k_finalize_far, dim3(gv), dim3(256), g, h->mg, up, ws.d_hdrs, ws.va, h->d_map, h->d_flags, ws.d_bitmaps, ws.mapbits_patched ? h->d_mapbits : nullptr, h->d_bgcount, thr_new);
-      ws.closefar_fused = true;
-      ws.finalize_fused = true;
-    }
-  }
-  if (!far_single)
-  {
-  r = launch_cluster(h, ws, g, n, static_cast<float>(dp.ground_points_max_distance), map_cmax(h), no_update && n >= 4, use_dilated ? h->d_mapclose : nullptr,
-                     (keep_dirty && no_update) ? &up : nullptr);
-  if (r != VOFOD_OK)
-    return r;
-  }
-  if (dbg)
-    HIPCHK(hipEventRecord(ev[2], h->stream));
-
-  // ---- K8/K9 findCloseFarClusters :703-750 (tables and images were prepared before the chain was enqueued)
-  if (!ws.closefar_fused)
-  {
-    // few frames: the undecided voxels go through a list to a sweep kernel with 16 lanes per voxel (ws.d_cand is free until
-    // k_finalize); many frames: swept in place
-    const bool split = n < 8 && !use_dilated;
-    KLAUNCH(h, k_closefar, fgrid(g, gv), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_labels, use_dilated ? h->d_mapclose : nullptr,
-            split ? ws.d_cand : nullptr, ws.d_hdrs);
-    if (split)
-      KLAUNCH(h, k_closefar_sweep, fgrid(g, (ws.vox_cap * 16u + 255u) / 256u), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_cand);
-  }
-  ws.closefar_fused = false;
-  if (dbg)
-    HIPCHK(hipEventRecord(ev[3], h->stream));
-
-  // ---- K10 updateVMaps :943-950 + cluster table + candidate members
-  if (!ws.finalize_fused)
-    KLAUNCH(h, k_finalize, fgrid(g, gv), dim3(256), g, h->mg, up, ws.d_hdrs, ws.va, ws.d_labels, h->d_map, h->d_flags, ws.d_table, ws.d_cand, keep_dirty ? nullptr : ws.d_bitmaps);
-  ws.bitmap_clean = frame_path ? bitmap_was_clean : !keep_dirty;
-  ws.finalize_fused = false;
-  const bool lite_on = !switch_off("VOFOD_LITE");
-  const bool dtail_on = !switch_off("VOFOD_DEVICE_TAIL");
-  // (round 4: a single map-updating scan - the reference's own mode - takes the device tail too: no cluster table down, explore
-  // jobs up, results down between the kernels; the flood fills then write their frontiers to the map itself, vofod_nodelet.cpp:1712-1715)
-  const bool single_update = !no_update && n == 1 && phase == FRAMES_SYNC;
-  ws.dtail = dtail_on && !dbg && ((n >= 4 && no_update) || single_update);
-  ws.lite = !ws.dtail && lite_on && !dbg && n >= 4 && no_update;
-  hipStream_t tail_stream_used = h->stream;  // where the device tail's last operation was enqueued
-  if (ws.dtail && single_update && (flags & VOFOD_SCAN_AUTO_RAYCAST))
-  {
-    // VOFOD_SCAN_AUTO_RAYCAST applies the pending raycast update (or starts a pass) between ++its and the classification
-    // (:949-963), i.e. between the kernels enqueued so far and the tail: the scan's status comes back first (a scan that has to
-    // run again, or failed, must not have moved the raycast state), then the raycast role, then the tail kernels.
-    HIPCHK(hipMemcpyAsync(&ws.h_packed[0].hdr, ws.d_hdrs, sizeof(FrameHdr), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (ws.h_packed[0].hdr.status == VOFOD_OK)
-    {
-      h->detection_its++;  // :949
-      if (h->raycast_pending)
-        raycast_finish_locked(h);
-      else
-        raycast_begin_locked(h, &scans[0], tfs);
-      rc_done = true;
-    }
-  }
-  if (ws.dtail)
-  {
-    // Classification tail on the device (kernels_tail.h): boxes + gates, flood fills, detection records; nothing comes back
-    // but the records.  The background latch (:716-721) is needed now, not at collect time.
-    if (h->bgcount_fresh)
-    {
-      if (h->ev_bgcount)
-        HIPCHK(hipEventSynchronize(h->ev_bgcount));
-      uint64_t t = 0;
-      for (int i = 0; i < MB_SLOTS; i++)
-        t += h->h_bgcount[8 * i];
-      h->n_bg_voxels = t;
-      h->bgcount_fresh = false;
-    }
-    if (h->n_bg_voxels > h->background_min_sufficient_pts)
-      h->background_pts_sufficient = true;
-    // A small submitted batch (fewer frames than half the CUs: its whole chain runs on the ticket's stream) keeps flood-fill
-    // buffers of its own and its tail on that stream: the tails of the batches in flight overlap.  On the shared tail stream
-    // they took turns - k_tail_prep + k_explore + k_tail_finish last 250-280 us in the company of other batches' frame kernels
-    // (120 us alone), and that turn WAS the pace of 32-frame batches (device timeline, tools/trace32.sh).
-    int own_tail = -1;
-    if (phase == FRAMES_LAUNCH && two_chains && !staged && n < 128u)
-      for (int t = 0; t < vofod_handle::MAX_INFLIGHT; t++)
-        if (&ws == h->slot(t))
-          own_tail = t;
-    ExploreBufs& eb = own_tail >= 0 ? h->explore_slot[own_tail] : h->explore;
-    {
-      const uint32_t ebF = own_tail >= 0 ? std::max<uint32_t>(eb.F, (n + 31u) & ~31u) : h->ws.F;
-      r = ensure_explore(h, eb, ebF, static_cast<size_t>(ebF) * vtd::TP_MAXC, static_cast<size_t>(ebF) * vtd::TP_MAXM);
-    }
-    if (r != VOFOD_OK)
-      return r;
-    // A submitted batch runs its tail on the handle's tail stream: one wave per frame does the flood
-    // fills (latency bound, ~0.1 ms), which overlaps with the streaming kernels of the next batch instead of delaying them.
-    // The tail stream also serialises the tails of the batches in flight on the shared flood-fill buffers.
-    hipStream_t chain_stream = h->stream;
-    struct TailStream
-    {
-      vofod_handle* h;
-      hipStream_t saved;
-      ~TailStream() { h->stream = saved; }
-    } tail_guard{h, h->stream};
-    if (!h->ev_explore)
-      HIPCHK(hipEventCreateWithFlags(&h->ev_explore, hipEventDisableTiming));
-    // (large batches: the tails take turns on the tail stream, underneath the frame kernel of the next batch)
-    if (own_tail >= 0)
-      ;  // (own buffers, own stream: nothing to wait for)
-    else if (phase == FRAMES_LAUNCH && h->stream_tail)
-    {
-      HIPCHK(hipEventRecord(ws.ev_packed, chain_stream));  // the cluster tables of this batch are complete
-      h->stream = h->stream_tail;
-      HIPCHK(hipStreamWaitEvent(h->stream, ws.ev_packed, 0));
-    }
-    else
-      HIPCHK(hipStreamWaitEvent(h->stream, h->ev_explore, 0));  // (a synchronous call: wait for the tails of batches in flight)
-    vtd::TailParams tp{};
-    tp.min_points = dp.classification__min_points;
-    tp.max_distance = dp.classification__max_distance;
-    tp.max_size = dp.classification__max_size;
-    tp.max_explore = dp.classification__max_explore_distance;
-    tp.voxel_size = sp.voxel_size;
-    tp.latches = (h->background_pts_sufficient && h->sure_background_sufficient) ? 1 : 0;
-    vc::ExploreParams ep{};
-    ep.thr_unknown = static_cast<float>(dp.voxel_map__thresholds__frontiers);
-    ep.thr_ground = thr_new;
-    ep.frontier_value = static_cast<float>(dp.voxel_map__thresholds__frontiers);
-    ep.ray_score = dp.voxel_map__scores__ray;
-    ep.no_update = no_update ? 1 : 0;
-    ep.stack_cap = vc::EX_CELLS;
-    // the records (135 KB) go straight into the pinned host slots from the last tail kernel: no copy command on any stream (see k_tail_finish)
-    static const bool diag_no_tail = std::getenv("VOFOD_DIAG_NO_TAIL") != nullptr;  // (diagnostics: timing of the pipeline without the tail kernel - results are wrong)
-    if (diag_no_tail && n >= 128u)
-      ;
-    else if ((ws.far_ran && ws.close_first == 1) || far_single)
-      // close-first frames: ordered lists from the frame kernel (or k_far_final), the whole tail in one kernel of one wave per frame
-      KLAUNCH(h, vtd::k_tail_far, dim3((n + vtd::TAIL_WPB - 1) / vtd::TAIL_WPB), dim3(64 * vtd::TAIL_WPB), g, ws.d_hdrs, ws.d_args, ws.d_table, ws.d_cand, ws.va, h->mg, tp, ep, eb.d_jobs, eb.d_members, h->d_map, eb.d_overlay, eb.d_stack, eb.d_explored, eb.d_touched,
-              eb.d_ovl_list, eb.d_ovl_count, eb.d_results, eb.d_visited, ws.d_dets, ws.h_dets_dev, far_single ? ws.d_tailc : static_cast<vtd::TailCluster*>(nullptr),
-              (ws.prof_deferred && h->d_prof_ccl && !far_single) ? h->d_prof_ccl + 32 * static_cast<size_t>(ws.prof_slot0) : static_cast<unsigned long long*>(nullptr));
-    else
-    {
-      KLAUNCH(h, vtd::k_tail_prep, dim3(n), dim3(vtd::TP_THREADS), g, ws.d_hdrs, ws.d_args, ws.d_table, ws.d_cand, ws.va, h->mg, tp, eb.d_jobs, ws.d_job_be, ws.d_job_be + ws.F, eb.d_members, ws.d_tailc,
-              ws.d_dets);
-      KLAUNCH(h, vc::k_explore, dim3(n), dim3(64), ep, h->mg, eb.d_jobs, ws.d_job_be, ws.d_job_be + ws.F, eb.d_members, h->d_map, eb.d_overlay, eb.d_stack, eb.d_explored, eb.d_touched, eb.d_ovl_list,
-              eb.d_ovl_count, eb.d_results, eb.d_visited);
-      KLAUNCH(h, vtd::k_tail_finish, dim3(n), dim3(64), ws.d_tailc, eb.d_results, ws.d_dets, ws.h_dets_dev);
-    }
-    if (own_tail < 0)
-      HIPCHK(hipEventRecord(h->ev_explore, h->stream));  // the shared flood-fill buffers are free again
-    tail_stream_used = h->stream;
-  }
-  else if (ws.lite)
-  {
-    KLAUNCH(h, k_pack_lite, dim3(n), dim3(256), g, ws.d_hdrs, ws.d_table, ws.d_cand, ws.va, ws.d_lite);
-    if (phase == FRAMES_LAUNCH)
-    {
-      HIPCHK(hipEventRecord(ws.ev_packed, h->stream));
-      HIPCHK(hipStreamWaitEvent(ws.copy_stream, ws.ev_packed, 0));
-      HIPCHK(hipMemcpyAsync(ws.h_lite, ws.d_lite, sizeof(PackedLite) * n, hipMemcpyDeviceToHost, ws.copy_stream));
-    }
-    else
-      HIPCHK(hipMemcpyAsync(ws.h_lite, ws.d_lite, sizeof(PackedLite) * n, hipMemcpyDeviceToHost, h->stream));
-  }
-  else
-  {
-    KLAUNCH(h, k_pack, fgrid(g, (std::max(SPEC_C, SPEC_M) + 255) / 256), dim3(256), g, ws.d_hdrs, ws.d_table, ws.d_cand, ws.va, ws.d_packed);
-    HIPCHK(hipMemcpyAsync(ws.h_packed, ws.d_packed, sizeof(PackedFrame) * n, hipMemcpyDeviceToHost, h->stream));
-  }
-  if (dbg)
-    HIPCHK(hipEventRecord(ev[4], h->stream));
-  tr_launch = ms_since(t0);
-  if (phase == FRAMES_LAUNCH)
-  {
-    h2d_guard.armed = false;
-    if (host_copies)
-      HIPCHK(hipEventSynchronize(ws.ev_h2d));  // (the whole chain is enqueued by now: the device works while the host waits for the link)
-    HIPCHK(hipEventRecord(ws.ev_done, ws.dtail ? tail_stream_used : ws.lite ? ws.copy_stream : h->stream));
-    ws.pending = true;
-    ws.job_n = n;
-    ws.job_g = g;
-    if (tfs != ws.job_tfs.data())
-      ws.job_tfs.assign(tfs, tfs + 12 * static_cast<size_t>(n));
-    if (scans != ws.job_scans.data())
-      ws.job_scans.assign(scans, scans + n);
-    return VOFOD_OK;
-  }
-  }  // launch part
-  else
-    g = ws.job_g;
-  if (phase == FRAMES_COLLECT)
-  {
-    HIPCHK(hipEventSynchronize(ws.ev_done));
-    ws.pending = false;
-    if (ws.prof_deferred && h->d_prof_ccl)
-    {
-      ws.prof_deferred = false;
-      if (const int pr = print_frame_prof(h, ws.prof_slot0, n, false); pr != VOFOD_OK)
-        return pr;
-    }
-  }
-  else
-  {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (ws.prof_deferred && h->d_prof_ccl)
-    {
-      ws.prof_deferred = false;
-      if (const int pr = print_frame_prof(h, ws.prof_slot0, n, false); pr != VOFOD_OK)
-        return pr;
-    }
-  }
-  tr_sync1 = ms_since(t0);
-  if (ws.lite)
-    for (uint32_t f = 0; f < n; f++)
-      ws.h_packed[f].hdr = ws.h_lite[f].hdr;  // the tail below reads the frames through the packed slots
-  if (ws.dtail)
-    for (uint32_t f = 0; f < n; f++)
-      ws.h_packed[f].hdr.status = ws.h_dets[f].status;
-  for (uint32_t f = 0; f < n; f++)
-    if (ws.h_packed[f].hdr.status == CCL_RETRY_STATUS)
-    {
-      // a frame held more bricks than the LDS clustering kernel takes: nothing of this batch was used (batches never
-      // update the map); the caller runs it again on the global-memory kernels
-      h->lds_ccl_off = true;
-      ws.rerun = true;
-      ws.job_n = n;
-      ws.bitmap_clean = false;
-      return CCL_RETRY_STATUS;
-    }
-  if (!no_update)
-  {
-    bool keep = false;
-    if (ws.mapbits_patched)
-    {
-      // (the image was patched by k_finalize_far - unless the scan has to run again or left the map: then it is rebuilt)
-      keep = ws.h_packed[0].hdr.status == VOFOD_OK && h->mapbits_valid;
-      ws.mapbits_patched = false;
-    }
-    if (keep)
-    {
-      h->bgcount_stale = true;  // (the counters on the device are newer than the host's sum: fetched when somebody needs it)
-      h->mapbits_gen++;         // (the dilated image of the batches is of an older state)
-    }
-    else
-      h->mapbits_valid = false;
-  }
-
-  if (h->bgcount_fresh)
-  {
-    if (h->ev_bgcount)
-      HIPCHK(hipEventSynchronize(h->ev_bgcount));  // the copy may have been enqueued on another chain's stream
-    uint64_t t = 0;
-    for (int i = 0; i < MB_SLOTS; i++)
-      t += h->h_bgcount[8 * i];
-    h->n_bg_voxels = t;
-    h->bgcount_fresh = false;
-  }
-  // (n_bg_voxels is the count findCloseFarClusters saw, i.e. of the map BEFORE this call's update; counters patched by this very
-  // call - bgcount_stale set above - belong to the next one and are not fetched here)
-  if (h->n_bg_voxels > h->background_min_sufficient_pts)  // :716-721
-    h->background_pts_sufficient = true;
-  for (uint32_t f = 0; f < n; f++)
-    if (ws.h_packed[f].hdr.status == CF_RETRY_STATUS)
-    {
-      // a frame with more pure-far bricks than the close-first kernel takes: nothing of this batch was used; the caller runs
-      // it again (same descriptors, staged columns kept) with the full clustering
-      h->cf_off = true;
-      h->cf_off_bg = h->n_bg_voxels;
-      ws.rerun = true;
-      ws.job_n = n;
-      return CCL_RETRY_STATUS;
-    }
-  if (!no_update && !rc_done)
-  {
-    h->detection_its++;  // :949
-    if (flags & VOFOD_SCAN_AUTO_RAYCAST)
-    {
-      if (h->raycast_pending)
-        raycast_finish_locked(h);
-      else
-        raycast_begin_locked(h, &scans[0], tfs);
-    }
-  }
-  double dev_ms[5] = {0, 0, 0, 0, 0};
-  if (dbg)
-  {
-    for (int i = 0; i < 4; i++)
-    {
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-      dev_ms[i] = ms;
-    }
-  }
-
-  if (ws.dtail)
-  {
-    // ---- the tail ran on the device: extractDetections' record (:848-877) from the raw detections, frame by frame
-    uint32_t fb = 0;
-    for (uint32_t f = 0; f < n; f++)
-      fb |= ws.h_dets[f].fallback;
-    if (!fb)
-    {
-      size_t total = 0;
-      if (phase == FRAMES_COLLECT && out)
-      {
-        // an output array too small for this batch: nothing is consumed - the ticket stays pending, ids are not handed
-        // out, *n_out tells the size to come back with
-        size_t need = 0;
-        for (uint32_t f = 0; f < n; f++)
-          need += ws.h_dets[f].n;
-        if (need > cap)
-        {
-          ws.pending = true;
-          *n_out = need;
-          return VOFOD_ERR_CAPACITY;
-        }
-      }
-      for (uint32_t f = 0; f < n; f++)
-      {
-        const vtd::FrameDets& D = ws.h_dets[f];
-        if (D.status != VOFOD_OK)
-          ret = D.status;
-        const float* tf = tfs + 12 * f;
-        const float tpos[3] = {tf[3], tf[7], tf[11]};
-        for (uint32_t i = 0; i < D.n; i++)
-        {
-          const vtd::DetRaw& R = D.d[i];
-          vofod_detection det{};
-          const float d[3] = {tpos[0] - R.center[0], tpos[1] - R.center[1], tpos[2] - R.center[2]};
-          const double det_dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-          det.id = h->last_detection_id++;
-          det.frame = f;
-          det.n_points = R.n_points;
-          const float cov = static_cast<float>(std::sqrt(det_dist) * dp.output__position_sigma);
-          for (int q = 0; q < 3; q++)
-            det.covariance[4 * q] = cov;
-          const double u = R.conf_sum / R.n_points;  // :860-865
-          det.confidence = static_cast<float>(1.0 / std::exp(u));
-          const double vray_res = sp.sensor_vfov / static_cast<double>(sp.sensor_vrays);
-          const double hray_res = 2 * M_PI / static_cast<double>(sp.sensor_hrays);
-          det.detection_probability = std::min(std::atan(1.0 / det_dist) / (vray_res * dp.classification__min_points), 1.0) * std::min(std::atan(1.0 / det_dist) / hray_res, 1.0);
-          for (int a = 0; a < 3; a++)
-            det.position[a] = R.center[a];
-          if (out && total < cap)
-            out[total] = det;
-          total++;
-        }
-        if (n_out_per_frame)
-          n_out_per_frame[f] = D.n;
-      }
-      if (trace)
-        std::fprintf(stderr, "[vofod trace] n=%u device tail: sync %.3f end %.3f ms, %zu detections\n", n, tr_sync1, ms_since(t0), total);
-      *n_out = total;
-      if (total > cap)
-        ret = VOFOD_ERR_CAPACITY;
-      return ret;
-    }
-    if (!no_update && (fb & (vtd::TAIL_FB_DETS | vtd::TAIL_FB_EXPLORE)))
-    {
-      // A map-updating scan whose flood fills have already written their frontiers to the map: the tail cannot be run again.
-      // More detections than the record slots hold (TP_MAXD per frame): everything needed is on the device - the clusters in
-      // canonical order (d_tailc) and their explore results.  (A work list overflow cannot happen for radii the device accepts.)
-      if (fb & vtd::TAIL_FB_EXPLORE)
-      {
-        h->err = "device tail: flood-fill work list overflow";
-        return VOFOD_ERR_DEVICE;
-      }
-      std::vector<vtd::TailCluster> tc(vtd::TP_MAXC);
-      std::vector<vc::ExploreResult> res(vtd::TP_MAXC);
-      HIPCHK(hipMemcpy(tc.data(), ws.d_tailc, sizeof(vtd::TailCluster) * vtd::TP_MAXC, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(res.data(), h->explore.d_results, sizeof(vc::ExploreResult) * vtd::TP_MAXC, hipMemcpyDeviceToHost));  // (frame 0: result slots 0..TP_MAXC-1)
-      size_t total = 0;
-      const float* tf = tfs;
-      for (int c = 0; c < vtd::TP_MAXC; c++)
-      {
-        if (tc[c].job < 0 || tc[c].job >= vtd::TP_MAXC || !res[tc[c].job].floating)
-          continue;
-        vofod_detection det{};
-        const float d[3] = {tf[3] - tc[c].obb_center[0], tf[7] - tc[c].obb_center[1], tf[11] - tc[c].obb_center[2]};
-        const double det_dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        det.id = h->last_detection_id++;
-        det.frame = 0;
-        det.n_points = tc[c].n_members;
-        const float cov = static_cast<float>(std::sqrt(det_dist) * dp.output__position_sigma);
-        for (int q = 0; q < 3; q++)
-          det.covariance[4 * q] = cov;
-        const double u = res[tc[c].job].conf_sum / tc[c].n_members;  // :860-865
-        det.confidence = static_cast<float>(1.0 / std::exp(u));
-        const double vray_res = sp.sensor_vfov / static_cast<double>(sp.sensor_vrays);
-        const double hray_res = 2 * M_PI / static_cast<double>(sp.sensor_hrays);
-        det.detection_probability = std::min(std::atan(1.0 / det_dist) / (vray_res * dp.classification__min_points), 1.0) * std::min(std::atan(1.0 / det_dist) / hray_res, 1.0);
-        for (int a = 0; a < 3; a++)
-          det.position[a] = tc[c].obb_center[a];
-        if (out && total < cap)
-          out[total] = det;
-        total++;
-      }
-      if (n_out_per_frame)
-        n_out_per_frame[0] = static_cast<uint32_t>(total);
-      *n_out = total;
-      return total > cap ? VOFOD_ERR_CAPACITY : ret;
-    }
-    // a frame exceeded a capacity of the device tail: the host tail redoes the batch from the full tables
-    // (capacities of k_tail_prep - members, clusters, radius: no flood fill has run yet, also on a map-updating scan)
-    ws.dtail = false;
-    KLAUNCH(h, k_pack, fgrid(g, (std::max(SPEC_C, SPEC_M) + 255) / 256), dim3(256), g, ws.d_hdrs, ws.d_table, ws.d_cand, ws.va, ws.d_packed);
-    HIPCHK(hipMemcpyAsync(ws.h_packed, ws.d_packed, sizeof(PackedFrame) * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  // ---- tail: classifyClusters :961 + extractDetections :963.
-  // Host: canonical cluster order, OBB + gates of the few candidate clusters.  Device (k_explore): the flood
-  // fills and uncertainty sums, one wave per frame, jobs of a frame in the reference's order.
-  const auto t_tail = clk::now();
-  const float thr_frontiers = static_cast<float>(dp.voxel_map__thresholds__frontiers);
-  struct FrameTail
-  {
-    std::vector<HostCluster> cl;
-    vt::MemberIndex by_root;
-    std::vector<int> job_of;  // per cluster: index into jobs or -1
-    bool host_fallback = false;
-  };
-  std::vector<FrameTail> tails(n);
-  std::vector<vc::ExploreJob> jobs;
-  std::vector<uint32_t> job_begin(n + 1, 0);
-  std::vector<int> job_members;
-  const bool latches = h->background_pts_sufficient && h->sure_background_sufficient;
-  // phase A (serial): frames whose tables overflowed the speculative read-back fetch the rest
-  std::vector<std::vector<ClusterRec>> recs_big(n);
-  std::vector<std::vector<CandMemberX>> members_big(n);
-  std::vector<uint8_t> big_recs(n, 0), big_members(n, 0);
-  for (uint32_t f = 0; f < n; f++)
-  {
-    FrameHdr& hdr = ws.h_packed[f].hdr;
-    if (hdr.status != VOFOD_OK)
-      ret = hdr.status;
-    if (ws.lite)
-    {
-      // lite read-back: only the candidate clusters' records came back; the header's C becomes their number
-      const PackedLite& L = ws.h_lite[f];
-      PackedFrame& pf = ws.h_packed[f];
-      if (L.n_recs <= LITE_C)
-      {
-        std::memcpy(pf.table, L.recs, sizeof(ClusterRec) * L.n_recs);
-        static_assert(LITE_C <= SPEC_C && LITE_M <= SPEC_M, "the lite lists are unpacked into the packed slot");
-      }
-      else
-      {
-        // more candidate clusters than the lite slot holds: fetch the frame's whole table, keep the candidates
-        std::vector<ClusterRec> all(hdr.C);
-        HIPCHK(hipMemcpy(all.data(), ws.d_table + static_cast<size_t>(f) * ws.vox_cap, sizeof(ClusterRec) * hdr.C, hipMemcpyDeviceToHost));
-        for (const ClusterRec& r : all)
-          if (r.cand && !r.close)
-            recs_big[f].push_back(r);
-        big_recs[f] = 1;
-      }
-      hdr.C = L.n_recs;
-      if (L.n_members <= LITE_M)
-        std::memcpy(pf.members, L.members, sizeof(CandMemberX) * L.n_members);
-      else
-        big_members[f] = 1;
-    }
-    else
-    {
-      big_recs[f] = hdr.C > SPEC_C;
-      big_members[f] = hdr.n_cand > SPEC_M;
-      if (big_recs[f])
-      {
-        recs_big[f].resize(hdr.C);
-        HIPCHK(hipMemcpy(recs_big[f].data(), ws.d_table + static_cast<size_t>(f) * ws.vox_cap, sizeof(ClusterRec) * hdr.C, hipMemcpyDeviceToHost));
-      }
-    }
-    if (big_members[f])
-    {
-      members_big[f].resize(hdr.n_cand);
-      CandMemberX* d_tmp = static_cast<CandMemberX*>(ws.d_members_big);  // n_cand <= V <= vox_cap: sized with the workspace
-      KLAUNCH(h, k_gather_members, dim3((hdr.n_cand + 255) / 256), dim3(256), g, f, hdr.n_cand, ws.d_cand, ws.va, d_tmp);
-      HIPCHK(hipMemcpyAsync(members_big[f].data(), d_tmp, sizeof(CandMemberX) * hdr.n_cand, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-    }
-  }
-  // phase B (parallel over frames): canonical order, member index, boxes and gates, the frame's explore jobs
-  std::vector<std::vector<vc::ExploreJob>> jobs_f(n);
-  std::vector<std::vector<int>> members_f(n);
-  auto prep_frame = [&](uint32_t f) {
-    FrameTail& T = tails[f];
-    const PackedFrame& pf = ws.h_packed[f];
-    const FrameHdr& hdr = pf.hdr;
-    const ClusterRec* recs = big_recs[f] ? recs_big[f].data() : pf.table;
-    const CandMemberX* members = big_members[f] ? members_big[f].data() : pf.members;
-    // canonical order: size desc, smallest member asc
-    T.cl.resize(hdr.C);
-    for (uint32_t c = 0; c < hdr.C; c++)
-      T.cl[c].rec = recs[c];
-    std::sort(T.cl.begin(), T.cl.end(), [](const HostCluster& a, const HostCluster& b) {
-      if (a.rec.size != b.rec.size)
-        return a.rec.size > b.rec.size;
-      return a.rec.root < b.rec.root;
-    });
-    {
-      std::vector<std::pair<uint64_t, vt::Member>> tmp(hdr.n_cand);
-      for (uint32_t i = 0; i < hdr.n_cand; i++)
-      {
-        const CandMemberX& m = members[i];
-        tmp[i] = {(static_cast<uint64_t>(m.root) << 32) | m.v, vt::Member{m.v, {m.x, m.y, m.z}, m.count}};
-      }
-      T.by_root.build(tmp);
-    }
-    T.job_of.assign(hdr.C, -1);
-    const float* tf = tfs + 12 * f;
-    const float tpos[3] = {tf[3], tf[7], tf[11]};
-    std::vector<vc::ExploreJob>& jl = jobs_f[f];
-    std::vector<int>& ml = members_f[f];
-    // classify_cluster :1648-1690: boxes and gates
-    for (uint32_t ci = 0; ci < hdr.C; ci++)
-    {
-      HostCluster& c = T.cl[ci];
-      if (c.rec.close)
-        continue;
-      c.cclass = VOFOD_CLASS_INVALID;
-      if (!c.rec.cand)
-        continue;  // fails min_points or cannot pass max_size (device-side gate)
-      const vt::MemberSpan mem = T.by_root.of(c.rec.root);
-      c.boxes = vt::boxes_of(mem);
-      c.evaluated = true;
-      if (static_cast<int>(mem.size()) < dp.classification__min_points)
-        continue;
-      {
-        const float d[3] = {tpos[0] - c.boxes.obb_center[0], tpos[1] - c.boxes.obb_center[1], tpos[2] - c.boxes.obb_center[2]};
-        const double dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        if (dist > dp.classification__max_distance)
-          continue;
-      }
-      {
-        const float d[3] = {c.boxes.obb_max[0] - c.boxes.obb_min[0], c.boxes.obb_max[1] - c.boxes.obb_min[1], c.boxes.obb_max[2] - c.boxes.obb_min[2]};
-        c.obb_size = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        if (c.obb_size > dp.classification__max_size)
-          continue;
-      }
-      if (!latches)  // :1694, :1719-1722
-      {
-        c.cclass = VOFOD_CLASS_UNKNOWN;
-        continue;
-      }
-      vc::ExploreJob job{};
-      job.frame = f;
-      job.n_members = static_cast<uint32_t>(mem.size());
-      job.member_off = static_cast<uint32_t>(ml.size() / 3);  // rebased when the frames are concatenated
-      job.R = static_cast<int>((c.obb_size + dp.classification__max_explore_distance) / sp.voxel_size);  // :1696
-      for (const vt::Member& m : mem)
-      {
-        int o[3];
-        h->hg.coordToIdx(m.p, o);
-        ml.insert(ml.end(), o, o + 3);
-      }
-      int mn[3], mx[3];  // getSubmapCopy(aabb, inflate 2) voxel_map.cpp:550-559
-      h->hg.coordToIdx(c.boxes.aabb_min, mn);
-      h->hg.coordToIdx(c.boxes.aabb_max, mx);
-      for (int a = 0; a < 3; a++)
-      {
-        job.box_lo[a] = std::clamp(mn[a] - 2, 0, h->hg.s[a] - 1);
-        job.box_hi[a] = std::clamp(mx[a] + 2, 0, h->hg.s[a] - 1);
-      }
-      if (job.R > vc::EX_MAX_R || job.R < 0)
-        T.host_fallback = true;
-      T.job_of[ci] = static_cast<int>(jl.size());  // rebased below
-      jl.push_back(job);
-    }
-    if (jl.size() > vc::EX_MAX_JOBS)
-      T.host_fallback = true;
-  };
-  h->pool->parallel_for(n, prep_frame);
-  // phase C (serial): concatenate the frames' job lists in frame order
-  for (uint32_t f = 0; f < n; f++)
-  {
-    job_begin[f] = static_cast<uint32_t>(jobs.size());
-    const uint32_t jbase = static_cast<uint32_t>(jobs.size()), mbase = static_cast<uint32_t>(job_members.size() / 3);
-    for (vc::ExploreJob j : jobs_f[f])
-    {
-      j.member_off += mbase;
-      j.result_slot = static_cast<uint32_t>(jobs.size());
-      jobs.push_back(j);
-    }
-    job_members.insert(job_members.end(), members_f[f].begin(), members_f[f].end());
-    for (int& ji : tails[f].job_of)
-      if (ji >= 0)
-        ji += static_cast<int>(jbase);
-  }
-  job_begin[n] = static_cast<uint32_t>(jobs.size());
-
-  tr_prep = ms_since(t0);
-  std::vector<vc::ExploreResult> results(jobs.size());
-  const bool force_host = std::getenv("VOFOD_EXPLORE") && std::strcmp(std::getenv("VOFOD_EXPLORE"), "host") == 0;  // tests exercise the fallback
-  bool any_host = force_host;
-  for (const FrameTail& T : tails)
-    any_host |= T.host_fallback;
-  if (!jobs.empty() && !any_host)
-  {
-    r = ensure_explore(h, h->explore, h->ws.F, jobs.size(), job_members.size() / 3);
-    if (r != VOFOD_OK)
-      return r;
-    // a collected async batch runs its tail on a second stream so that it does not queue behind the next batch's chain
-    struct StreamSwap
-    {
-      vofod_handle* h;
-      hipStream_t saved;
-      StreamSwap(vofod_handle* h_, bool on) : h(h_), saved(h_->stream)
-      {
-        if (on)
-          h->stream = h->stream_tail;
-      }
-      ~StreamSwap() { h->stream = saved; }
-    } swap_guard(h, phase == FRAMES_COLLECT);
-    ExploreBufs& eb = h->explore;
-    if (h->ev_explore)
-      HIPCHK(hipStreamWaitEvent(h->stream, h->ev_explore, 0));  // a device tail in flight may still use the flood-fill buffers
-    HIPCHK(hipMemcpyAsync(eb.d_jobs, jobs.data(), sizeof(vc::ExploreJob) * jobs.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(eb.d_job_begin, job_begin.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(eb.d_members, job_members.data(), sizeof(int) * job_members.size(), hipMemcpyHostToDevice, h->stream));
-    vc::ExploreParams ep{};
-    ep.thr_unknown = thr_frontiers;
-    ep.thr_ground = thr_new;
-    ep.frontier_value = thr_frontiers;
-    ep.ray_score = dp.voxel_map__scores__ray;
-    ep.no_update = no_update;
-    ep.stack_cap = vc::EX_CELLS;
-    KLAUNCH(h, vc::k_explore, dim3(n), dim3(64), ep, h->mg, eb.d_jobs, eb.d_job_begin, eb.d_job_begin + 1, eb.d_members, h->d_map, eb.d_overlay, eb.d_stack, eb.d_explored, eb.d_touched,
-            eb.d_ovl_list, eb.d_ovl_count, eb.d_results, eb.d_visited);
-    HIPCHK(hipMemcpyAsync(results.data(), eb.d_results, sizeof(vc::ExploreResult) * jobs.size(), hipMemcpyDeviceToHost, h->stream));
-    if (h->ev_explore)
-      HIPCHK(hipEventRecord(h->ev_explore, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (!no_update)
-      h->mapbits_valid = false;
-  }
-
-  tr_explore = ms_since(t0);
-  size_t total = 0;
-  for (uint32_t f = 0; f < n; f++)
-  {
-    FrameTail& T = tails[f];
-    const FrameHdr& hdr = ws.h_packed[f].hdr;
-    const float* tf = tfs + 12 * f;
-    const float tpos[3] = {tf[3], tf[7], tf[11]};
-    uint32_t n_det_frame = 0;
-    if (any_host && job_begin[f + 1] > job_begin[f])
-    {
-      // fallback (Manhattan radius or job count beyond the device kernel's limits): sequential host path over read-back boxes
-      r = host_explore_frame(h, T.cl, T.by_root, T.job_of, jobs, results, no_update, thr_frontiers, thr_new, dp);
-      if (r != VOFOD_OK)
-        return r;
-    }
-    for (uint32_t ci = 0; ci < hdr.C; ci++)
-    {
-      HostCluster& c = T.cl[ci];
-      const int ji = T.job_of[ci];
-      if (ji < 0)
-        continue;
-      c.cclass = results[ji].floating ? VOFOD_CLASS_MAV : VOFOD_CLASS_UNKNOWN;
-    }
-    // extractDetections :834-879
-    for (uint32_t ci = 0; ci < hdr.C; ci++)
-    {
-      HostCluster& c = T.cl[ci];
-      if (c.rec.close || c.cclass != VOFOD_CLASS_MAV)
-        continue;
-      const vt::MemberSpan mem = T.by_root.of(c.rec.root);
-      vofod_detection det{};
-      const float d[3] = {tpos[0] - c.boxes.obb_center[0], tpos[1] - c.boxes.obb_center[1], tpos[2] - c.boxes.obb_center[2]};
-      const double det_dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-      det.id = h->last_detection_id++;
-      det.frame = f;
-      det.n_points = mem.size();
-      const float cov = static_cast<float>(std::sqrt(det_dist) * dp.output__position_sigma);
-      for (int q = 0; q < 3; q++)
-        det.covariance[4 * q] = cov;
-      const double u = results[T.job_of[ci]].conf_sum / mem.size();  // :860-865
-      det.confidence = static_cast<float>(1.0 / std::exp(u));
-      const double vray_res = sp.sensor_vfov / static_cast<double>(sp.sensor_vrays);
-      const double hray_res = 2 * M_PI / static_cast<double>(sp.sensor_hrays);
-      det.detection_probability = std::min(std::atan(1.0 / det_dist) / (vray_res * dp.classification__min_points), 1.0) * std::min(std::atan(1.0 / det_dist) / hray_res, 1.0);
-      for (int a = 0; a < 3; a++)
-        det.position[a] = c.boxes.obb_center[a];
-      if (out && total < cap)
-        out[total] = det;
-      total++;
-      n_det_frame++;
-    }
-    if (n_out_per_frame)
-      n_out_per_frame[f] = n_det_frame;
-
-    if (dbg)
-    {
-      vofod_scan_debug& d = dbg[f];
-      d.n_input_after_crop = hdr.n_in;
-      d.n_bg_voxels = h->n_bg_voxels;
-      d.background_pts_sufficient = h->background_pts_sufficient;
-      d.sure_background_sufficient = h->sure_background_sufficient;
-      // far-only view (dbg[0].far_only): what the production path of a read-only batch computes - the far clusters, and labels
-      // for their voxels only.  A frame that went through the full clustering all the same (no dilated image, more pure-far
-      // bricks than the close-first path takes, VOFOD_CLOSE_FIRST=0) is cut down to that view here.
-      const bool far_view = dbg[0].far_only != 0;
-      uint32_t n_shown = hdr.C;
-      if (far_view && !hdr.far_only)
-      {
-        n_shown = 0;
-        for (uint32_t c = 0; c < hdr.C; c++)
-          n_shown += T.cl[c].rec.close ? 0u : 1u;
-      }
-      d.n_weighted = hdr.V;
-      d.n_clusters = n_shown;
-      if ((d.weighted || d.labels) && d.weighted_cap < hdr.V)
-        ret = VOFOD_ERR_CAPACITY;
-      else
-      {
-        if (d.weighted && hdr.V)
-          HIPCHK(hipMemcpy(d.weighted, ws.va.pts + static_cast<size_t>(f) * ws.vox_cap, sizeof(float4) * hdr.V, hipMemcpyDeviceToHost));
-        if (d.labels && hdr.V)
-        {
-          HIPCHK(hipMemcpy(d.labels, ws.d_labels + static_cast<size_t>(f) * ws.vox_cap, sizeof(uint32_t) * hdr.V, hipMemcpyDeviceToHost));
-          if (far_view && !hdr.far_only)
-          {
-            std::vector<uint32_t> far_roots;
-            for (uint32_t c = 0; c < hdr.C; c++)
-              if (!T.cl[c].rec.close)
-                far_roots.push_back(T.cl[c].rec.root);
-            std::sort(far_roots.begin(), far_roots.end());
-            for (uint32_t v = 0; v < hdr.V; v++)
-              if (!std::binary_search(far_roots.begin(), far_roots.end(), d.labels[v]))
-                d.labels[v] = CF_LABEL_NONE;
-          }
-        }
-      }
-      if (d.clusters)
-      {
-        if (d.clusters_cap < n_shown)
-          ret = VOFOD_ERR_CAPACITY;
-        else
-          for (uint32_t c = 0, c_out = 0; c < hdr.C; c++)
-          {
-            const HostCluster& hc = T.cl[c];
-            if (far_view && hc.rec.close)
-              continue;
-            vofod_cluster_info& ci = d.clusters[c_out++];
-            ci.first_member = hc.rec.root;
-            ci.n_points = hc.rec.size;
-            ci.is_close = hc.rec.close;
-            ci.cclass = hc.cclass;
-            for (int a = 0; a < 3; a++)
-            {
-              ci.aabb_min[a] = (static_cast<float>(hc.rec.imin[a]) + 0.5f) * g.leaf[a] + hdr.offset[a];
-              ci.aabb_max[a] = (static_cast<float>(hc.rec.imax[a]) + 0.5f) * g.leaf[a] + hdr.offset[a];
-              ci.obb_center[a] = hc.evaluated ? hc.boxes.obb_center[a] : NAN;
-            }
-            ci.obb_size = hc.obb_size;
-          }
-      }
-      d.stage_ms[0] = dev_ms[0];
-      d.stage_ms[1] = dev_ms[1];
-      d.stage_ms[2] = dev_ms[2];
-      d.stage_ms[3] = dev_ms[3];
-      d.stage_ms[4] = ms_since(t_tail);
-      d.stage_ms[5] = ms_since(t0);
-    }
-  }
-  if (trace)
-  {
-    size_t sumC = 0, sumCand = 0, sumEval = 0;
-    for (uint32_t f = 0; f < n; f++)
-    {
-      sumC += ws.h_packed[f].hdr.C;
-      sumCand += ws.h_packed[f].hdr.n_cand;
-      for (const auto& c : tails[f].cl)
-        sumEval += c.evaluated;
-    }
-    std::fprintf(stderr, "[vofod trace] n=%u launch %.3f sync1 %.3f prep %.3f explore %.3f end %.3f ms jobs %zu C %zu cand_members %zu evaluated %zu | sort %.3f gates %.3f\n", n, tr_launch, tr_sync1,
-                 tr_prep, tr_explore, ms_since(t0), jobs.size(), sumC, sumCand, sumEval, tr_a, tr_b);
-    (void)tr_c;
-  }
-  *n_out = total;
-  if (total > cap)
-    ret = VOFOD_ERR_CAPACITY;
-  return ret;
-}
-
 }  // namespace
 
+#include "frames_launch.h"
+#include "frames_collect.h"
 #include "driver_aux.h"
 #include "collective.h"
 #include "mapsync_host.h"
