@@ -32,6 +32,41 @@ def test_hip_library_exports_every_declared_symbol():
     assert sp.sensor_hrays == 1024 and sp.sensor_vrays == 128
 
 
+_CREATE_WITHOUT_DEVICE = r"""
+import ctypes as C, sys
+from vofod_amd import capi
+lib = capi.Library(sys.argv[1], "vofod_")
+runtime = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)  # (loaded with the library)
+n = C.c_int(0)
+if C.CDLL(runtime).hipGetDeviceCount(C.byref(n)) == 0 and n.value > 0:
+    print("device present")
+    sys.exit(0)
+sp, dp = capi.StaticParams(), capi.DynParams()
+lib.default_params(sp, dp)
+for _ in range(3):
+    h = C.c_void_p()
+    print("create", lib.create(sp, dp, C.byref(h)), h.value)
+"""
+
+
+def test_create_without_a_device_fails_cleanly():
+    """Where the HIP runtime reports no device, vofod_create tears its half-built handle down (every owner of device_mem.h empty)
+    and returns VOFOD_ERR_DEVICE - three times in a row, in a process of its own: a crash would be the child's, and is seen."""
+    import os
+    import sys
+
+    so = ROOT / "vofod_amd" / "csrc" / "libvofod_hip.so"
+    if not so.exists():
+        subprocess.run(["make", "-C", str(so.parent)], check=True, capture_output=True)
+    env = dict(os.environ, PYTHONPATH=str(ROOT))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", _CREATE_WITHOUT_DEVICE, str(so)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    if "device present" in r.stdout:
+        pytest.skip("a device is present: vofod_create succeeds here")
+    assert r.stdout.split("\n")[:3] == [f"create {capi.ERR_DEVICE} None"] * 3, (r.stdout, r.stderr)
+
+
 def test_oracle_exports_the_same_surface(oracle):
     sp, dp = capi.StaticParams(), capi.DynParams()
     oracle.default_params(sp, dp)

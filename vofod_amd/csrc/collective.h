@@ -80,10 +80,11 @@ struct vofod_comm
 {
   vcoll::Comm comm = nullptr;
   int rank = 0, n_ranks = 1, device = 0;
-  hipStream_t stream = nullptr;
-  char *d_send = nullptr, *d_recv = nullptr, *h_stage = nullptr;  // h_stage: pinned, send slot followed by the receive area
-  size_t cap_bytes = 0;  // per-rank payload the buffers are sized for
-  uint64_t *d_ctl = nullptr, *h_ctl = nullptr;  // vofod_broadcast_map's control words (device / pinned), allocated with the communicator
+  DevStream stream;
+  DevBuf<char> d_send, d_recv;  // (d_send.n: the per-rank payload the three buffers are sized for)
+  PinBuf<char> h_stage;         // send slot followed by the receive area
+  DevBuf<uint64_t> d_ctl;       // vofod_broadcast_map's control words (device / pinned), allocated with the communicator
+  PinBuf<uint64_t> h_ctl;
   std::mutex mtx;
   std::string err;
 };
@@ -130,16 +131,10 @@ int vofod_comm_create(const uint8_t id[VOFOD_COMM_ID_BYTES], int32_t rank, int32
   const bool comm_ok = vcoll::api().CommInitRank(&c->comm, n_ranks, u, rank) == 0;
   if (!comm_ok)
     c->comm = nullptr;
-  bool stream_ok = comm_ok && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-  if (!stream_ok)
-    c->stream = nullptr;
-  bool ctl_ok = stream_ok && hipMalloc(reinterpret_cast<void**>(&c->d_ctl), 4 * sizeof(uint64_t)) == hipSuccess;
-  if (!ctl_ok)
-    c->d_ctl = nullptr;
-  ctl_ok = ctl_ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_ctl), 4 * sizeof(uint64_t)) == hipSuccess;
+  const bool stream_ok = comm_ok && c->stream.create(hipStreamCreateWithFlags, hipStreamNonBlocking) == hipSuccess;
+  const bool ctl_ok = stream_ok && c->d_ctl.alloc(4) == hipSuccess && c->h_ctl.alloc(4) == hipSuccess;
   if (!ctl_ok)
   {
-    c->h_ctl = nullptr;
     {
       std::scoped_lock lck(vcoll::load_mutex());
       vcoll::api().err = !comm_ok ? "ncclCommInitRank failed" : !stream_ok ? "hipStreamCreate failed" : "control word allocation failed";
@@ -157,19 +152,7 @@ void vofod_comm_destroy(vofod_comm* c)
     return;
   (void)hipSetDevice(c->device);
   if (c->comm)
-    (void)vcoll::api().CommDestroy(c->comm);
-  if (c->d_send)
-    (void)hipFree(c->d_send);
-  if (c->d_recv)
-    (void)hipFree(c->d_recv);
-  if (c->h_stage)
-    (void)hipHostFree(c->h_stage);
-  if (c->d_ctl)
-    (void)hipFree(c->d_ctl);
-  if (c->h_ctl)
-    (void)hipHostFree(c->h_ctl);
-  if (c->stream)
-    (void)hipStreamDestroy(c->stream);
+    (void)vcoll::api().CommDestroy(c->comm);  // (ahead of its stream, which goes with the members)
   delete c;
 }
 
@@ -247,20 +230,12 @@ int vofod_allgather_detections(vofod_comm* c, const vofod_detection* local, cons
       return VOFOD_ERR_DEVICE;                                    \
     }                                                             \
   } while (0)
-  if (bytes > c->cap_bytes)
+  if (bytes > c->d_send.n)  // (allocated last: its capacity stands for all three)
   {
-    if (c->d_send)
-      (void)hipFree(c->d_send);
-    if (c->d_recv)
-      (void)hipFree(c->d_recv);
-    if (c->h_stage)
-      (void)hipHostFree(c->h_stage);
-    c->d_send = c->d_recv = c->h_stage = nullptr;
-    c->cap_bytes = 0;
-    COLLCHK(hipMalloc(reinterpret_cast<void**>(&c->d_send), bytes));
-    COLLCHK(hipMalloc(reinterpret_cast<void**>(&c->d_recv), bytes * c->n_ranks));
-    COLLCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), bytes * (c->n_ranks + 1)));
-    c->cap_bytes = bytes;
+    c->d_send.reset();
+    COLLCHK(c->d_recv.alloc(bytes * c->n_ranks));
+    COLLCHK(c->h_stage.alloc(bytes * (c->n_ranks + 1)));
+    COLLCHK(c->d_send.alloc(bytes));
   }
   // pack: the frame's detections (in order) at the head of its slot, the count behind them
   VCHK(vofod_pack_detection_slots(local, n_per_frame, frames_per_rank, d_max, c->h_stage));

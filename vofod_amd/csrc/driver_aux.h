@@ -22,46 +22,44 @@ int gscan(vofod_handle* h, const uint32_t* d_in, uint32_t n, uint32_t* d_out, ui
   return VOFOD_OK;
 }
 
-template <class T>
-int regrow(vofod_handle* h, T*& p, size_t n)
-{
-  if (p)
-    (void)hipFree(p);
-  p = nullptr;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)));
-  return VOFOD_OK;
-}
-
 int sep_ensure_words(vofod_handle* h, size_t n_words)
 {
   vr::SepState& s = h->sep;
-  if (!s.d_small)
+  auto& o = h->sep_own;
+  if (!o.d_offsets)  // (the last of the three: it stands for all of them)
   {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_small), 16 * sizeof(uint32_t)));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s.h_small), 16 * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_offsets), 3 * (2 * MAX_R + 1) * (2 * MAX_R + 1) * (2 * MAX_R + 1) * sizeof(int)));
+    HIPCHK(alloc_view(o.d_small, s.d_small, 16));
+    HIPCHK(o.h_small.alloc(16));
+    s.h_small = o.h_small;
+    HIPCHK(alloc_view(o.d_offsets, s.d_offsets, 3 * (2 * MAX_R + 1) * (2 * MAX_R + 1) * (2 * MAX_R + 1)));
   }
-  if (n_words <= s.words_cap)
+  if (n_words + 2 <= o.d_tprefix.n)  // (the last of the three again)
     return VOFOD_OK;
-  int r;
-  if ((r = regrow(h, s.d_tbits, n_words + 2)) || (r = regrow(h, s.d_tpop, n_words + 2)) || (r = regrow(h, s.d_tprefix, n_words + 2)))
-    return r;
-  s.words_cap = n_words;
+  o.d_tprefix.reset();
+  HIPCHK(alloc_view(o.d_tbits, s.d_tbits, n_words + 2));
+  HIPCHK(alloc_view(o.d_tpop, s.d_tpop, n_words + 2));
+  HIPCHK(alloc_view(o.d_tprefix, s.d_tprefix, n_words + 2));
   return VOFOD_OK;
 }
 
 int sep_ensure_pts(vofod_handle* h, size_t n)
 {
   vr::SepState& s = h->sep;
-  if (n <= s.pts_cap)
+  auto& o = h->sep_own;
+  if (o.d_bsum && n <= o.d_nsure.n)  // (d_bsum is the last of the ten: while it is there, all of them are)
     return VOFOD_OK;
   const size_t cap = n + n / 4 + 1024;
-  int r;
-  if ((r = regrow(h, s.d_px, cap)) || (r = regrow(h, s.d_py, cap)) || (r = regrow(h, s.d_pz, cap)) || (r = regrow(h, s.d_pi, cap)) || (r = regrow(h, s.d_sure, cap)) ||
-      (r = regrow(h, s.d_sure_pre, cap + 1)) || (r = regrow(h, s.d_vcnt, cap)) || (r = regrow(h, s.d_first, cap + 1)) || (r = regrow(h, s.d_nsure, cap)) ||
-      (r = regrow(h, s.d_bsum, cap / vr::GS_EPB + 1024)))
-    return r;
-  s.pts_cap = cap;
+  o.d_bsum.reset();
+  HIPCHK(alloc_view(o.d_px, s.d_px, cap));
+  HIPCHK(alloc_view(o.d_py, s.d_py, cap));
+  HIPCHK(alloc_view(o.d_pz, s.d_pz, cap));
+  HIPCHK(alloc_view(o.d_pi, s.d_pi, cap));
+  HIPCHK(alloc_view(o.d_sure, s.d_sure, cap));
+  HIPCHK(alloc_view(o.d_sure_pre, s.d_sure_pre, cap + 1));
+  HIPCHK(alloc_view(o.d_vcnt, s.d_vcnt, cap));
+  HIPCHK(alloc_view(o.d_first, s.d_first, cap + 1));
+  HIPCHK(alloc_view(o.d_nsure, s.d_nsure, cap));
+  HIPCHK(alloc_view(o.d_bsum, s.d_bsum, cap / vr::GS_EPB + 1024));
   return VOFOD_OK;
 }
 
@@ -659,54 +657,6 @@ void vofod_destroy(vofod_handle* h)
   (void)hipSetDevice(h->device);
   if (h->stream)
     (void)hipStreamSynchronize(h->stream);
-  h->ws.release();
-  for (auto& w : h->wsx)
-    w.release();
-  h->aux.release();
-  h->sepws.release();
-  h->msync.release();
-  void* ptrs[] = {h->d_map, h->d_flags, h->d_ray, h->d_mapbits, h->d_mapclose, h->d_prof_slab, h->d_prof_ccl, h->d_counter, h->d_lut_dirs, h->d_lut_offs, h->d_mask, h->d_rows, h->d_crows, h->d_boxstage, h->d_idxstage,
-                  h->sep.d_tbits, h->sep.d_tpop, h->sep.d_tprefix, h->sep.d_bsum, h->sep.d_px, h->sep.d_py, h->sep.d_pz, h->sep.d_pi, h->sep.d_sure, h->sep.d_sure_pre,
-                  h->sep.d_vcnt, h->sep.d_first, h->sep.d_nsure, h->sep.d_offsets, h->sep.d_small};
-  for (void* p : ptrs)
-    if (p)
-      (void)hipFree(p);
-  std::vector<ExploreBufs*> explore_all{&h->explore};
-  for (ExploreBufs& e : h->explore_slot)
-    explore_all.push_back(&e);
-  for (ExploreBufs* e : explore_all)
-    for (void* p : {static_cast<void*>(e->d_overlay), static_cast<void*>(e->d_stack), static_cast<void*>(e->d_explored), static_cast<void*>(e->d_touched), static_cast<void*>(e->d_ovl_list),
-                    static_cast<void*>(e->d_ovl_count), static_cast<void*>(e->d_job_begin), static_cast<void*>(e->d_visited), static_cast<void*>(e->d_jobs), static_cast<void*>(e->d_results),
-                    static_cast<void*>(e->d_members)})
-      if (p)
-        (void)hipFree(p);
-  for (auto& c : h->ctab)
-    for (void* p : {static_cast<void*>(c.d_rows), static_cast<void*>(c.d_boffs), static_cast<void*>(c.d_sure), static_cast<void*>(c.d_amb), static_cast<void*>(c.d_pair), static_cast<void*>(c.d_lbtab)})
-      if (p)
-        (void)hipFree(p);
-  if (h->h_counter)
-    (void)hipHostFree(h->h_counter);
-  if (h->d_bgcount)
-    (void)hipFree(h->d_bgcount);
-  if (h->h_bgcount)
-    (void)hipHostFree(h->h_bgcount);
-  if (h->sep.h_small)
-    (void)hipHostFree(h->sep.h_small);
-  for (hipEvent_t e : {h->ev_stagger, h->ev_explore, h->ev_bgcount})
-    if (e)
-      (void)hipEventDestroy(e);
-  if (h->stream)
-    (void)hipStreamDestroy(h->stream);
-  if (h->stream_tail)
-    (void)hipStreamDestroy(h->stream_tail);
-  if (h->stream_key)
-    (void)hipStreamDestroy(h->stream_key);
-  for (hipStream_t st : h->stream_frames)
-    if (st)
-      (void)hipStreamDestroy(st);
-  for (int t = 1; t < vofod_handle::MAX_INFLIGHT; t++)
-    if (h->chain_stream[t])
-      (void)hipStreamDestroy(h->chain_stream[t]);
   delete h;
 }
 
@@ -738,7 +688,8 @@ int vofod_create(const vofod_static_params* sp, const vofod_dyn_params* dp, vofo
     }                                                                           \
   } while (0)
   CREATE_CHK(hipSetDevice(h->device));
-  CREATE_CHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  CREATE_CHK(h->chain_stream[0].create(hipStreamCreateWithFlags, hipStreamNonBlocking));
+  h->stream = h->chain_stream[0];
   {
     // the tail's one small kernel (k_explore) has the host waiting for it: highest priority, so that it is dispatched at the
     // next kernel boundary of the batches in flight instead of behind their queued kernels
@@ -747,22 +698,21 @@ int vofod_create(const vofod_static_params* sp, const vofod_dyn_params* dp, vofo
     int prio_tail = prio_hi;
     if (const char* e = std::getenv("VOFOD_TAIL_PRIO"))  // (diagnostics) hi | mid | lo
       prio_tail = e[0] == 'l' ? prio_lo : e[0] == 'm' ? (prio_lo + prio_hi) / 2 : prio_hi;
-    CREATE_CHK(hipStreamCreateWithPriority(&h->stream_tail, hipStreamNonBlocking, prio_tail));
+    CREATE_CHK(h->stream_tail.create(hipStreamCreateWithPriority, hipStreamNonBlocking, prio_tail));
     // staged pipeline of submitted batches (launch_frames): streaming kernels below the frame kernels
-    CREATE_CHK(hipStreamCreateWithPriority(&h->stream_key, hipStreamNonBlocking, prio_lo));
+    CREATE_CHK(h->stream_key.create(hipStreamCreateWithPriority, hipStreamNonBlocking, prio_lo));
     // (VOFOD_FRAME_STREAMS: diagnostics - the number of frame streams, 1..8)
     h->n_frame_streams = 2;  // (more streams cost more than they bring: 811 k / 763 k / 656 k frames/s with 2 / 4 / 8 of them, 32-frame batches 435 k / 268 k / 216 k)
     if (const char* e = std::getenv("VOFOD_FRAME_STREAMS"))
       h->n_frame_streams = std::min(std::max(std::atoi(e), 1), static_cast<int>(vofod_handle::MAX_FRAME_STREAMS));
     for (int i = 0; i < h->n_frame_streams; i++)
-      CREATE_CHK(hipStreamCreateWithPriority(&h->stream_frames[i], hipStreamNonBlocking, (prio_lo + prio_hi) / 2));
+      CREATE_CHK(h->stream_frames[i].create(hipStreamCreateWithPriority, hipStreamNonBlocking, (prio_lo + prio_hi) / 2));
     h->stream_frame = h->stream_frames[0];
   }
-  h->chain_stream[0] = h->stream;
   // (tickets 1-3 have their streams from the start; tickets 4-7 - only small batches gain from more than four in flight - get
   // theirs when they are first taken: streams that merely exist are not free)
   for (int t = 1; t < 4; t++)
-    CREATE_CHK(hipStreamCreateWithFlags(&h->chain_stream[t], hipStreamNonBlocking));
+    CREATE_CHK(h->chain_stream[t].create(hipStreamCreateWithFlags, hipStreamNonBlocking));
   for (int a = 0; a < 3; a++)
   {
     h->exclude_center[a] = sp->exclude_offset[a];
@@ -789,18 +739,18 @@ int vofod_create(const vofod_static_params* sp, const vofod_dyn_params* dp, vofo
   h->mg.sz = sizes[2];
   h->mg.n = static_cast<uint64_t>(sizes[0]) * sizes[1] * sizes[2];
   const size_t M = h->mg.n;
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_map), M * sizeof(float)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_flags), M * sizeof(float)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_ray), M * sizeof(float)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_mapbits), ((M + 63) / 64 + 2) * sizeof(unsigned long long)));
+  CREATE_CHK(h->d_map.alloc(M));
+  CREATE_CHK(h->d_flags.alloc(M));
+  CREATE_CHK(h->d_ray.alloc(M));
+  CREATE_CHK(h->d_mapbits.alloc((M + 63) / 64 + 2));
   CREATE_CHK(hipMemset(h->d_mapbits, 0, ((M + 63) / 64 + 2) * sizeof(unsigned long long)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_mapclose), ((M + 63) / 64 + 2) * sizeof(unsigned long long)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_counter), 8 * sizeof(unsigned long long)));
-  CREATE_CHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_counter), 8 * sizeof(unsigned long long)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_bgcount), 8 * MB_SLOTS * sizeof(unsigned long long)));
-  CREATE_CHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_bgcount), 8 * MB_SLOTS * sizeof(unsigned long long)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_rows), MAX_STENCIL_ROWS * sizeof(StencilRow)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_crows), MAX_STENCIL_ROWS * sizeof(CloseRow)));
+  CREATE_CHK(h->d_mapclose.alloc((M + 63) / 64 + 2));
+  CREATE_CHK(h->d_counter.alloc(8));
+  CREATE_CHK(h->h_counter.alloc(8));
+  CREATE_CHK(h->d_bgcount.alloc(8 * MB_SLOTS));
+  CREATE_CHK(h->h_bgcount.alloc(8 * MB_SLOTS));
+  CREATE_CHK(h->d_rows.alloc(MAX_STENCIL_ROWS));
+  CREATE_CHK(h->d_crows.alloc(MAX_STENCIL_ROWS));
   // sensor
   const size_t n = static_cast<size_t>(sp->sensor_hrays) * sp->sensor_vrays;
   std::vector<float> dirs(3 * n), offs(3 * n, 0.0f);
@@ -813,9 +763,9 @@ int vofod_create(const vofod_static_params* sp, const vofod_dyn_params* dp, vofo
   std::vector<uint8_t> mask(n, 1);
   if (sp->mask)
     std::copy(sp->mask, sp->mask + n, mask.begin());
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_lut_dirs), 3 * n * sizeof(float)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_lut_offs), 3 * n * sizeof(float)));
-  CREATE_CHK(hipMalloc(reinterpret_cast<void**>(&h->d_mask), n));
+  CREATE_CHK(h->d_lut_dirs.alloc(3 * n));
+  CREATE_CHK(h->d_lut_offs.alloc(3 * n));
+  CREATE_CHK(h->d_mask.alloc(n));
   CREATE_CHK(hipMemcpy(h->d_lut_dirs, dirs.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice));
   CREATE_CHK(hipMemcpy(h->d_lut_offs, offs.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice));
   CREATE_CHK(hipMemcpy(h->d_mask, mask.data(), n, hipMemcpyHostToDevice));
@@ -922,12 +872,11 @@ int vofod_load_apriori(vofod_handle* h, const float* xyz, size_t n)
   VCHK(busy_check(h, true, true));
   if (n)
   {
-    float* d = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&d), n * 3 * sizeof(float)));
+    DevBuf<float> d;
+    HIPCHK(d.alloc(n * 3));
     HIPCHK(hipMemcpy(d, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice));
     KLAUNCH(h, k_apriori, dim3((n + 255) / 256), dim3(256), h->d_map, h->mg, d, static_cast<uint32_t>(n));
     HIPCHK(hipStreamSynchronize(h->stream));
-    (void)hipFree(d);
   }
   h->sure_background_sufficient = true;  // vofod_nodelet.cpp:343-344
   h->background_pts_sufficient = true;
@@ -986,7 +935,7 @@ int vofod_voxels_as_pc(vofod_handle* h, int which, float threshold, int greater_
   if (P == 0)
     return VOFOD_OK;
   VCHK(ensure_boxstage(h, static_cast<size_t>(P) * 4));
-  KLAUNCH(h, vr::k_col_emit_xyzi, dim3((ncol + 255) / 256), dim3(256), h->mg, m, threshold, greater_than, s.d_tprefix, P, reinterpret_cast<float4*>(h->d_boxstage));
+  KLAUNCH(h, vr::k_col_emit_xyzi, dim3((ncol + 255) / 256), dim3(256), h->mg, m, threshold, greater_than, s.d_tprefix, P, reinterpret_cast<float4*>(h->d_boxstage.p));
   HIPCHK(hipMemcpyAsync(out, h->d_boxstage, sizeof(vofod_point_xyzi) * P, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return VOFOD_OK;
@@ -1127,8 +1076,7 @@ int vofod_reserve(vofod_handle* h, int tickets)
     Workspace* w = h->slot(t);
     if (w->F == 0)
       VCHK(grow_workspace(h, *w, "extra workspace: ", h->ws.F, h->ws.pt_cap, h->ws.vox_cap, h->ws.words_cap, h->ws.bricks_cap));
-    if (t > 0 && !h->chain_stream[t])
-      HIPCHK(hipStreamCreateWithFlags(&h->chain_stream[t], hipStreamNonBlocking));
+    VCHK(ensure_chain_stream(h, t));
   }
   // the device tail's flood-fill buffers: shared by the batches of 128 frames and more (their tails take turns on the tail
   // stream), per ticket for smaller batches (launch_device_tail sizes those by the batch; reserved here for full workspaces)

@@ -23,15 +23,9 @@ struct FrameCall
   bool rc_done = false;     // ++its and the raycast role of VOFOD_SCAN_AUTO_RAYCAST have run ahead of the device tail
   bool far_single = false;  // a single map-updating scan clustered close first on the general path (kernels_far.h)
   hipStream_t tail_stream_used = nullptr;  // where the device tail's last operation was enqueued
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // debug output: stage boundaries on the chain's stream
+  DevEvent ev[5];  // debug output: stage boundaries on the chain's stream
   clk::time_point t0 = clk::now();
   double tr_launch = 0, tr_sync1 = 0;  // VOFOD_TRACE
-  ~FrameCall()  // (the events are destroyed on every return path)
-  {
-    for (auto& x : ev)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
 };
 
 // How a launch is routed.  What differs between a submitted and a synchronous launch is decided here, once.
@@ -59,6 +53,14 @@ struct StreamScope
   }
   ~StreamScope() { h->stream = saved; }
 };
+
+// the chain streams of tickets 4-7 are created when the ticket is first taken (vofod_create has made those of tickets 0-3)
+int ensure_chain_stream(vofod_handle* h, int t)
+{
+  if (!h->chain_stream[t])
+    HIPCHK(h->chain_stream[t].create(hipStreamCreateWithFlags, hipStreamNonBlocking));
+  return VOFOD_OK;
+}
 
 // which in-flight slot is `ws` (-1: not a ticket's workspace)
 int slot_index(vofod_handle* h, const Workspace& ws)
@@ -137,8 +139,7 @@ int route_submitted(vofod_handle* h, const Workspace& ws, uint32_t n, LaunchRout
     const int t = slot_index(h, ws);
     if (t >= 1)
     {
-      if (!h->chain_stream[t])
-        HIPCHK(hipStreamCreateWithFlags(&h->chain_stream[t], hipStreamNonBlocking));
+      VCHK(ensure_chain_stream(h, t));
       rt.chain = h->chain_stream[t];
     }
     // A small submitted batch (fewer frames than half the CUs: its whole chain runs on the ticket's stream) keeps flood-fill
@@ -294,7 +295,7 @@ int cluster_far_single(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const Gr
 // ---- K8/K9 findCloseFarClusters :703-750 (tables and images were prepared before the chain was enqueued) and
 // ---- K10 updateVMaps :943-950 + cluster table + candidate members: whatever the clustering has not done already
 int closefar_and_finalize(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, const GridParams& g, uint32_t n, const CloseParams& cpar, const UpdateParams& up, bool use_dilated, bool keep_dirty,
-                          vofod_scan_debug* dbg, hipEvent_t* ev)
+                          vofod_scan_debug* dbg, const DevEvent* ev)
 {
   const uint32_t gv = (ws.vox_cap + 255u) / 256u;
   if (!lf.closefar_fused)
@@ -345,7 +346,7 @@ int launch_device_tail(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, co
   // the background latch (:716-721) is needed now, not at collect time
   VCHK(latch_background(h));
   ExploreBufs& eb = rt.own_tail >= 0 ? h->explore_slot[rt.own_tail] : h->explore;
-  const uint32_t ebF = rt.own_tail >= 0 ? std::max<uint32_t>(eb.F, (n + 31u) & ~31u) : h->ws.F;
+  const uint32_t ebF = rt.own_tail >= 0 ? std::max<uint32_t>(eb.F(), (n + 31u) & ~31u) : h->ws.F;
   VCHK(ensure_explore(h, eb, ebF, static_cast<size_t>(ebF) * vtd::TP_MAXC, static_cast<size_t>(ebF) * vtd::TP_MAXM));
   // A submitted batch runs its tail on the handle's tail stream: one wave per frame does the flood
   // fills (latency bound, ~0.1 ms), which overlaps with the streaming kernels of the next batch instead of delaying them.
@@ -353,7 +354,7 @@ int launch_device_tail(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, co
   hipStream_t chain_stream = h->stream;
   StreamScope tail_scope(h);
   if (!h->ev_explore)
-    HIPCHK(hipEventCreateWithFlags(&h->ev_explore, hipEventDisableTiming));
+    HIPCHK(h->ev_explore.create(hipEventCreateWithFlags, hipEventDisableTiming));
   // (large batches: the tails take turns on the tail stream, underneath the frame kernel of the next batch)
   if (rt.own_tail >= 0)
     ;  // (own buffers, own stream: nothing to wait for)
@@ -441,10 +442,10 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   // error return must not leave it standing for a different batch), and only a launch of the very same job reuses its inputs
   const bool rerun = ws.rerun && ws.job_n == n;
   ws.rerun = false;
-  hipEvent_t* ev = call.ev;
+  DevEvent* ev = call.ev;
   if (dbg)
     for (int i = 0; i < 5; i++)
-      HIPCHK(hipEventCreate(&ev[i]));
+      HIPCHK(ev[i].create(hipEventCreate));
   const float thr_new = static_cast<float>(dp.voxel_map__thresholds__new_obstacles);
 
   // ---- the routing decisions that do not depend on the frames

@@ -244,31 +244,20 @@ __global__ __launch_bounds__(256) void k_ms_scatter(const uint32_t* __restrict__
 
 }  // namespace vms
 
-// Per-handle state of the snapshots (owned by vofod_handle, released by vofod_destroy).  The shadow of a map costs 4 * M bytes
+// Per-handle state of the snapshots (owned by vofod_handle).  The shadow of a map costs 4 * M bytes
 // (78 MB at 0.25 m, 1.2 GB at 0.1 m for configs[4]); it is allocated on the first export of that map.
 struct MapSyncState
 {
-  uint32_t* d_shadow[3] = {nullptr, nullptr, nullptr};
-  uint32_t* d_tiles = nullptr;   // [3][ntiles] difference counts
-  uint32_t* d_prefix = nullptr;  // [3][ntiles + 1] their exclusive scan
-  uint32_t* d_bsum = nullptr;    // gscan's block sums
-  uint32_t* d_small = nullptr;   // [0..2] totals per map, [3] the check flag
-  uint32_t* h_small = nullptr;   // pinned copy
-  uint8_t* d_wire = nullptr;     // staging of host-side snapshots and of vofod_broadcast_map (its control words live in vofod_comm)
-  size_t wire_cap = 0;
+  DevBuf<uint32_t> d_shadow[3];
+  DevBuf<uint32_t> d_tiles;   // [3][ntiles] difference counts
+  DevBuf<uint32_t> d_prefix;  // [3][ntiles + 1] their exclusive scan
+  DevBuf<uint32_t> d_bsum;    // gscan's block sums
+  DevBuf<uint32_t> d_small;   // [0..2] totals per map, [3] the check flag
+  PinBuf<uint32_t> h_small;   // its host copy
+  DevBuf<uint8_t> d_wire;     // staging of host-side snapshots and of vofod_broadcast_map (its control words live in vofod_comm)
   uint32_t ntiles = 0;
   uint64_t chain_gen = 0;        // export side: generation last exported (0 = no chain) ...
   int32_t chain_mask = 0;        // ... and its maps mask
   uint64_t applied_gen = 0;      // apply side: generation last applied (0 = none) ...
   int32_t applied_mask = 0;      // ... and its maps mask
-  void release()
-  {
-    for (void* p : {static_cast<void*>(d_shadow[0]), static_cast<void*>(d_shadow[1]), static_cast<void*>(d_shadow[2]), static_cast<void*>(d_tiles),
-                    static_cast<void*>(d_prefix), static_cast<void*>(d_bsum), static_cast<void*>(d_small), static_cast<void*>(d_wire)})
-      if (p)
-        (void)hipFree(p);
-    if (h_small)
-      (void)hipHostFree(h_small);
-    *this = MapSyncState{};
-  }
 };

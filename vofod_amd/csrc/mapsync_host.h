@@ -35,30 +35,23 @@ uint64_t ms_fresh_gen()
 int ms_ensure(vofod_handle* h)
 {
   MapSyncState& s = h->msync;
-  if (s.d_tiles)
+  if (s.h_small)  // (allocated last: it stands for all five)
     return VOFOD_OK;
   const uint64_t nt = (h->mg.n + vms::MS_TILE - 1) / vms::MS_TILE;
   s.ntiles = static_cast<uint32_t>(nt);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_tiles), 3 * (nt + 1) * sizeof(uint32_t)));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_prefix), 3 * (nt + 1) * sizeof(uint32_t)));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_bsum), (nt / vr::GS_EPB + 2) * sizeof(uint32_t)));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_small), 16 * sizeof(uint32_t)));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s.h_small), 16 * sizeof(uint32_t)));
+  HIPCHK(s.d_tiles.alloc(3 * (nt + 1)));
+  HIPCHK(s.d_prefix.alloc(3 * (nt + 1)));
+  HIPCHK(s.d_bsum.alloc(nt / vr::GS_EPB + 2));
+  HIPCHK(s.d_small.alloc(16));
+  HIPCHK(s.h_small.alloc(16));
   return VOFOD_OK;
 }
 
 int ms_ensure_wire(vofod_handle* h, size_t bytes)
 {
   MapSyncState& s = h->msync;
-  if (bytes <= s.wire_cap)
-    return VOFOD_OK;
-  const size_t cap = std::max(bytes + bytes / 4 + 4096, 2 * s.wire_cap);  // (geometric: a stream of growing deltas reallocates rarely)
-  if (s.d_wire)
-    (void)hipFree(s.d_wire);
-  s.d_wire = nullptr;
-  s.wire_cap = 0;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_wire), cap));
-  s.wire_cap = cap;
+  if (bytes > s.d_wire.n)
+    HIPCHK(s.d_wire.alloc(std::max(bytes + bytes / 4 + 4096, 2 * s.d_wire.n)));  // (geometric: a stream of growing deltas reallocates rarely)
   return VOFOD_OK;
 }
 
@@ -132,7 +125,7 @@ int ms_export_locked(vofod_handle* h, int maps, int kind, uint8_t* d_dst, size_t
   if (full)  // the shadows are allocated on the first export of their map (4 * M bytes each)
     for (int m = 0; m < 3; m++)
       if ((maps >> m & 1) && !s.d_shadow[m])
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_shadow[m]), h->mg.n * sizeof(uint32_t)));
+        HIPCHK(s.d_shadow[m].alloc(h->mg.n));
   vms::WireHeader hd{};
   hd.magic = vms::MS_MAGIC;
   hd.version = vms::MS_VERSION;
@@ -240,7 +233,7 @@ int ms_apply_locked(vofod_handle* h, const vms::WireHeader& hd, const uint8_t* d
       }
       else
       {
-        VCHK(ms_count_map(h, VOFOD_MAP_RAYCAST, true, reinterpret_cast<const uint32_t*>(h->d_ray), 4));
+        VCHK(ms_count_map(h, VOFOD_MAP_RAYCAST, true, reinterpret_cast<const uint32_t*>(h->d_ray.p), 4));
         HIPCHK(hipMemcpyAsync(h->d_counter + 1, s.d_small + 4, sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
       }
     }

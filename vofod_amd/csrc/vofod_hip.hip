@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "device_mem.h"
 #include "host_tail.h"
 #include "thread_pool.h"
 #include "kernels_brick.h"
@@ -210,6 +211,14 @@ struct SlowCall
     }                                                                                                        \
   } while (0)
 
+// (where there is no handle to report to: the caller returns the error code itself)
+#define HIP_TRY(expr)                                      \
+  do                                                       \
+  {                                                        \
+    if (const hipError_t e_ = (expr); e_ != hipSuccess)    \
+      return e_;                                           \
+  } while (0)
+
 // (the same for the driver's own functions: a status other than VOFOD_OK ends the caller with it)
 #define VCHK(expr)                             \
   do                                           \
@@ -229,6 +238,7 @@ struct Prof
   };
   std::vector<Rec> recs;
   std::vector<hipEvent_t> pool;
+  std::vector<DevEvent> owned;  // every event of recs and pool: they live as long as the handle
   hipEvent_t get()
   {
     if (!pool.empty())
@@ -237,9 +247,9 @@ struct Prof
       pool.pop_back();
       return e;
     }
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
-    return e;
+    owned.emplace_back();
+    (void)owned.back().create(hipEventCreate);
+    return owned.back();
   }
 };
 
@@ -288,61 +298,69 @@ struct LaunchFlags
   bool closefar_fused = false;  // the clustering answered hasCloseTo as well (dilated image inside k_flatten / the frame kernel)
 };
 
+// A plain struct of pointers (what the kernels take by value; vr::SepState) cannot hold an owner: the owner stands beside it, and
+// the struct's member `v` is the view of the owner's allocation.
+template <class T>
+hipError_t alloc_view(DevBuf<T>& own, T*& v, size_t n)
+{
+  const hipError_t e = own.alloc(n);
+  v = own;
+  return e;
+}
+
 struct Workspace
 {
   uint32_t F = 0, pt_cap = 0, vox_cap = 0, words_cap = 0, nblk_cap = 0, bricks_cap = 0;
+  // BrickArrays, VoxelArrays, SlabArrays and FrameScratch go to the kernels by value: they hold plain pointers, and the storage
+  // behind every member has its owner here (sa.keys shares d_ptrank's)
   BrickArrays ba{};
-  unsigned long long* d_bconn = nullptr;  // per brick: connectivity mask over the forward stencil (transitive reduction)
-  FrameArgs* d_args = nullptr;
-  FrameHdr* d_hdrs = nullptr;
-  unsigned long long* d_bitmaps = nullptr;
-  uint32_t* d_wprefix = nullptr;
-  uint32_t* d_blocksums = nullptr;
   VoxelArrays va{};
-  uint32_t* d_labels = nullptr;
-  ClusterRec* d_table = nullptr;
-  CandMember* d_cand = nullptr;
-  uint32_t* d_ptrank = nullptr;
-  SlabArrays sa{};  // key list / extras of the LDS-slab voxelisation (keys share d_ptrank's storage)
+  SlabArrays sa{};  // key list / extras of the LDS-slab voxelisation
   FrameScratch fs{};  // row tables of the brick-first frame kernel (kernels_frame.h)
-  float* d_stage = nullptr;  // F * pt_cap * 5 words: x, y, z, intensity, range of host-resident inputs
-  char* d_stage_aos = nullptr;  // host-resident array-of-structs clouds (the nodelet's 48-byte ouster_ros::Point) cross the link as they are:
-  size_t stage_aos_bytes = 0;   // F * aos_pitch bytes, allocated on first use; the kernels read x / y / z in place at the struct's stride
-  size_t aos_pitch = 0;
-  PackedFrame* d_packed = nullptr;
-  PackedFrame* h_packed = nullptr;  // pinned
-  PackedLite* d_lite = nullptr;
-  PackedLite* h_lite = nullptr;  // pinned
+  DevBuf<unsigned long long> ba_bricks, fs_rowT, fs_nodeA, fs_bbsave;
+  DevBuf<uint32_t> ba_bparent, ba_bmin, ba_bcmin, ba_blist, va_key, va_parent, va_csize, va_cclose, va_bb, sa_extras, sa_counts, fs_rowQ, fs_bmin;
+  DevBuf<float4> va_pts, fs_frag;
+  DevBuf<int32_t> va_cbox;
+  DevBuf<unsigned long long> d_bconn;  // per brick: connectivity mask over the forward stencil (transitive reduction)
+  DevBuf<FrameArgs> d_args;
+  DevBuf<FrameHdr> d_hdrs;
+  DevBuf<unsigned long long> d_bitmaps;
+  DevBuf<uint32_t> d_wprefix;
+  DevBuf<uint32_t> d_blocksums;
+  DevBuf<uint32_t> d_labels;
+  DevBuf<ClusterRec> d_table;
+  DevBuf<CandMember> d_cand;
+  DevBuf<uint32_t> d_ptrank;
+  DevBuf<float> d_stage;  // F * pt_cap * 5 words: x, y, z, intensity, range of host-resident inputs
+  DevBuf<char> d_stage_aos;  // host-resident array-of-structs clouds (the nodelet's 48-byte ouster_ros::Point) cross the link as they are:
+  size_t aos_pitch = 0;      // F * aos_pitch bytes, allocated on first use; the kernels read x / y / z in place at the struct's stride
+  DevBuf<PackedFrame> d_packed;
+  PinBuf<PackedFrame> h_packed;
+  DevBuf<PackedLite> d_lite;
+  PinBuf<PackedLite> h_lite;
   bool lite = false;  // the batch in this workspace was read back through the lite slots (no debug output asked for)
   bool mapbits_patched = false;  // k_finalize_far kept the map's occupancy image and counters up to date with this scan's update
   bool prof_deferred = false;  // VOFOD_LDS_PROF=2: the frame kernel's stamps of this batch are printed when it is collected
   uint32_t prof_slot0 = 0;
   int close_first = 0;  // k_frame_lds: 1 = cluster the far voxels only (read-only batches), 2 = the same with labels for the far-only debug view
   bool dtail = false;  // ... or its classification tail ran on the device (kernels_tail.h): only detection records come back
-  vtd::TailCluster* d_tailc = nullptr;
-  vtd::FrameDets* d_dets = nullptr;
-  vtd::FrameDets* h_dets = nullptr;  // pinned
-  vtd::FrameDets* h_dets_dev = nullptr;  // the same slots as the device sees them (k_tail_finish writes the records there)
-  uint32_t* d_job_be = nullptr;      // [2][F]: first and one-past-last explore job of every frame
+  DevBuf<vtd::TailCluster> d_tailc;
+  DevBuf<vtd::FrameDets> d_dets;
+  PinBuf<vtd::FrameDets> h_dets;  // mapped, coherent
+  vtd::FrameDets* h_dets_dev = nullptr;  // the same slots as the device sees them (k_tail_finish writes the records there): an alias, not an allocation
+  DevBuf<uint32_t> d_job_be;      // [2][F]: first and one-past-last explore job of every frame
   // per-frame launch arguments in pinned host memory: their upload is a true asynchronous copy, so a batch is enqueued while the
   // previous chain still runs (a copy from pageable memory makes the submitting thread wait for the stream)
   struct PinnedArgs
   {
-    FrameArgs* p = nullptr;
-    size_t n = 0;
-    FrameArgs& operator[](size_t i) { return p[i]; }
-    const FrameArgs& operator[](size_t i) const { return p[i]; }
-    FrameArgs* data() { return p; }
-    hipError_t assign(size_t n_, const FrameArgs& v)
+    PinBuf<FrameArgs> buf;
+    FrameArgs& operator[](size_t i) { return buf.p[i]; }
+    const FrameArgs& operator[](size_t i) const { return buf.p[i]; }
+    FrameArgs* data() { return buf; }
+    hipError_t assign(size_t n, const FrameArgs& v)
     {
-      if (p)
-        (void)hipHostFree(p);
-      p = nullptr;
-      n = n_;
-      if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(FrameArgs) * std::max<size_t>(n, 1)); e != hipSuccess)
-        return e;
-      for (size_t i = 0; i < n; i++)
-        p[i] = v;
+      HIP_TRY(buf.alloc(n));
+      std::fill_n(buf.p, n, v);
       return hipSuccess;
     }
   } h_args;
@@ -350,49 +368,20 @@ struct Workspace
   bool bitmap_clean = false;   // the occupancy bitmaps are all-zero (k_finalize clears the words it used)
   vofod_dyn_params job_dp{};   // the dynamic parameters the pending batch was submitted with
   bool rerun = false;          // the next launch repeats this workspace's batch (LDS overflow): frame arguments and staged columns are kept
-  void* d_members_big = nullptr;  // vox_cap gathered candidate members: read-back of a frame whose list exceeds the packed slot
+  DevBuf<CandMemberX> d_members_big;  // vox_cap gathered candidate members: read-back of a frame whose list exceeds the packed slot
   // state of a submitted, not yet collected batch (vofod_batch_submit / vofod_batch_collect)
   bool pending = false;
   uint32_t job_n = 0;
   GridParams job_g{};
   std::vector<float> job_tfs;
-  hipEvent_t ev_done = nullptr;
-  hipEvent_t ev_packed = nullptr;   // the read-back slots are complete on the chain's stream
-  hipEvent_t ev_key = nullptr;      // staged pipeline: the batch's streaming kernels (brick codes) are through
-  hipEvent_t ev_h2d = nullptr;      // the host-resident columns of a submitted batch have crossed the link (vofod_batch_submit returns behind it)
-  hipStream_t copy_stream = nullptr;  // device-to-host copy of the slots: the chain's stream goes on with the next batch meanwhile
+  DevEvent ev_done;
+  DevEvent ev_packed;   // the read-back slots are complete on the chain's stream
+  DevEvent ev_key;      // staged pipeline: the batch's streaming kernels (brick codes) are through
+  DevEvent ev_h2d;      // the host-resident columns of a submitted batch have crossed the link (vofod_batch_submit returns behind it)
+  DevStream copy_stream;  // device-to-host copy of the slots: the chain's stream goes on with the next batch meanwhile
 
-  void release()
-  {
-    if (d_stage_aos)
-      (void)hipFree(d_stage_aos);
-    d_stage_aos = nullptr;
-    stage_aos_bytes = 0;
-    void* ptrs[] = {d_bconn, ba.bricks, ba.bparent, ba.bmin, ba.bcmin, ba.blist, d_args, d_hdrs, d_bitmaps, d_wprefix, d_blocksums, va.pts, va.key, va.parent, va.csize, va.cbox, va.cclose, va.bb, d_labels, d_table, d_cand, d_ptrank, sa.extras, sa.counts, d_stage, d_packed, d_lite, d_tailc, d_dets, d_job_be, d_members_big, fs.rowT, fs.rowQ, fs.bmin, fs.nodeA, fs.bbsave, fs.frag};
-    for (void* p : ptrs)
-      if (p)
-        (void)hipFree(p);
-    if (h_packed)
-      (void)hipHostFree(h_packed);
-    if (h_lite)
-      (void)hipHostFree(h_lite);
-    if (h_args.p)
-      (void)hipHostFree(h_args.p);
-    if (h_dets)
-      (void)hipHostFree(h_dets);
-    if (ev_done)
-      (void)hipEventDestroy(ev_done);
-    if (ev_packed)
-      (void)hipEventDestroy(ev_packed);
-    if (ev_key)
-      (void)hipEventDestroy(ev_key);
-    if (ev_h2d)
-      (void)hipEventDestroy(ev_h2d);
-    if (copy_stream)
-      (void)hipStreamDestroy(copy_stream);
-    *this = Workspace();
-  }
-
+  // Grow to at least these capacities.  What was there is released first (two 6.4 GB workspaces must never coexist); a failure
+  // leaves an empty workspace.
   hipError_t ensure(uint32_t F_, uint32_t pt_cap_, uint32_t vox_cap_, uint32_t words_cap_, uint32_t bricks_cap_ = 0)
   {
     if (F_ <= F && pt_cap_ <= pt_cap && vox_cap_ <= vox_cap && words_cap_ <= words_cap && bricks_cap_ <= bricks_cap)
@@ -402,101 +391,97 @@ struct Workspace
     vox_cap_ = std::max(vox_cap_, vox_cap);
     words_cap_ = std::max(words_cap_, words_cap);
     bricks_cap_ = std::max(bricks_cap_, bricks_cap);
-    release();
+    *this = Workspace();
+    const hipError_t e = allocate(F_, pt_cap_, vox_cap_, words_cap_, bricks_cap_);
+    if (e != hipSuccess)
+      *this = Workspace();
+    return e;
+  }
+
+private:
+  // every allocation of an empty workspace; the capacities are set last
+  hipError_t allocate(const uint32_t F_, const uint32_t pt_cap_, const uint32_t vox_cap_, const uint32_t words_cap_, const uint32_t bricks_cap_)
+  {
+    const uint32_t nblk_cap_ = (words_cap_ + SCAN_WPB - 1) / SCAN_WPB + 1;
+    const size_t FV = static_cast<size_t>(F_) * vox_cap_;
+    const size_t FB = F_ * std::max<size_t>(bricks_cap_, 1);
+    const size_t FW = F_ * (static_cast<size_t>(words_cap_) + 2);
+    HIP_TRY(alloc_view(ba_bricks, ba.bricks, FB));
+    HIP_TRY(hipMemset(ba.bricks, 0, sizeof(unsigned long long) * FB));
+    HIP_TRY(d_bconn.alloc(FB));
+    HIP_TRY(alloc_view(ba_bparent, ba.bparent, FB));
+    HIP_TRY(alloc_view(ba_bmin, ba.bmin, FB));
+    HIP_TRY(alloc_view(ba_bcmin, ba.bcmin, FB));
+    HIP_TRY(hipMemset(ba.bmin, 0xff, sizeof(uint32_t) * FB));
+    HIP_TRY(hipMemset(ba.bcmin, 0xff, sizeof(uint32_t) * FB));
+    HIP_TRY(alloc_view(ba_blist, ba.blist, FV));
+    HIP_TRY(d_args.alloc(F_));
+    HIP_TRY(d_hdrs.alloc(F_));
+    HIP_TRY(d_bitmaps.alloc(FW));
+    HIP_TRY(d_wprefix.alloc(FW));
+    HIP_TRY(d_blocksums.alloc(static_cast<size_t>(F_) * nblk_cap_));
+    HIP_TRY(alloc_view(va_pts, va.pts, FV));
+    HIP_TRY(alloc_view(va_key, va.key, FV));
+    HIP_TRY(alloc_view(va_parent, va.parent, FV));
+    HIP_TRY(alloc_view(va_csize, va.csize, FV));
+    HIP_TRY(alloc_view(va_cbox, va.cbox, 6 * FV));
+    HIP_TRY(alloc_view(va_cclose, va.cclose, FV));
+    HIP_TRY(alloc_view(va_bb, va.bb, FV));
+    HIP_TRY(d_labels.alloc(FV));
+    HIP_TRY(d_table.alloc(FV));
+    HIP_TRY(d_cand.alloc(FV));
+    // (the frame kernel's code list: every wave of a frame's workgroup appends to a segment of its own - whole rounds of the input pass)
+    fs.keys_cap = (pt_cap_ + IN_SEG_ALIGN - 1u) / IN_SEG_ALIGN * IN_SEG_ALIGN;
+    HIP_TRY(d_ptrank.alloc(static_cast<size_t>(F_) * fs.keys_cap));
+    HIP_TRY(alloc_view(sa_extras, sa.extras, static_cast<size_t>(F_) * pt_cap_));
+    HIP_TRY(alloc_view(sa_counts, sa.counts, 2 * static_cast<size_t>(F_)));
+    sa.keys = d_ptrank;
+    HIP_TRY(d_stage.alloc(5 * static_cast<size_t>(F_) * pt_cap_));
+    HIP_TRY(d_packed.alloc(F_));
+    HIP_TRY(d_lite.alloc(F_));
+    HIP_TRY(d_tailc.alloc(vtd::TP_MAXC * static_cast<size_t>(F_)));
+    HIP_TRY(d_dets.alloc(F_));
+    HIP_TRY(d_job_be.alloc(2 * static_cast<size_t>(F_)));
+    HIP_TRY(d_members_big.alloc(vox_cap_));
+    HIP_TRY(alloc_view(fs_rowT, fs.rowT, 4 * FR_ROWS_MAX * static_cast<size_t>(F_)));
+    HIP_TRY(alloc_view(fs_rowQ, fs.rowQ, 4 * FR_ROWS_MAX * static_cast<size_t>(F_)));
+    HIP_TRY(alloc_view(fs_bmin, fs.bmin, LB_MAX * static_cast<size_t>(F_)));
+    HIP_TRY(alloc_view(fs_nodeA, fs.nodeA, 4 * LB_MAX * static_cast<size_t>(F_)));
+    HIP_TRY(alloc_view(fs_bbsave, fs.bbsave, FR_BB64 * static_cast<size_t>(F_)));
+    HIP_TRY(alloc_view(fs_frag, fs.frag, static_cast<size_t>(F_) * std::max<uint32_t>(pt_cap_, 1)));
+    HIP_TRY(h_packed.alloc(F_));
+    HIP_TRY(h_lite.alloc(F_));
+    HIP_TRY(h_dets.alloc(F_, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(h_dets, 0, sizeof(vtd::FrameDets) * F_);
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_dets_dev), h_dets, 0));
+    HIP_TRY(h_args.assign(F_, FrameArgs{}));
+    HIP_TRY(ev_done.create(hipEventCreateWithFlags, hipEventDisableTiming));
+    HIP_TRY(ev_packed.create(hipEventCreateWithFlags, hipEventDisableTiming));
+    HIP_TRY(ev_h2d.create(hipEventCreateWithFlags, hipEventDisableTiming));
+    HIP_TRY(ev_key.create(hipEventCreateWithFlags, hipEventDisableTiming));
+    HIP_TRY(copy_stream.create(hipStreamCreateWithFlags, hipStreamNonBlocking));
+    // the memsets above run on the null stream, the kernels on non-blocking streams: wait for the fills to land
+    HIP_TRY(hipDeviceSynchronize());
     F = F_;
     pt_cap = pt_cap_;
     vox_cap = vox_cap_;
     words_cap = words_cap_;
     bricks_cap = bricks_cap_;
-    nblk_cap = (words_cap + SCAN_WPB - 1) / SCAN_WPB + 1;
-    hipError_t e;
-    const size_t FV = static_cast<size_t>(F) * vox_cap;
-#define WS_ALLOC(ptr, bytes)                                     \
-  if ((e = hipMalloc(reinterpret_cast<void**>(&ptr), (bytes))) != hipSuccess) \
-    return e;
-    WS_ALLOC(ba.bricks, sizeof(unsigned long long) * F * std::max<size_t>(bricks_cap, 1));
-    if ((e = hipMemset(ba.bricks, 0, sizeof(unsigned long long) * F * std::max<size_t>(bricks_cap, 1))) != hipSuccess)
-      return e;
-    WS_ALLOC(d_bconn, sizeof(unsigned long long) * F * std::max<size_t>(bricks_cap, 1));
-    WS_ALLOC(ba.bparent, sizeof(uint32_t) * F * std::max<size_t>(bricks_cap, 1));
-    WS_ALLOC(ba.bmin, sizeof(uint32_t) * F * std::max<size_t>(bricks_cap, 1));
-    WS_ALLOC(ba.bcmin, sizeof(uint32_t) * F * std::max<size_t>(bricks_cap, 1));
-    if ((e = hipMemset(ba.bmin, 0xff, sizeof(uint32_t) * F * std::max<size_t>(bricks_cap, 1))) != hipSuccess)
-      return e;
-    if ((e = hipMemset(ba.bcmin, 0xff, sizeof(uint32_t) * F * std::max<size_t>(bricks_cap, 1))) != hipSuccess)
-      return e;
-    WS_ALLOC(ba.blist, sizeof(uint32_t) * FV);
-    WS_ALLOC(d_args, sizeof(FrameArgs) * F);
-    WS_ALLOC(d_hdrs, sizeof(FrameHdr) * F);
-    WS_ALLOC(d_bitmaps, sizeof(unsigned long long) * F * (static_cast<size_t>(words_cap) + 2));
-    WS_ALLOC(d_wprefix, sizeof(uint32_t) * F * (static_cast<size_t>(words_cap) + 2));
-    WS_ALLOC(d_blocksums, sizeof(uint32_t) * F * nblk_cap);
-    WS_ALLOC(va.pts, sizeof(float4) * FV);
-    WS_ALLOC(va.key, sizeof(uint32_t) * FV);
-    WS_ALLOC(va.parent, sizeof(uint32_t) * FV);
-    WS_ALLOC(va.csize, sizeof(uint32_t) * FV);
-    WS_ALLOC(va.cbox, sizeof(int32_t) * 6 * FV);
-    WS_ALLOC(va.cclose, sizeof(uint32_t) * FV);
-    WS_ALLOC(va.bb, sizeof(uint32_t) * FV);
-    WS_ALLOC(d_labels, sizeof(uint32_t) * FV);
-    WS_ALLOC(d_table, sizeof(ClusterRec) * FV);
-    WS_ALLOC(d_cand, sizeof(CandMember) * FV);
-    // (the frame kernel's code list: every wave of a frame's workgroup appends to a segment of its own - whole rounds of the input pass)
-    fs.keys_cap = (pt_cap + IN_SEG_ALIGN - 1u) / IN_SEG_ALIGN * IN_SEG_ALIGN;
-    WS_ALLOC(d_ptrank, sizeof(uint32_t) * static_cast<size_t>(F) * fs.keys_cap);
-    WS_ALLOC(sa.extras, sizeof(uint32_t) * static_cast<size_t>(F) * pt_cap);
-    WS_ALLOC(sa.counts, sizeof(uint32_t) * 2 * F);
-    sa.keys = d_ptrank;
-    WS_ALLOC(d_stage, sizeof(float) * 5 * static_cast<size_t>(F) * pt_cap);
-    WS_ALLOC(d_packed, sizeof(PackedFrame) * F);
-    WS_ALLOC(d_lite, sizeof(PackedLite) * F);
-    WS_ALLOC(d_tailc, sizeof(vtd::TailCluster) * vtd::TP_MAXC * static_cast<size_t>(F));
-    WS_ALLOC(d_dets, sizeof(vtd::FrameDets) * F);
-    WS_ALLOC(d_job_be, sizeof(uint32_t) * 2 * F);
-    WS_ALLOC(d_members_big, sizeof(CandMemberX) * static_cast<size_t>(std::max<uint32_t>(vox_cap, 1)));
-    WS_ALLOC(fs.rowT, sizeof(unsigned long long) * 4 * FR_ROWS_MAX * static_cast<size_t>(F));
-    WS_ALLOC(fs.rowQ, sizeof(uint32_t) * 4 * FR_ROWS_MAX * static_cast<size_t>(F));
-    WS_ALLOC(fs.bmin, sizeof(uint32_t) * LB_MAX * static_cast<size_t>(F));
-    WS_ALLOC(fs.nodeA, sizeof(unsigned long long) * 4 * LB_MAX * static_cast<size_t>(F));
-    WS_ALLOC(fs.bbsave, sizeof(unsigned long long) * FR_BB64 * static_cast<size_t>(F));
-    WS_ALLOC(fs.frag, sizeof(float4) * static_cast<size_t>(F) * std::max<uint32_t>(pt_cap, 1));
-#undef WS_ALLOC
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h_packed), sizeof(PackedFrame) * F)) != hipSuccess)
-      return e;
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h_lite), sizeof(PackedLite) * F)) != hipSuccess)
-      return e;
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h_dets), sizeof(vtd::FrameDets) * F, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess)
-      return e;
-    std::memset(h_dets, 0, sizeof(vtd::FrameDets) * F);
-    if ((e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h_dets_dev), h_dets, 0)) != hipSuccess)
-      return e;
-    if ((e = h_args.assign(F, FrameArgs{})) != hipSuccess)
-      return e;
-    if ((e = hipEventCreateWithFlags(&ev_done, hipEventDisableTiming)) != hipSuccess)
-      return e;
-    if ((e = hipEventCreateWithFlags(&ev_packed, hipEventDisableTiming)) != hipSuccess)
-      return e;
-    if ((e = hipEventCreateWithFlags(&ev_h2d, hipEventDisableTiming)) != hipSuccess)
-      return e;
-    if ((e = hipEventCreateWithFlags(&ev_key, hipEventDisableTiming)) != hipSuccess)
-      return e;
-    if ((e = hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking)) != hipSuccess)
-      return e;
-    // the memsets above run on the null stream, the kernels on non-blocking streams: wait for the fills to land
-    return hipDeviceSynchronize();
+    nblk_cap = nblk_cap_;
+    return hipSuccess;
   }
 };
 
 struct ExploreBufs
 {
-  uint32_t F = 0;
-  size_t jobs_cap = 0, members_cap = 0;
-  unsigned long long* d_overlay = nullptr;
-  uint32_t *d_stack = nullptr, *d_explored = nullptr, *d_touched = nullptr, *d_ovl_list = nullptr, *d_ovl_count = nullptr, *d_job_begin = nullptr;
-  uint32_t* d_visited = nullptr;  // per frame slot: visited bits of the running flood fill (all-zero between fills)
-  vc::ExploreJob* d_jobs = nullptr;
-  vc::ExploreResult* d_results = nullptr;
-  int* d_members = nullptr;
+  DevBuf<unsigned long long> d_overlay;
+  DevBuf<uint32_t> d_stack, d_explored, d_touched, d_ovl_list, d_ovl_count, d_job_begin;
+  DevBuf<uint32_t> d_visited;  // per frame slot: visited bits of the running flood fill (all-zero between fills)
+  DevBuf<vc::ExploreJob> d_jobs;
+  DevBuf<vc::ExploreResult> d_results;
+  DevBuf<int> d_members;  // three words per member
+  // frame slots of the per-frame buffers (d_visited is the last of them that ensure_explore allocates: it stands for all eight)
+  uint32_t F() const { return static_cast<uint32_t>(d_visited.n / vc::EX_WORDS); }
 };
 
 struct HostCluster
@@ -510,7 +495,7 @@ struct HostCluster
 
 struct vofod_handle
 {
-  unsigned long long *d_prof_slab = nullptr, *d_prof_ccl = nullptr;  // stamp buffers of the VOFOD_LDS_PROF diagnostics
+  DevBuf<unsigned long long> d_prof_slab, d_prof_ccl;  // stamp buffers of the VOFOD_LDS_PROF diagnostics
   // A frame of a batch held more pure-far bricks than the close-first frame kernel takes (a cold map: nothing is "close"): the
   // batch ran again with the full clustering, and so do the following ones - until the map has gained background voxels
   // (nVoxelsOver well above the count at the overflow) or was reset.
@@ -524,23 +509,23 @@ struct vofod_handle
   std::string err;
   Prof prof;
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t stream_tail = nullptr;  // tail (k_explore) of collected async batches
-  hipStream_t stream_key = nullptr;   // staged pipeline: streaming kernels of all submitted batches, lowest priority
+  hipStream_t stream = nullptr;  // where every KLAUNCH goes: borrowed (chain_stream[0] outside a StreamScope, which points it elsewhere for its length)
+  DevStream stream_tail;  // tail (k_explore) of collected async batches
+  DevStream stream_key;   // staged pipeline: streaming kernels of all submitted batches, lowest priority
   // staged pipeline: the frame kernels of the submitted batches take the frame streams in turn.  A stream runs its kernels one
   // after the other, and a frame kernel lasts from its first workgroup's start to its LAST workgroup's end - about two workgroup
   // durations once the starts are staggered: with two streams a CU whose workgroup ended early had nothing to run until the other
   // stream's previous kernel had drained completely (round 5: ~15 % of the CU time; the stamps of tools/phase_table.sh show it).
   static constexpr int MAX_FRAME_STREAMS = 8;
-  hipStream_t stream_frames[MAX_FRAME_STREAMS] = {};
+  DevStream stream_frames[MAX_FRAME_STREAMS];
   int n_frame_streams = 0;
-  hipStream_t stream_frame = nullptr;  // == stream_frames[0]
+  hipStream_t stream_frame = nullptr;  // == stream_frames[0] (borrowed)
   int frame_toggle = 0;
   // Batches in flight.  Slots are allocated on first use.  Large batches gain nothing beyond four; small ones (whole chains side
   // by side, tails included) gain up to eight PROVIDED their streams do not share hardware queues - the runtime deals a process's
   // streams onto four by default (GPU_MAX_HW_QUEUES): 142 k frames/s at 32 frames with four queues, 204-289 k with 16.
   static constexpr int MAX_INFLIGHT = 8;
-  hipStream_t chain_stream[MAX_INFLIGHT] = {};  // [0] == stream; in-flight batches run their chains on separate streams and overlap on the device
+  DevStream chain_stream[MAX_INFLIGHT];  // [0]: the handle's own stream; in-flight batches run their chains on separate streams and overlap on the device
   Workspace wsx[MAX_INFLIGHT - 1];              // workspaces of tickets 1..7 (ticket 0 uses ws)
   Workspace* slot(int t) { return t == 0 ? &ws : &wsx[t - 1]; }
   ExploreBufs explore_slot[MAX_INFLIGHT];  // flood-fill buffers of small submitted batches: their tails run on the tickets' own streams
@@ -550,25 +535,26 @@ struct vofod_handle
 
   MapGeom mg{};
   vt::Geom hg{};
-  float *d_map = nullptr, *d_flags = nullptr, *d_ray = nullptr;
-  unsigned long long* d_mapbits = nullptr;
-  unsigned long long* d_mapclose = nullptr;  // d_mapbits dilated by hasCloseTo's stencil (k_dilate), valid while gens match
+  DevBuf<float> d_map, d_flags, d_ray;
+  DevBuf<unsigned long long> d_mapbits;
+  DevBuf<unsigned long long> d_mapclose;  // d_mapbits dilated by hasCloseTo's stencil (k_dilate), valid while gens match
   uint64_t mapbits_gen = 0, mapclose_gen = ~0ull;
   float mapclose_dist = -1.0f;
-  unsigned long long* d_counter = nullptr;  // scratch words
-  unsigned long long *d_bgcount = nullptr, *h_bgcount = nullptr;  // MB_SLOTS partial nVoxelsOver counters (64 B apart); host pinned copy
+  DevBuf<unsigned long long> d_counter;  // scratch words
+  DevBuf<unsigned long long> d_bgcount;
+  PinBuf<unsigned long long> h_bgcount;  // MB_SLOTS partial nVoxelsOver counters (64 B apart); host pinned copy
   bool bgcount_fresh = false;
-  hipEvent_t ev_stagger = nullptr;  // the streaming kernels of the batch submitted last have finished
+  DevEvent ev_stagger;  // the streaming kernels of the batch submitted last have finished
   bool ev_stagger_set = false;
-  hipEvent_t ev_explore = nullptr;  // the shared flood-fill buffers are free again (device tails of batches on different streams take turns)
-  hipEvent_t ev_bgcount = nullptr;  // recorded behind the device-to-host copy of the background count: waited for before the count is consumed
-  unsigned long long* h_counter = nullptr;  // pinned
+  DevEvent ev_explore;  // the shared flood-fill buffers are free again (device tails of batches on different streams take turns)
+  DevEvent ev_bgcount;  // recorded behind the device-to-host copy of the background count: waited for before the count is consumed
+  PinBuf<unsigned long long> h_counter;
   bool mapbits_valid = false;
   float mapbits_thr = 0;
   uint64_t n_bg_voxels = 0;
 
-  float *d_lut_dirs = nullptr, *d_lut_offs = nullptr;
-  uint8_t* d_mask = nullptr;
+  DevBuf<float> d_lut_dirs, d_lut_offs;
+  DevBuf<uint8_t> d_mask;
 
   Workspace ws, aux, sepws;
   ExploreBufs explore;
@@ -579,13 +565,13 @@ struct vofod_handle
     float leaf[3] = {0, 0, 0}, tol = 0, cmax = 0;
     ClusterParams cp{};
     int n_rows = 0;
-    StencilRow* d_rows = nullptr;
+    DevBuf<StencilRow> d_rows;
     bool brick_ok = false;
     BrickParams bp{};
-    BrickOff* d_boffs = nullptr;
-    unsigned long long *d_sure = nullptr, *d_amb = nullptr;
-    int8_t* d_pair = nullptr;  // [64*64] stencil index of offset(o2) - offset(o1), -1 when outside the forward stencil
-    LbTables* d_lbtab = nullptr;  // row / octant tables of the LDS clustering (k_frame_lds)
+    DevBuf<BrickOff> d_boffs;
+    DevBuf<unsigned long long> d_sure, d_amb;
+    DevBuf<int8_t> d_pair;  // [64*64] stencil index of offset(o2) - offset(o1), -1 when outside the forward stencil
+    DevBuf<LbTables> d_lbtab;  // row / octant tables of the LDS clustering (k_frame_lds)
     bool lds_ok = false;
   } ctab[2];
   int ctab_next = 0;
@@ -596,12 +582,10 @@ struct vofod_handle
     int n_rows = 0;
   } closetab;
   bool ray_dirty = false;
-  StencilRow* d_rows = nullptr;
-  CloseRow* d_crows = nullptr;
-  float* d_boxstage = nullptr;
-  size_t boxstage_cap = 0;
-  uint64_t* d_idxstage = nullptr;
-  size_t idxstage_cap = 0;
+  DevBuf<StencilRow> d_rows;
+  DevBuf<CloseRow> d_crows;
+  DevBuf<float> d_boxstage;
+  DevBuf<uint64_t> d_idxstage;
   std::vector<CandMemberX> h_members_big;
 
   bool background_pts_sufficient = false, sure_background_sufficient = false;
@@ -609,7 +593,15 @@ struct vofod_handle
   uint32_t last_detection_id = 0;
   bool raycast_pending = false;
   int raycast_start_its = 0;
-  vr::SepState sep;
+  vr::SepState sep;  // a view, like Workspace::ba: its buffers are owned by sep_own (words_cap / pts_cap are not used: the owners know)
+  struct SepBufs
+  {
+    DevBuf<unsigned long long> d_tbits;
+    DevBuf<uint32_t> d_tpop, d_tprefix, d_bsum, d_sure, d_sure_pre, d_vcnt, d_first, d_nsure, d_small;
+    DevBuf<float> d_px, d_py, d_pz, d_pi;
+    DevBuf<int> d_offsets;
+    PinBuf<uint32_t> h_small;
+  } sep_own;
   MapSyncState msync;  // snapshots / deltas of the maps (mapsync.h, mapsync_host.h)
   bool sep_pending = false;
   int sep_start_its = 0;
@@ -897,12 +889,8 @@ void fill_grid_params(vofod_handle* h, GridParams& g, const float leaf[3], bool 
 
 int ensure_boxstage(vofod_handle* h, size_t n)
 {
-  if (n <= h->boxstage_cap)
-    return VOFOD_OK;
-  if (h->d_boxstage)
-    (void)hipFree(h->d_boxstage);
-  h->boxstage_cap = std::max<size_t>(n, 1u << 20);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_boxstage), h->boxstage_cap * sizeof(float)));
+  if (n > h->d_boxstage.n)
+    HIPCHK(h->d_boxstage.alloc(std::max<size_t>(n, 1u << 20)));
   return VOFOD_OK;
 }
 
@@ -931,13 +919,8 @@ int scatter_set(vofod_handle* h, float* d_map, const std::vector<uint64_t>& idx,
 {
   if (idx.empty())
     return VOFOD_OK;
-  if (idx.size() > h->idxstage_cap)
-  {
-    if (h->d_idxstage)
-      (void)hipFree(h->d_idxstage);
-    h->idxstage_cap = std::max<size_t>(idx.size(), 1u << 16);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_idxstage), h->idxstage_cap * sizeof(uint64_t)));
-  }
+  if (idx.size() > h->d_idxstage.n)
+    HIPCHK(h->d_idxstage.alloc(std::max<size_t>(idx.size(), 1u << 16)));
   HIPCHK(hipMemcpyAsync(h->d_idxstage, idx.data(), idx.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
   KLAUNCH(h, k_scatter_set, dim3((idx.size() + 255) / 256), dim3(256), d_map, h->d_idxstage, static_cast<uint32_t>(idx.size()), value);
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1006,13 +989,8 @@ int stage_cloud(vofod_handle* h, Workspace& ws, uint32_t f, const void* x, const
       {
         const size_t pitch = (ws.pt_cap * stride + 255) & ~static_cast<size_t>(255);
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (ws.d_stage_aos)
-          (void)hipFree(ws.d_stage_aos);
-        ws.d_stage_aos = nullptr;
-        ws.stage_aos_bytes = 0;
         ws.aos_pitch = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&ws.d_stage_aos), pitch * ws.F));
-        ws.stage_aos_bytes = pitch * ws.F;
+        HIPCHK(ws.d_stage_aos.alloc(pitch * ws.F));
         ws.aos_pitch = pitch;
       }
       if (ws.d_stage_aos && block <= ws.aos_pitch)
@@ -1133,7 +1111,7 @@ int launch_voxelize(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams&
     }
     lf.in_packed = packed;
     if (!h->ev_stagger)
-      HIPCHK(hipEventCreateWithFlags(&h->ev_stagger, hipEventDisableTiming));
+      HIPCHK(h->ev_stagger.create(hipEventCreateWithFlags, hipEventDisableTiming));
     HIPCHK(hipEventRecord(h->ev_stagger, h->stream));  // the next batch's chain may start now
     h->ev_stagger_set = true;
     lf.frame_fused = true;
@@ -1160,9 +1138,9 @@ int launch_voxelize(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams&
     // VOFOD_SLAB_EMIT=0 keeps the separate emission kernels for every batch size
     const bool slab_emit_on = !switch_off("VOFOD_SLAB_EMIT");
     ws.bitmap_clean = false;
-    unsigned long long*& d_prof_se = h->d_prof_slab;  // VOFOD_LDS_PROF=1 (diagnostics): per-handle stamp buffer
+    DevBuf<unsigned long long>& d_prof_se = h->d_prof_slab;  // VOFOD_LDS_PROF=1 (diagnostics): per-handle stamp buffer
     if (!d_prof_se && std::getenv("VOFOD_LDS_PROF"))
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&d_prof_se), sizeof(unsigned long long) * 16 * 4096));
+      HIPCHK(d_prof_se.alloc(16 * 4096));
     if (slab_emit_on && n >= 128)
     {
       // batches that fill the chip: one workgroup per frame walks the slabs in order and emits the voxel records itself
@@ -1274,28 +1252,23 @@ int cluster_tables(vofod_handle* h, const GridParams& g, float tol, float cmax, 
     std::vector<BrickOff> offs;
     std::vector<unsigned long long> sure, amb;
     ct->brick_ok = build_brick_tables(g.leaf, tol, cmax, offs, sure, amb);
-    for (void* p : {static_cast<void*>(ct->d_rows), static_cast<void*>(ct->d_boffs), static_cast<void*>(ct->d_sure), static_cast<void*>(ct->d_amb)})
-      if (p)
-        (void)hipFree(p);
-    ct->d_rows = nullptr;
-    ct->d_boffs = nullptr;
-    ct->d_sure = ct->d_amb = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&ct->d_rows), sizeof(StencilRow) * std::max<size_t>(rows.size(), 1)));
+    ct->d_boffs.reset();
+    ct->d_sure.reset();
+    ct->d_amb.reset();
+    HIPCHK(ct->d_rows.alloc(rows.size()));
     HIPCHK(hipMemcpy(ct->d_rows, rows.data(), sizeof(StencilRow) * rows.size(), hipMemcpyHostToDevice));
     ct->n_rows = static_cast<int>(rows.size());
     if (ct->brick_ok)
     {
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&ct->d_boffs), sizeof(BrickOff) * std::max<size_t>(offs.size(), 1)));
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&ct->d_sure), sizeof(unsigned long long) * std::max<size_t>(sure.size(), 1)));
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&ct->d_amb), sizeof(unsigned long long) * std::max<size_t>(amb.size(), 1)));
+      HIPCHK(ct->d_boffs.alloc(offs.size()));
+      HIPCHK(ct->d_sure.alloc(sure.size()));
+      HIPCHK(ct->d_amb.alloc(amb.size()));
       HIPCHK(hipMemcpy(ct->d_boffs, offs.data(), sizeof(BrickOff) * offs.size(), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(ct->d_sure, sure.data(), sizeof(unsigned long long) * sure.size(), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(ct->d_amb, amb.data(), sizeof(unsigned long long) * amb.size(), hipMemcpyHostToDevice));
       ct->bp.n_off = static_cast<int>(offs.size());
       ct->bp.r2 = ct->cp.r2;
-      if (ct->d_pair)
-        (void)hipFree(ct->d_pair);
-      ct->d_pair = nullptr;
+      ct->d_pair.reset();
       if (offs.size() <= 64)
       {
         std::vector<int8_t> pair(64 * 64, -1);
@@ -1307,15 +1280,14 @@ int cluster_tables(vofod_handle* h, const GridParams& g, float tol, float cmax, 
               if (offs[o3].dx == dx && offs[o3].dy == dy && offs[o3].dz == dz)
                 pair[o1 * 64 + o2] = static_cast<int8_t>(o3);
           }
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&ct->d_pair), pair.size()));
+        HIPCHK(ct->d_pair.alloc(pair.size()));
         HIPCHK(hipMemcpy(ct->d_pair, pair.data(), pair.size(), hipMemcpyHostToDevice));
       }
       LbTables lt;
       ct->lds_ok = build_lds_tables(EdgeClassifier(g.leaf, tol, cmax), offs, sure, amb, lt);
       if (ct->lds_ok)
       {
-        if (!ct->d_lbtab)
-          HIPCHK(hipMalloc(reinterpret_cast<void**>(&ct->d_lbtab), sizeof(LbTables)));
+        HIPCHK(ct->d_lbtab.reserve(1));
         HIPCHK(hipMemcpy(ct->d_lbtab, &lt, sizeof(LbTables), hipMemcpyHostToDevice));
       }
     }
@@ -1521,10 +1493,10 @@ int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridPa
     const uint32_t lb_limit = std::getenv("VOFOD_LDS_MAX_BRICKS") ? std::min<uint32_t>(LB_MAX, std::atoi(std::getenv("VOFOD_LDS_MAX_BRICKS"))) : LB_MAX;
     if (lf.lean_emit)
     {
-      unsigned long long*& d_prof_all = h->d_prof_ccl;
+      DevBuf<unsigned long long>& d_prof_all = h->d_prof_ccl;
       if (!d_prof_all && std::getenv("VOFOD_LDS_PROF"))
       {
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&d_prof_all), sizeof(unsigned long long) * 32 * 4096));
+        HIPCHK(d_prof_all.alloc(32 * 4096));
         HIPCHK(hipMemset(d_prof_all, 0, sizeof(unsigned long long) * 32 * 4096));
       }
       // VOFOD_LDS_PROF=2: a submitted batch keeps the stamps in its ticket's slots and prints them when it is collected - the
@@ -1546,7 +1518,7 @@ int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridPa
         // (four instantiations: close first or not, packed 16-byte column loads or strided ones; the profile names the algorithmic
         // variant only: k_frame_lds_far / k_frame_lds_full)
 #define VOFOD_FRAME_LAUNCH(label, kern, UP, WT, CF)                                                                                                                                          \
-  KLAUNCH_AS(h, label, kern, dim3(n), dim3(FR_THREADS), g, bp, ct->d_lbtab, ws.d_hdrs, ws.sa, ws.pt_cap, ws.va, ws.d_labels, lb_limit, reinterpret_cast<uint32_t*>(ws.d_table), ws.fs, h->mg, mapclose, \
+  KLAUNCH_AS(h, label, kern, dim3(n), dim3(FR_THREADS), g, bp, ct->d_lbtab, ws.d_hdrs, ws.sa, ws.pt_cap, ws.va, ws.d_labels, lb_limit, reinterpret_cast<uint32_t*>(ws.d_table.p), ws.fs, h->mg, mapclose, \
           h->d_mapbits, h->d_crows, h->closetab.n_rows, UP, ws.d_table, ws.d_cand, WT, d_prof, lf.ref_lattice, ws.d_args, CF)
         const UpdateParams up_none{};
         if (lf.far_ran)  // read-only batches: cluster the far voxels only (the close-first instantiation)
@@ -1583,7 +1555,7 @@ int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridPa
     if (bp.n_off <= 64 && ct->d_pair)
     {
       // ws.d_table is free until k_finalize: it holds the per-brick connectivity masks (list order) in between
-      unsigned long long* conn = reinterpret_cast<unsigned long long*>(ws.d_table);
+      unsigned long long* conn = reinterpret_cast<unsigned long long*>(ws.d_table.p);
       KLAUNCH(h, k_brick_conn, fgrid(g, gv * CONN_LANES), dim3(256), g, bp, ct->d_boffs, ct->d_sure, ct->d_amb, ws.d_hdrs, ws.ba, conn, ws.d_bconn);
       KLAUNCH(h, k_brick_link_tr, fgrid(g, gv), dim3(256), g, bp, ct->d_boffs, ct->d_pair, ws.d_hdrs, ws.ba, conn, ws.d_bconn);
     }
@@ -1635,7 +1607,7 @@ int ensure_mapbits(vofod_handle* h, float thr)
   KLAUNCH(h, k_mapbits, dim3(1024), dim3(256), h->d_map, h->mg.n, thr, h->d_mapbits, h->d_bgcount);
   HIPCHK(hipMemcpyAsync(h->h_bgcount, h->d_bgcount, sizeof(unsigned long long) * 8 * MB_SLOTS, hipMemcpyDeviceToHost, h->stream));
   if (!h->ev_bgcount)
-    HIPCHK(hipEventCreateWithFlags(&h->ev_bgcount, hipEventDisableTiming));
+    HIPCHK(h->ev_bgcount.create(hipEventCreateWithFlags, hipEventDisableTiming));
   HIPCHK(hipEventRecord(h->ev_bgcount, h->stream));
   h->bgcount_fresh = true;
   h->mapbits_gen++;
@@ -1676,43 +1648,33 @@ int raycast_finish_locked(vofod_handle* h);
 int ensure_explore(vofod_handle* h, ExploreBufs& eb, uint32_t F, size_t n_jobs, size_t n_members)
 {
   const size_t ovl_words = (h->mg.n + 63) / 64;
-  if (eb.F < F)
+  if (eb.F() < F)
   {
-    for (void* p : {static_cast<void*>(eb.d_overlay), static_cast<void*>(eb.d_stack), static_cast<void*>(eb.d_explored), static_cast<void*>(eb.d_touched),
-                    static_cast<void*>(eb.d_ovl_list), static_cast<void*>(eb.d_ovl_count), static_cast<void*>(eb.d_job_begin), static_cast<void*>(eb.d_visited)})
-      if (p)
-        (void)hipFree(p);
-    eb.F = F;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_overlay), sizeof(unsigned long long) * ovl_words * F));
+    // (all eight go before the first comes back: the overlay is large.  Without d_visited there are no frame slots.)
+    for (DevBuf<uint32_t>* b : {&eb.d_visited, &eb.d_stack, &eb.d_explored, &eb.d_touched, &eb.d_ovl_list, &eb.d_ovl_count, &eb.d_job_begin})
+      b->reset();
+    HIPCHK(eb.d_overlay.alloc(ovl_words * F));
     HIPCHK(hipMemset(eb.d_overlay, 0, sizeof(unsigned long long) * ovl_words * F));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_stack), sizeof(uint32_t) * vc::EX_CELLS * F));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_explored), sizeof(uint32_t) * vc::EX_CELLS * F));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_touched), sizeof(uint32_t) * vc::EX_CELLS * F));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_ovl_list), sizeof(uint32_t) * vc::EX_CELLS * F));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_ovl_count), sizeof(uint32_t) * F));
+    HIPCHK(eb.d_stack.alloc(static_cast<size_t>(vc::EX_CELLS) * F));
+    HIPCHK(eb.d_explored.alloc(static_cast<size_t>(vc::EX_CELLS) * F));
+    HIPCHK(eb.d_touched.alloc(static_cast<size_t>(vc::EX_CELLS) * F));
+    HIPCHK(eb.d_ovl_list.alloc(static_cast<size_t>(vc::EX_CELLS) * F));
+    HIPCHK(eb.d_ovl_count.alloc(F));
     HIPCHK(hipMemset(eb.d_ovl_count, 0, sizeof(uint32_t) * F));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_job_begin), sizeof(uint32_t) * (F + 1)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_visited), sizeof(uint32_t) * vc::EX_WORDS * F));
+    HIPCHK(eb.d_job_begin.alloc(F + 1));
+    HIPCHK(eb.d_visited.alloc(static_cast<size_t>(vc::EX_WORDS) * F));
     HIPCHK(hipMemset(eb.d_visited, 0, sizeof(uint32_t) * vc::EX_WORDS * F));
     HIPCHK(hipDeviceSynchronize());  // null-stream memsets vs non-blocking streams
   }
-  if (eb.jobs_cap < n_jobs)
+  if (eb.d_results.n < n_jobs)  // (allocated behind d_jobs: it stands for both)
   {
-    if (eb.d_jobs)
-      (void)hipFree(eb.d_jobs);
-    if (eb.d_results)
-      (void)hipFree(eb.d_results);
-    eb.jobs_cap = std::max<size_t>(n_jobs * 2, 1024);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_jobs), sizeof(vc::ExploreJob) * eb.jobs_cap));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_results), sizeof(vc::ExploreResult) * eb.jobs_cap));
+    const size_t cap = std::max<size_t>(n_jobs * 2, 1024);
+    eb.d_results.reset();
+    HIPCHK(eb.d_jobs.alloc(cap));
+    HIPCHK(eb.d_results.alloc(cap));
   }
-  if (eb.members_cap < n_members)
-  {
-    if (eb.d_members)
-      (void)hipFree(eb.d_members);
-    eb.members_cap = std::max<size_t>(n_members * 2, 1 << 16);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&eb.d_members), sizeof(int) * 3 * eb.members_cap));
-  }
+  if (eb.d_members.n < 3 * n_members)
+    HIPCHK(eb.d_members.alloc(3 * std::max<size_t>(n_members * 2, 1 << 16)));
   return VOFOD_OK;
 }
 
