@@ -470,7 +470,11 @@ def test_voxels_as_pc_debug_clouds(oracle, hip):
 def test_single_pass_input_points_on_cell_boundaries(oracle, hip, voxel_size):
     """The frame kernel reads the input once and encodes the survivors in a reference lattice; points within a rounding band of a
     cell boundary are re-encoded with the frame's own offset.  Frames full of points a few ulps around cell boundaries
-    (of the reference lattice and of the frame's own), with different bounding boxes per frame, against the oracle."""
+    (of the reference lattice and of the frame's own), with different bounding boxes per frame, against the oracle.
+    0.25 m: the frame kernel runs (asserted) - its input pass and the fragile route; these frames occupy ~7 800 bricks, more than
+    the LDS clustering takes, so the batch is then run again on the general kernels (tests/test_gpu_frame_inputs.py compares the
+    frame kernel's own output on the same points inside a smaller box).  0.1 m: the default area has 4.76 M bricks of 0.4 m, far
+    beyond the frame kernel's lattice (fill_ref_lattice) - this parameter runs on the general kernels alone (asserted)."""
     sensor = "os1-16"
     ref, dev = make_pair(oracle, hip, sensor, voxel_size, max_batch=6, ground_points_max_distance=6 * voxel_size)
     for d in (ref, dev):
@@ -500,8 +504,18 @@ def test_single_pass_input_points_on_cell_boundaries(oracle, hip, voxel_size):
         tfs.append(t)
     tfs = np.stack(tfs)
     da, pa, ga = ref.process_batch(scans, tfs, debug=True)
+    dev.lib.profile_enable(dev.h, 1)
     db, pb, gb = dev.process_batch(scans, tfs, debug=True)
+    names = _profiled_kernels(dev.lib, dev)
+    dev.lib.profile_enable(dev.h, 0)
     np.testing.assert_array_equal(pb, pa)
     for x, y in zip(ga, gb):
         assert_scan_debug_equal(x, y)
     assert min(len(x["weighted"]) for x in ga) > 2000
+    if not os.environ.get("VOFOD_TEST_HARNESS_SELFCHECK"):
+        lds_off = os.environ.get("VOFOD_CCL") == "voxel" or os.environ.get("VOFOD_BRICK_LDS") == "0"
+        frame = [n for n in names if n.startswith("k_frame_lds")]
+        if voxel_size == 0.25 and not lds_off:
+            assert frame, names
+        else:
+            assert not frame and "k_bbox" in names, names

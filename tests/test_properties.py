@@ -2,12 +2,14 @@
 stages of a scan against numpy / scipy.  The statements that go through the C-ABI alone live in tests/statements.py, where
 tests/test_gpu_statements.py holds the HIP library to the very same functions; here they run on the oracle."""
 import ctypes as C
+import math
 
 import numpy as np
 import pytest
 from hypothesis import given, settings, strategies as st
 
 import statements
+from frame_geometry import FALLBACK_SWITCHES, ROOT, TABLE, capacities, ref_lattice
 from vofod_amd import capi
 
 
@@ -306,3 +308,41 @@ def test_close_far_split_and_clusters_of_a_scan_against_scipy(oracle, sensor, vs
 @pytest.mark.parametrize("seed,max_bg", [(1, 0.8), (2, 0.8), (3, 1.6), (4, 2.2), (5, 0.8)])
 def test_sepclusters_role_against_numpy(oracle, seed, max_bg):
     statements.sepclusters_role_against_numpy(oracle, seed, max_bg)
+
+
+# ---- the frame kernel's area x voxel-size limit (fill_ref_lattice, vofod_hip.hip) --------------------------------------------
+@pytest.mark.parametrize("row", list(TABLE))
+def test_geometry_table_mirrors_fill_ref_lattice(row):
+    """fill_ref_lattice in host float32 arithmetic: dims, bricks, eps and exactly the stated failing conditions for every row -
+    each "off" row lies just beyond ONE limit, its "on" neighbour just inside it"""
+    off, size, vs, dims, bricks, eps, fails, _, _ = TABLE[row]
+    cap = capacities()
+    assert (cap["LB_BITWORDS"], cap["FR_ROWS_MAX"], cap["FR_MAX_NBZ"]) == (9984, 8192, 64)  # what the table was worked out for
+    rl = ref_lattice(off, size, vs, cap)
+    assert tuple(rl["dims"]) == dims
+    assert rl["bricks"] == bricks
+    assert abs(rl["eps"] - eps) < 5e-5, rl["eps"]
+    assert tuple(k for k, ok in rl["conds"].items() if not ok) == fails
+    assert rl["on"] == (not fails)
+    n_vox = np.prod([math.ceil(float(np.float32(1) / np.float32(vs) * np.float32(s))) + 1 for s in size])
+    assert n_vox <= (38.0e6 if row == "default_0.2" else 20.0e6)  # voxels of the map each detector allocates three times (host memory of the GPU cases)
+
+
+def test_geometry_table_limits_are_tight():
+    """the rows that name a limit sit at it: 99.5 % of the brick cap, nbx 509 / 521 around 512, nbz 63 / 67 around 64, rows 8 016 /
+    9 018 around 8 192"""
+    cap = capacities()
+    rl = {k: ref_lattice(*TABLE[k][:3], cap) for k in TABLE}
+    assert 0.99 < rl["default"]["bricks"] / (cap["LB_BITWORDS"] * 32) <= 1.0
+    assert (rl["long_x_508"]["nb"][0], rl["long_x_520"]["nb"][0]) == (509, 521)
+    assert (rl["tall_62"]["nb"][2], rl["tall_66"]["nb"][2]) == (63, 67)
+    assert (rl["long_y_rows_8016"]["rows"], rl["long_y_rows_9018"]["rows"]) == (8016, 9018)
+    assert rl["far_4000"]["eps"] < 0.05 < rl["far_5000"]["eps"]
+
+
+def test_fallback_switch_list_is_the_matrix_script_s():
+    """the route assertions of test_gpu_frame_inputs.py loosen under exactly the switches tools/run_fallback_matrix.sh runs"""
+    import re
+
+    text = (ROOT / "tools" / "run_fallback_matrix.sh").read_text()
+    assert set(re.findall(r"VOFOD_[A-Z_]+(?==)", text)) == set(FALLBACK_SWITCHES)

@@ -972,8 +972,10 @@ int stage_cloud(vofod_handle* h, Workspace& ws, uint32_t f, const void* x, const
   // the kernels then read the columns in place at the struct's stride (the frame kernel's strided input pass, k_bbox / k_setbits / k_count).  Round 3 gathered every column on the
   // host (three passes over the cloud and a synchronisation per column: ~1 ms per frame).  4 x the bytes of packed columns over
   // PCIe: the link's ceiling for this layout is ~8 k frames/s of OS1-128.
-  // The kernels dereference floats in place: only structs whose stride and member offsets are multiples of 4 take this path, a
-  // packed / odd layout is gathered below.  The staging block is sized by the FIRST frame of a batch (or by
+  // The kernels dereference floats in place ON THE DEVICE, where the copy starts at the lowest of the three members: only
+  // structs whose stride and whose members' distances from that lowest member are multiples of 4 take this path (the host
+  // addresses need not be aligned: x at +1 of a packed 20-byte struct with y at +5 and z at +9 is read in place), a struct of
+  // odd stride or with members an odd distance apart is gathered below.  The staging block is sized by the FIRST frame of a batch (or by
   // vofod_reserve's caller, which passes through here with frame 0 too); a later frame of the same batch whose struct is
   // larger than the block's pitch allows is gathered as well - growing the block there would free it under the earlier frames'
   // copies and pointers.
@@ -1061,7 +1063,10 @@ RefLattice fill_ref_lattice(const GridParams& g)
   const float u = 1.1920929e-7f;  // 2^-23
   const float e1 = 2.0f * (2.0f * cmax) * inv_max * u, e2 = 2.0f * cmax * u * inv_max + dmax * 2.0f * u;
   rl.eps = 4.0f * (e1 + e2) + 1e-4f;
-  // (eps < 0.05: at most ~30 % of the points are fragile, and three words of the frame's side list hold each of them)
+  // (eps < 0.05: a point is fragile when any of its three fractions lies within eps of a boundary - up to 1 - (1 - 2 eps)^3 = 27 %
+  // of uniformly spread points; measured on OS1-16 scenes, whose ground sheet lies on a cell boundary: 45 % at eps 0.036 and 52 % at
+  // eps 0.047, areas 3-4 km from the origin (tests/test_gpu_frame_inputs.py), 3 % on the default area.  The frame's side list holds
+  // one entry per input point, so any share fits)
   // the frame kernel's bricks are bricks of this lattice: its brick bitmap has to fit LDS (LB_BITWORDS), its brick rows the
   // per-frame row tables, the brick coordinates the fields of a code (9 + 9 + 6 bits)
   for (int a = 0; a < 3; a++)
@@ -1516,7 +1521,7 @@ int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridPa
       {
         lf.far_ran = up_tables && mapclose && ws.close_first;
         // (four instantiations: close first or not, packed 16-byte column loads or strided ones; the profile names the algorithmic
-        // variant only: k_frame_lds_far / k_frame_lds_full)
+        // variant, k_frame_lds_far / k_frame_lds_full, and the strided input pass by the suffix _strided)
 #define VOFOD_FRAME_LAUNCH(label, kern, UP, WT, CF)                                                                                                                                          \
   KLAUNCH_AS(h, label, kern, dim3(n), dim3(FR_THREADS), g, bp, ct->d_lbtab, ws.d_hdrs, ws.sa, ws.pt_cap, ws.va, ws.d_labels, lb_limit, reinterpret_cast<uint32_t*>(ws.d_table.p), ws.fs, h->mg, mapclose, \
           h->d_mapbits, h->d_crows, h->closetab.n_rows, UP, ws.d_table, ws.d_cand, WT, d_prof, lf.ref_lattice, ws.d_args, CF)
@@ -1526,14 +1531,14 @@ int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridPa
           if (lf.in_packed)
             VOFOD_FRAME_LAUNCH("k_frame_lds_far", k_frame_lds_far_p, *up_tables, 1, ws.close_first);
           else
-            VOFOD_FRAME_LAUNCH("k_frame_lds_far", k_frame_lds_far, *up_tables, 1, ws.close_first);
+            VOFOD_FRAME_LAUNCH("k_frame_lds_far_strided", k_frame_lds_far, *up_tables, 1, ws.close_first);
         }
         else
         {
           if (lf.in_packed)
             VOFOD_FRAME_LAUNCH("k_frame_lds_full", k_frame_lds_full_p, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0);
           else
-            VOFOD_FRAME_LAUNCH("k_frame_lds_full", k_frame_lds_full, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0);
+            VOFOD_FRAME_LAUNCH("k_frame_lds_full_strided", k_frame_lds_full, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0);
         }
 #undef VOFOD_FRAME_LAUNCH
         lf.finalize_fused = up_tables && mapclose;

@@ -102,8 +102,9 @@ class SynthScan:
     keep: list = field(default_factory=list)
 
 
-def make_scan(scene: Scene, tf: np.ndarray, sensor: str = "os1-128", seed: int = 0, noise_sigma: float = 0.02) -> SynthScan:
-    h, w, vfov_deg, max_range = SENSORS[sensor]
+def make_scan(scene: Scene, tf: np.ndarray, sensor="os1-128", seed: int = 0, noise_sigma: float = 0.02) -> SynthScan:
+    """`sensor`: a name of SENSORS, or (vrays, hrays, vfov_deg, max_range_m) itself"""
+    h, w, vfov_deg, max_range = SENSORS[sensor] if isinstance(sensor, str) else sensor
     vfov = np.float32(np.deg2rad(vfov_deg))
     rng = np.random.default_rng(seed + 104729)
     dirs_s = sim_lut(w, h, float(vfov)).astype(np.float64)
