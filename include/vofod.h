@@ -123,6 +123,21 @@ enum { VOFOD_MEM_HOST = 0, VOFOD_MEM_DEVICE = 1 };
  * base pointer + common byte stride, so the 48-byte ouster_ros::Point AoS
  * (x at +0, y +4, z +8, intensity +16, range +36 in ouster_ros >= 0.10) and a
  * packed SoA (stride 4) both work without a copy on the caller's side. */
+/* RANGE IMAGES.  A vofod_scan with x == y == z == NULL and range != NULL is a range image: what the sensor itself delivers,
+ * width * height uint32 millimetres at stride_bytes, pixel i = row * width + col in the order of the handle's LUT
+ * (vofod_static_params::lut_*), in either memspace.  The product library rebuilds the points on the device; the point of pixel i
+ * is DEFINED as (every operation IEEE float32, each rounded once, no fused multiply-add)
+ *     r    = float(range[i]) * 0.001f                          (uint32 -> float32 round-to-nearest-even, then one multiply)
+ *     p[a] = (lut_directions[3i+a] * r) + lut_offsets[3i+a]     a = 0, 1, 2
+ *     p    = (+0, +0, +0)  when range[i] == 0                   (what ouster_ros publishes for a pixel without a return)
+ * - the sensor model check_sensor_params holds a cloud to (vofod_nodelet.cpp:1869-1917).  It is NOT bit-identical to the cloud
+ * ouster_ros publishes: ouster_ros evaluates in double with the unnormalised LUT and casts afterwards; the two differ by about
+ * one float32 ulp of the coordinate, far inside the 1e-3 of that check.
+ * vofod_process_scan, vofod_process_batch and vofod_batch_submit accept range images (a batch may mix them with point scans);
+ * `intensity` stays optional there and is still required by vofod_raycast_begin and VOFOD_SCAN_AUTO_RAYCAST.  Exactly one or two
+ * of x, y, z NULL is VOFOD_ERR_INVALID_ARG, and so is all three NULL without `range`.  A device-resident range column needs a
+ * base and a stride that are multiples of 4 bytes.  vofod_check_sensor_params compares points against the LUT and takes no
+ * range image.  The CPU oracle has no range input: it returns VOFOD_ERR_INVALID_ARG for one. */
 typedef struct vofod_scan {
   const void* x;          /* float */
   const void* y;          /* float */
@@ -394,6 +409,14 @@ int vofod_serialize_detections(const vofod_msg_header* header, const vofod_detec
 int vofod_serialize_status(const vofod_msg_header* header, int detection_enabled, int detection_active, uint8_t* buf, size_t cap, size_t* n_bytes);
 int vofod_serialize_profiling_info(uint32_t stamp_sec, uint32_t stamp_nsec, uint32_t routine_id, uint64_t event_sequence, uint8_t event_type, uint8_t* buf, size_t cap,
                                    size_t* n_bytes);
+
+/* ------------------------------------------------- range images (product library only)
+ *
+ * The points of a range image (see vofod_scan) as the hot path sees them: decoded on the device with the handle's LUT by the
+ * kernel the per-scan entry points use (k_range_decode), into three packed columns of width * height floats in `out_memspace`
+ * (VOFOD_MEM_HOST or VOFOD_MEM_DEVICE).  For debug clouds and for holding the kernel to the definition.
+ * VOFOD_ERR_INVALID_ARG: `scan` is no range image; VOFOD_ERR_SIZE_MISMATCH: its width or height differ from the handle's. */
+int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, float* y, float* z, int32_t out_memspace);
 
 /* ------------------------------------------------- batched mode: the collective (product library only)
  *

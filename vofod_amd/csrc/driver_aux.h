@@ -88,6 +88,17 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
     d_rng = static_cast<const char*>(scan->range);
     stride = scan->stride_bytes;
   }
+  else if (is_range_image(*scan))
+  {
+    // a range image: only the two columns the raycast reads go to frame slot 0.  Columns 0-2 and the frame's arguments stay as
+    // they are: under VOFOD_SCAN_AUTO_RAYCAST they hold this very scan's decoded points.
+    float* base = h->ws.d_stage;
+    VCHK(stage_host_column(h, base + 3 * static_cast<size_t>(h->ws.pt_cap), scan->intensity, scan->stride_bytes, n));
+    VCHK(stage_host_column(h, base + 4 * static_cast<size_t>(h->ws.pt_cap), scan->range, scan->stride_bytes, n));
+    d_int = reinterpret_cast<const char*>(base + 3 * static_cast<size_t>(h->ws.pt_cap));
+    d_rng = reinterpret_cast<const char*>(base + 4 * static_cast<size_t>(h->ws.pt_cap));
+    stride = 4;
+  }
   else
   {
     const int r = stage_cloud(h, h->ws, 0, scan->x ? scan->x : scan->intensity, scan->y ? scan->y : scan->intensity, scan->z ? scan->z : scan->intensity,
@@ -1108,6 +1119,31 @@ int vofod_batch_collect(vofod_handle* h, int ticket, vofod_detection* out, size_
     return r != VOFOD_OK ? r : collect();
   };
   return with_reruns(collect, again);
+}
+
+int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, float* y, float* z, int32_t out_memspace)
+{
+  if (!h || !scan || !x || !y || !z || !is_range_image(*scan) || (out_memspace != VOFOD_MEM_HOST && out_memspace != VOFOD_MEM_DEVICE) ||
+      (scan->memspace != VOFOD_MEM_HOST && scan->memspace != VOFOD_MEM_DEVICE))
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  (void)hipSetDevice(h->device);
+  if (scan->height != h->sp.sensor_vrays || scan->width != h->sp.sensor_hrays)
+    return VOFOD_ERR_SIZE_MISMATCH;
+  VCHK(busy_check(h, true, false));
+  // one frame through the batch path's staging and kernel: frame slot 0 of the synchronous workspace
+  Workspace& ws = h->ws;
+  const size_t npts = static_cast<size_t>(scan->width) * scan->height;
+  const float tf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  bool host_copies = false;
+  VCHK(stage_inputs(h, ws, scan, tf, 1, npts, host_copies));
+  VCHK(decode_ranges(h, ws, npts));
+  float* out[3] = {x, y, z};
+  for (int c = 0; c < 3; c++)
+    HIPCHK(hipMemcpyAsync(out[c], ws.d_stage + static_cast<size_t>(c) * ws.pt_cap, npts * sizeof(float), out_memspace == VOFOD_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                          h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VOFOD_OK;
 }
 
 int vofod_raycast_begin(vofod_handle* h, const vofod_scan* scan, const float tf[12])

@@ -157,6 +157,9 @@ int route_submitted(vofod_handle* h, const Workspace& ws, uint32_t n, LaunchRout
   return VOFOD_OK;
 }
 
+// a range image (include/vofod.h): no point columns, only the sensor's range column
+inline bool is_range_image(const vofod_scan& s) { return !s.x && !s.y && !s.z && s.range; }
+
 // ---- stage inputs (filterAndTransform :621-684 reads them)
 // (the re-run of a batch that overflowed the LDS kernels keeps the frame arguments and the staged columns of its first
 // launch: the caller's host buffers need not outlive vofod_batch_submit)
@@ -169,7 +172,14 @@ int route_submitted(vofod_handle* h, const Workspace& ws, uint32_t n, LaunchRout
 int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const float* tfs, uint32_t n, size_t npts, bool& host_copies)
 {
   bool staged_2d = false;
-  if (n >= 2 && scans[0].memspace == VOFOD_MEM_HOST)
+  ws.n_rjobs = 0;
+  auto slot = [&](uint32_t f) { return ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5; };
+  // the frame's arguments point at the packed x | y | z columns of its staging slot (copied there, or decoded there by k_range_decode)
+  auto slot_args = [&](uint32_t f) {
+    float* base = slot(f);
+    return stage_cloud(h, ws, f, base, base + ws.pt_cap, base + 2 * static_cast<size_t>(ws.pt_cap), nullptr, nullptr, 4, npts, VOFOD_MEM_DEVICE, FA_SCAN, tfs + 12 * f);
+  };
+  if (n >= 2 && scans[0].memspace == VOFOD_MEM_HOST && scans[0].x)
   {
     const char* x0 = static_cast<const char*>(scans[0].x);
     const ptrdiff_t pitch = static_cast<const char*>(scans[1].x) - x0;
@@ -185,9 +195,29 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
     {
       HIPCHK(hipMemcpy2DAsync(ws.d_stage, sizeof(float) * 5 * ws.pt_cap, x0, static_cast<size_t>(pitch), npts * 12, n, hipMemcpyHostToDevice, h->stream));
       for (uint32_t f = 0; f < n; f++)
+        VCHK(slot_args(f));
+      staged_2d = true;
+    }
+  }
+  // Host-resident range images at a constant pitch (one uint32 column per frame, 4 B per point: a third of the x | y | z block)
+  // cross the link the same way, with ONE 2-D copy into column 4 of the slots; k_range_decode rebuilds columns 0-2 from there.
+  if (n >= 2 && scans[0].memspace == VOFOD_MEM_HOST && is_range_image(scans[0]))
+  {
+    const char* r0 = static_cast<const char*>(scans[0].range);
+    const ptrdiff_t pitch = static_cast<const char*>(scans[1].range) - r0;
+    bool ok = pitch >= static_cast<ptrdiff_t>(npts * 4);
+    for (uint32_t f = 0; f < n && ok; f++)
+    {
+      const vofod_scan& s = scans[f];
+      ok = s.memspace == VOFOD_MEM_HOST && is_range_image(s) && s.stride_bytes == 4 && static_cast<const char*>(s.range) == r0 + static_cast<ptrdiff_t>(f) * pitch;
+    }
+    if (ok)
+    {
+      HIPCHK(hipMemcpy2DAsync(ws.d_stage + 4 * static_cast<size_t>(ws.pt_cap), sizeof(float) * 5 * ws.pt_cap, r0, static_cast<size_t>(pitch), npts * 4, n, hipMemcpyHostToDevice, h->stream));
+      for (uint32_t f = 0; f < n; f++)
       {
-        float* base = ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5;
-        VCHK(stage_cloud(h, ws, f, base, base + ws.pt_cap, base + 2 * static_cast<size_t>(ws.pt_cap), nullptr, nullptr, 4, npts, VOFOD_MEM_DEVICE, FA_SCAN, tfs + 12 * f));
+        VCHK(slot_args(f));
+        ws.h_rjobs.p[ws.n_rjobs++] = vrd::RangeJob{reinterpret_cast<const char*>(slot(f) + 4 * static_cast<size_t>(ws.pt_cap)), slot(f), 4, 0};
       }
       staged_2d = true;
     }
@@ -197,8 +227,49 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
   {
     const vofod_scan& s = scans[f];
     host_copies |= s.memspace != VOFOD_MEM_DEVICE;
-    VCHK(stage_cloud(h, ws, f, s.x, s.y, s.z, nullptr, nullptr, s.stride_bytes, npts, s.memspace, FA_SCAN, tfs + 12 * f));
+    if (!is_range_image(s))
+    {
+      VCHK(stage_cloud(h, ws, f, s.x, s.y, s.z, nullptr, nullptr, s.stride_bytes, npts, s.memspace, FA_SCAN, tfs + 12 * f));
+      continue;
+    }
+    // a range image: device-resident ranges are read where they lie, a host column goes to column 4 of the slot (gathered when strided)
+    vrd::RangeJob job{static_cast<const char*>(s.range), slot(f), s.stride_bytes, 0};
+    if (s.memspace != VOFOD_MEM_DEVICE)
+    {
+      VCHK(stage_host_column(h, slot(f) + 4 * static_cast<size_t>(ws.pt_cap), s.range, s.stride_bytes, npts));
+      job.src = reinterpret_cast<const char*>(slot(f) + 4 * static_cast<size_t>(ws.pt_cap));
+      job.stride = 4;
+    }
+    else if (s.stride_bytes % 4 != 0 || reinterpret_cast<uintptr_t>(s.range) % 4 != 0)
+    {
+      h->err = "device-resident range column: base and stride must be multiples of 4 bytes";
+      return VOFOD_ERR_INVALID_ARG;
+    }
+    VCHK(slot_args(f));
+    ws.h_rjobs.p[ws.n_rjobs++] = job;
   }
+  if (ws.n_rjobs)
+    HIPCHK(hipMemcpyAsync(ws.d_rjobs, ws.h_rjobs, sizeof(vrd::RangeJob) * ws.n_rjobs, hipMemcpyHostToDevice, h->stream));
+  return VOFOD_OK;
+}
+
+// k_range_decode over the job list stage_inputs left in the workspace: one launch per batch, on the stream of the staging copies
+int decode_ranges(vofod_handle* h, Workspace& ws, size_t npts)
+{
+  if (!ws.n_rjobs)
+    return VOFOD_OK;
+  bool vec = npts % 4 == 0 && ws.pt_cap % 4 == 0;
+  for (uint32_t j = 0; j < ws.n_rjobs && vec; j++)
+    vec = ws.h_rjobs.p[j].stride == 4 && reinterpret_cast<uintptr_t>(ws.h_rjobs.p[j].src) % 16 == 0;
+  // few frames: one per thread keeps every CU busy; many: up to RD_CHUNK_MAX per thread share one read of the LUT
+  const uint32_t chunk = std::min(std::max(ws.n_rjobs / 16u, 1u), vrd::RD_CHUNK_MAX);
+  const uint32_t n_px = static_cast<uint32_t>(npts), threads = vec ? n_px / 4u : n_px;
+  const dim3 grid((threads + vrd::RD_THREADS - 1) / vrd::RD_THREADS, (ws.n_rjobs + chunk - 1) / chunk);
+  if (vec)
+    KLAUNCH_AS(h, "k_range_decode", vrd::k_range_decode<true>, grid, dim3(vrd::RD_THREADS), ws.d_rjobs.p, ws.n_rjobs, chunk, n_px, ws.pt_cap, h->d_lut_dirs.p, h->d_lut_offs.p);
+  else
+    KLAUNCH_AS(h, "k_range_decode", vrd::k_range_decode<false>, grid, dim3(vrd::RD_THREADS), ws.d_rjobs.p, ws.n_rjobs, chunk, n_px, ws.pt_cap, h->d_lut_dirs.p, h->d_lut_offs.p);
+  HIPCHK(hipGetLastError());
   return VOFOD_OK;
 }
 
@@ -433,7 +504,7 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   for (uint32_t f = 0; f < n; f++)
   {
     const vofod_scan& s = call.scans[f];
-    if (!s.x || !s.y || !s.z)
+    if ((!s.x || !s.y || !s.z) && !is_range_image(s))  // (one or two of the three NULL, or no range column either)
       return VOFOD_ERR_INVALID_ARG;
     if (static_cast<size_t>(s.width) * s.height != npts)  // :895-899
       return VOFOD_ERR_SIZE_MISMATCH;
@@ -480,6 +551,8 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   else
     host_copies = false;
   H2DGuard h2d_guard{ws.ev_h2d, host_copies};
+  if (!rerun)
+    VCHK(decode_ranges(h, ws, npts));
 
   GridParams& g = call.g;
   const float leaf[3] = {sp.voxel_size, sp.voxel_size, sp.voxel_size};

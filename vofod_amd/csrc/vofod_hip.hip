@@ -32,6 +32,7 @@
 #include "kernels_far.h"
 #include "kernels_voxelize.h"
 #include "mapsync.h"
+#include "range_decode.h"
 
 using namespace vk;
 
@@ -334,6 +335,10 @@ struct Workspace
   DevBuf<float> d_stage;  // F * pt_cap * 5 words: x, y, z, intensity, range of host-resident inputs
   DevBuf<char> d_stage_aos;  // host-resident array-of-structs clouds (the nodelet's 48-byte ouster_ros::Point) cross the link as they are:
   size_t aos_pitch = 0;      // F * aos_pitch bytes, allocated on first use; the kernels read x / y / z in place at the struct's stride
+  // range images of the batch (range_decode.h): their job list, written in pinned memory by stage_inputs and uploaded with the inputs
+  DevBuf<vrd::RangeJob> d_rjobs;
+  PinBuf<vrd::RangeJob> h_rjobs;
+  uint32_t n_rjobs = 0;
   DevBuf<PackedFrame> d_packed;
   PinBuf<PackedFrame> h_packed;
   DevBuf<PackedLite> d_lite;
@@ -437,6 +442,8 @@ private:
     HIP_TRY(alloc_view(sa_counts, sa.counts, 2 * static_cast<size_t>(F_)));
     sa.keys = d_ptrank;
     HIP_TRY(d_stage.alloc(5 * static_cast<size_t>(F_) * pt_cap_));
+    HIP_TRY(d_rjobs.alloc(F_));
+    HIP_TRY(h_rjobs.alloc(F_));
     HIP_TRY(d_packed.alloc(F_));
     HIP_TRY(d_lite.alloc(F_));
     HIP_TRY(d_tailc.alloc(vtd::TP_MAXC * static_cast<size_t>(F_)));
@@ -948,6 +955,23 @@ int do_reset(vofod_handle* h)
   return VOFOD_OK;
 }
 
+// one host column of n 4-byte elements at `stride` into `dst` (device), gathered first where the stride is not 4
+int stage_host_column(vofod_handle* h, void* dst, const void* src, size_t stride, size_t n)
+{
+  std::vector<float> tmp;
+  if (stride != 4)
+  {
+    tmp.resize(n);
+    for (size_t i = 0; i < n; i++)
+      std::memcpy(&tmp[i], static_cast<const char*>(src) + i * stride, 4);
+    src = tmp.data();
+  }
+  HIPCHK(hipMemcpyAsync(dst, src, n * 4, hipMemcpyHostToDevice, h->stream));
+  if (stride != 4)
+    HIPCHK(hipStreamSynchronize(h->stream));  // tmp goes away
+  return VOFOD_OK;
+}
+
 // stage the columns of one cloud into the workspace if they live on the host; fill FrameArgs
 int stage_cloud(vofod_handle* h, Workspace& ws, uint32_t f, const void* x, const void* y, const void* z, const void* intensity, const void* range, size_t stride,
                 size_t n, int memspace, uint32_t flags, const float* tf)
@@ -1010,23 +1034,9 @@ int stage_cloud(vofod_handle* h, Workspace& ws, uint32_t f, const void* x, const
   }
   float* base = ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5;
   const void* cols[5] = {x, y, z, intensity, range};
-  std::vector<float> tmp;
   for (int c = 0; c < 5; c++)
-  {
-    if (!cols[c])
-      continue;
-    const void* src = cols[c];
-    if (stride != 4)
-    {
-      tmp.resize(n);
-      for (size_t i = 0; i < n; i++)
-        std::memcpy(&tmp[i], static_cast<const char*>(cols[c]) + i * stride, 4);
-      src = tmp.data();
-    }
-    HIPCHK(hipMemcpyAsync(base + static_cast<size_t>(c) * ws.pt_cap, src, n * 4, hipMemcpyHostToDevice, h->stream));
-    if (stride != 4)
-      HIPCHK(hipStreamSynchronize(h->stream));  // tmp is reused
-  }
+    if (cols[c])
+      VCHK(stage_host_column(h, base + static_cast<size_t>(c) * ws.pt_cap, cols[c], stride, n));
   a.x = reinterpret_cast<const char*>(base);
   a.y = reinterpret_cast<const char*>(base + ws.pt_cap);
   a.z = reinterpret_cast<const char*>(base + 2 * static_cast<size_t>(ws.pt_cap));

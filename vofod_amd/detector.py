@@ -39,6 +39,12 @@ class ScanData:
     memspace: int = capi.MEM_HOST
     stamp: float = 0.0
 
+    @classmethod
+    def range_image(cls, range, width: int, height: int, intensity=None, stride_bytes: int = 4, memspace: int = capi.MEM_HOST, stamp: float = 0.0) -> "ScanData":
+        """A range image (include/vofod.h): no point columns, only the sensor's uint32 millimetres (`width * height` of them at
+        `stride_bytes`, pixel order of the handle's LUT); the product library rebuilds the points on the device."""
+        return cls(x=None, y=None, z=None, width=width, height=height, intensity=intensity, range=range, stride_bytes=stride_bytes, memspace=memspace, stamp=stamp)
+
     def as_c(self) -> capi.Scan:
         def p(a):
             if a is None:
@@ -315,6 +321,18 @@ class VoFOD:
 
     def sepclusters_finish(self, allow: Sequence[int] = ()):
         return self._check(self.lib.sepclusters_finish(self.h), "vofod_sepclusters_finish", allow)
+
+    def range_to_points(self, scan: ScanData, out=None, allow: Sequence[int] = ()):
+        """The points of a range image as the hot path decodes them (vofod_range_to_points): three float32 arrays of w*h values,
+        or - with `out` = three device addresses - written to device memory (returns None)."""
+        cs = scan.as_c()
+        n = scan.width * scan.height
+        if out is not None:
+            self._check(self.lib.range_to_points(self.h, C.byref(cs), *(C.c_void_p(int(a)) for a in out), capi.MEM_DEVICE), "vofod_range_to_points", allow)
+            return None
+        xyz = [np.full(n, np.nan, dtype=np.float32) for _ in range(3)]
+        self._check(self.lib.range_to_points(self.h, C.byref(cs), *(capi.ptr(a) for a in xyz), capi.MEM_HOST), "vofod_range_to_points", allow)
+        return tuple(xyz)
 
     # ------------------------------------------------- stateless L4 helpers
     def voxel_grid_weighted(self, x, y, z, leaf: float, align_center=None):
