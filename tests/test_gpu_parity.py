@@ -277,9 +277,12 @@ def test_sensor_stream_with_auto_raycast(oracle, hip):
 
 
 def test_single_scans_with_more_detections_than_record_slots(oracle, hip):
-    """A map-updating scan whose flood fills find more floating clusters than the device tail has record slots (16 per frame):
-    the fills have already written their frontiers to the map, so the detections are rebuilt from the clusters and explore
-    results still on the device - ids, points, positions, confidences and the map equal the oracle's, scan after scan."""
+    """Map-updating scans of a swarm: 33 to 46 detections per scan, more than the device tail has record slots (16 per frame) - but
+    also 80 to 133 candidate clusters (counted on the oracle's debug view of the three scans), more than its 64 lanes.  The
+    cluster count is noticed first, before any fill has run: TAIL_FB_CLUSTERS, and the host tail redoes the scan.  So this test
+    holds the host tail behind k_tail_far to the oracle - ids, points, positions, confidences and the map, scan after scan; it
+    never enters device_tail_overflow_records (the rebuild of the records after the fills have written the map), which
+    test_gpu_tail_edges.py::test_detections_at_the_record_slots[17-scan] reaches with 23 candidates and asserts by kernel list."""
     ref, dev = make_pair(oracle, hip, "os1-128", 0.5)
     warm_scene = synth.make_scene(5, n_targets=0)
     scene = synth.make_scene(5, n_targets=160)  # same buildings (drawn first from the seed) + a swarm
