@@ -23,6 +23,11 @@
 //               D-E the clustering phases on the same bitmap / words (probe, octant test, exact test
 //                  across components only, LDS union-find, component minima, statistics, labels, cluster table).
 // A frame beyond the LDS capacities raises CCL_RETRY_STATUS: the host re-runs that batch on the general kernels.
+// Round 11, lean emission: a production batch (close first, tables written here, no debug output) reads the voxel records of the
+// candidates' members only - voxels of pure-far bricks.  The host then passes `lean`: step 4 stores the records of the pure-far
+// bricks alone (same record, same rank) - with FR_LEAN_WEIGHTS step 3's weights are counted for those bricks alone, too; ranks, V
+// and the capacity checks stay those of the whole frame.  The far-only debug view reads the whole cloud and keeps the full emission, as does every
+// launch under VOFOD_LEAN_EMIT=0 (read on every call, like the other switches).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,6 +67,11 @@ constexpr int CF_MAX = FR_THREADS;                 // close-first clustering: pu
 #define CF_G_DEF 4
 #endif
 constexpr int CF_G = CF_G_DEF;                     // bricks per thread whose map lookups are in flight together (close-first, first part)
+#ifndef FR_LEAN_WEIGHTS_DEF
+#define FR_LEAN_WEIGHTS_DEF 0
+#endif
+constexpr bool FR_LEAN_WEIGHTS = FR_LEAN_WEIGHTS_DEF != 0;  // 1 (not measured yet, hence off): close-first builds the pure-far list in FRONT of the counting pass 3b, which a lean launch then runs for its bricks only
+constexpr uint16_t FR_VBASE_NONE = 0xffffu;        // lean emission: "not counted" in place of a node's first voxel index
 constexpr uint32_t CF_LABEL_NONE = 0xffffffffu;    // label of a voxel outside the far clusters in the far-only debug view
 
 // per-frame scratch in global memory (L2-resident: touched sparsely)
@@ -343,7 +353,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
                                                          const MapGeom mg, const unsigned long long* __restrict__ mapclose, const unsigned long long* __restrict__ mapbits,
                                                          const CloseRow* __restrict__ crows, int n_crows, const UpdateParams up, ClusterRec* __restrict__ table_all,
                                                          CandMember* __restrict__ cand_all, int write_tables, unsigned long long* __restrict__ prof, const RefLattice rl, const FrameArgs* __restrict__ args,
-                                                         int close_first)
+                                                         int close_first, int lean)
 {
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) unsigned long long s_bb[FR_BB64];  // brick-lattice bitmap (bit = linear brick id) + exclusive popcount prefix per
@@ -965,9 +975,186 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   }
   __syncthreads();
   FR_STAMP(3);
+  // ---- close first (round 4).  The reference only ever uses the FAR clusters (findCloseFarClusters, vofod_nodelet.cpp:727-748:
+  // a cluster is close as soon as ONE member has a background voxel within hasCloseTo's stencil; close clusters feed nothing
+  // but a per-voxel map update, :946) - and on a warmed map the ground sheet and the buildings, one giant close component, are
+  // > 95 % of a frame.  The dilated map image answers hasCloseTo for a voxel with one bit, and a 4x4x4 brick is a clique under
+  // the tolerance (brick-level clustering is only planned then), so:
+  //   * a brick that holds a close voxel belongs to a close cluster as a whole;
+  //   * a far cluster is a connected component of bricks WITHOUT any close voxel ("pure-far" bricks) that has no edge to a
+  //     brick with one: walk from any of its voxels towards a close voxel - the last far voxel on the way has that edge.
+  // Here: which bricks are pure far (one lookup of the dilated image per occupied lattice row of a brick, until the first hit).
+  // Behind the emission: edges and unions around those few bricks only (tens to hundreds per frame instead of ~5 000).
+  // Same member lists, sizes, smallest members, hence the same candidates and detections as the full clustering; that one
+  // stays for the debug view of ALL clusters and for a frame with more than CF_MAX pure-far bricks (a cold map).
+  // Lean emission (round 11): a production batch (close_first == 1 with the tables written here) reads the voxel records of the
+  // candidates' members only, and those are voxels of pure-far bricks.  `lean` (wave-uniform, set by the host exactly then)
+  // restricts pass d - and with it the weights: the counting pass 3b, the extras - to the bricks of the pure-far list: the same
+  // records at the same ranks, the others are not written.  Ranks, V and every capacity check stay those of the whole frame.
+  // FR_LEAN_WEIGHTS: the list is built BEFORE the counting pass, which then skips every code of another brick; without it the
+  // counting pass stays as it was and the nodes outside the list are marked behind it, for the extras pass.
+  constexpr bool cf = CFM != 0;
+  const bool lean_on = cf && lean != 0;
+  const bool lean_cnt = lean_on && FR_LEAN_WEIGHTS;  // the counting pass is lean too
+  auto closebits = [&]() -> bool {
+    if constexpr (cf)
+    {
+      {
+        constexpr int NPT = LB_MAX / FR_THREADS;
+        const bool mapk_ok = s_mapk[3] != 0;
+        const int K0 = s_mapk[0], K1 = s_mapk[1], K2 = s_mapk[2];
+        // one voxel by itself (a brick that leaves the map, or a lattice that is no translate of the map's): as phase E; (k0, k1, k2): REFERENCE cell
+        auto voxel_close = [&](int k0, int k1, int k2) -> bool {
+          int mx_, my_, mz_;
+          if (mapk_ok)
+          {
+            mx_ = k0 + K0;
+            my_ = k1 + K1;
+            mz_ = k2 + K2;
+          }
+          else
+          {
+            const float cx = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(k0 + o0), 0.5f), g.leaf[0]), hoff0);
+            const float cy = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(k1 + o1), 0.5f), g.leaf[1]), hoff1);
+            const float cz = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(k2 + o2), 0.5f), g.leaf[2]), hoff2);
+            mx_ = static_cast<int>(floorf(__fmul_rn(__fsub_rn(cx, mg.off[0]), mg.vs_inv)));
+            my_ = static_cast<int>(floorf(__fmul_rn(__fsub_rn(cy, mg.off[1]), mg.vs_inv)));
+            mz_ = static_cast<int>(floorf(__fmul_rn(__fsub_rn(cz, mg.off[2]), mg.vs_inv)));
+          }
+          if (mx_ >= 0 && mx_ < mg.sx && my_ >= 0 && my_ < mg.sy && mz_ >= 0 && mz_ < mg.sz)
+          {
+            const uint64_t L = (static_cast<uint64_t>(mz_) * mg.sy + my_) * mg.sx + mx_;
+            return ((mapclose[L >> 6] >> (L & 63)) & 1ull) != 0ull;
+          }
+          bool hit = false;  // a centre outside the map (a point on the far face of the operation area): the clipped stencil sweep
+          for (int rr = 0; rr < n_crows && !hit; rr++)
+            hit = close_row_hit(mg, mapbits, crows[rr], mx_, my_, mz_);
+          return hit;
+        };
+        // Rounds: every round looks up ONE occupied lattice row (4 cells along x: 4 bits of the image, fetched as the two bytes
+        // that hold them) of each of the thread's bricks that is still undecided - the lookups of a round are in flight
+        // together, CF_G bricks per thread at a time.  Consecutive lanes hold consecutive nodes, i.e. neighbouring bricks of a
+        // brick row: their lookups fall into the same lines of the image.
+        const unsigned char* mc8 = reinterpret_cast<const unsigned char*>(mapclose);
+  #pragma unroll
+        for (int g0 = 0; g0 < NPT; g0 += CF_G)
+        {
+          uint32_t rem[CF_G];  // bit r: lattice row r = yy + 4 zz of the brick is occupied and not looked up yet
+          uint32_t far_m = 0;  // bit j: the group's j-th brick has shown no close voxel so far
+  #pragma unroll
+          for (int j = 0; j < CF_G; j++)
+          {
+            const uint32_t i = (g0 + j) * FR_THREADS + tid;
+            rem[j] = 0u;
+            if (g0 + j < NPT && i < n)
+            {
+              unsigned long long t = s_word[i];
+              t |= t >> 1;
+              t |= t >> 2;
+              uint32_t lo = static_cast<uint32_t>(t) & 0x11111111u, hi = static_cast<uint32_t>(t >> 32) & 0x11111111u;
+              lo = (lo | (lo >> 3) | (lo >> 6) | (lo >> 9)) & 0x000f000fu;
+              hi = (hi | (hi >> 3) | (hi >> 6) | (hi >> 9)) & 0x000f000fu;
+              rem[j] = (lo & 0xfu) | (lo >> 12) | ((hi & 0xfu) << 8) | ((hi >> 4) & 0xf000u);
+              far_m |= 1u << j;
+            }
+          }
+          for (;;)
+          {
+            uint32_t val[CF_G], meta[CF_G];  // meta: nibble | shift << 4 | looked up << 8
+            bool any = false;
+  #pragma unroll
+            for (int j = 0; j < CF_G; j++)
+            {
+              val[j] = meta[j] = 0u;
+              if (!rem[j])
+                continue;
+              any = true;
+              const uint32_t i = (g0 + j) * FR_THREADS + tid;
+              const int row = __ffs(static_cast<int>(rem[j])) - 1;
+              rem[j] &= rem[j] - 1u;
+              const uint32_t xyz = s_xyz[i];
+              const uint32_t nib = static_cast<uint32_t>(s_word[i] >> (4 * row)) & 0xfu;
+              const int k0 = 4 * fr_bx(xyz), k1 = 4 * fr_by(xyz) + (row & 3), k2 = 4 * fr_bz(xyz) + (row >> 2);
+              const int mx0 = k0 + K0, my_ = k1 + K1, mz_ = k2 + K2;
+              if (mapk_ok && mx0 >= 0 && mx0 + 3 < mg.sx && my_ >= 0 && my_ < mg.sy && mz_ >= 0 && mz_ < mg.sz)
+              {
+                const uint64_t L = (static_cast<uint64_t>(mz_) * mg.sy + my_) * mg.sx + mx0;
+                meta[j] = nib | (static_cast<uint32_t>(L & 7u) << 4) | 0x100u;
+                const unsigned char* q = mc8 + (L >> 3);  // (the image ends with two guard words)
+                val[j] = static_cast<uint32_t>(q[0]) | (static_cast<uint32_t>(q[1]) << 8);
+              }
+              else
+              {
+                bool hit = false;
+                for (int xx = 0; xx < 4 && !hit; xx++)
+                  if ((nib >> xx) & 1u)
+                    hit = voxel_close(k0 + xx, k1, k2);
+                if (hit)
+                {
+                  rem[j] = 0u;
+                  far_m &= ~(1u << j);
+                }
+              }
+            }
+            if (!any)
+              break;
+  #pragma unroll
+            for (int j = 0; j < CF_G; j++)
+              if ((meta[j] & 0x100u) && ((val[j] >> ((meta[j] >> 4) & 7u)) & meta[j] & 0xfu))
+              {
+                rem[j] = 0u;
+                far_m &= ~(1u << j);
+              }
+          }
+  #pragma unroll
+          for (int j = 0; j < CF_G; j++)
+          {
+            const bool pf = (far_m >> j) & 1u;
+            if (lean_on)
+            {
+              // lean emission: a node outside the pure-far list is marked "not counted" where its first voxel's index lives (V <= 65 535:
+              // no index is 0xffff); with the counting pass still ahead (FR_LEAN_WEIGHTS) the listed nodes are marked too - as counted
+              const uint32_t i = (g0 + j) * FR_THREADS + tid;
+              if (g0 + j < NPT && i < n && (FR_LEAN_WEIGHTS || !pf))
+                s_vbase[i] = pf ? static_cast<uint16_t>(0u) : FR_VBASE_NONE;
+            }
+            const unsigned long long m = __ballot(pf);
+            if (!m)
+              continue;
+            const int leader = __ffsll(static_cast<long long>(m)) - 1;
+            uint32_t base = 0;
+            if (lane == leader)
+              base = atomicAdd(&s_npf, static_cast<uint32_t>(__popcll(m)));
+            base = __builtin_amdgcn_readlane(base, leader);
+            const uint32_t pos = base + __popcll(m & ((1ull << lane) - 1ull));
+            if (pf && pos < static_cast<uint32_t>(CF_MAX))
+              s_pf[pos] = static_cast<uint16_t>((g0 + j) * FR_THREADS + tid);
+          }
+        }
+        __syncthreads();
+        if (s_npf > static_cast<uint32_t>(CF_MAX))
+        {
+          if (tid == 0)
+          {
+            h.status = CF_RETRY_STATUS;  // (a cold map: nearly every brick is pure far) the batch takes the full clustering
+            h.n_bricks = s_npf;
+            h.V = 0;
+          }
+          return false;
+        }
+      }
+    }
+    return true;
+  };
+  if constexpr (cf && FR_LEAN_WEIGHTS)
+  {
+    if (!closebits())
+      return;
+    FR_STAMP(15);
+  }
   // ---- 3b: weights (voxel_grid_weighted.cpp:181).  The bitmap is parked in global memory; its LDS becomes one byte
   // counter per voxel, indexed in brick order: first voxel of the node + set bits below.  Consecutive equal codes of a
-  // thread add once.  A counter that would pass 255 is undone and the points go to the frame's record list
+  // thread add once.  Points that would take a counter past 255 go to the frame's record list instead
   // (node * 64 + bit | (points - 1) << 25), added to the stored weights after the emission.
   uint32_t V = 0;
   {
@@ -975,24 +1162,29 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     for (int i = tid; i < FR_BB64 / 2; i += FR_THREADS)
       bsave[i] = reinterpret_cast<const ulonglong2*>(s_bb)[i];
     constexpr int NPT = LB_MAX / FR_THREADS;  // consecutive nodes per thread
+    // (two sums in one scan: all voxels << 16 | voxels that get a counter - a wave holds at most 64 * NPT * 64 < 65 536 of either.  They
+    // differ only in a lean launch behind FR_LEAN_WEIGHTS: V stays the frame's, the counters cover the pure-far bricks.)
+    static_assert(64 * NPT * 64 < 65536, "the packed sums of a wave");
     uint32_t pc[NPT], sum = 0;
 #pragma unroll
     for (int r = 0; r < NPT; r++)
     {
       const uint32_t i = tid * NPT + r;
-      pc[r] = i < n ? __popcll(s_word[i]) : 0u;
-      sum += pc[r];
+      const uint32_t c = i < n ? __popcll(s_word[i]) : 0u;
+      pc[r] = (lean_cnt && i < n && s_vbase[i] == FR_VBASE_NONE) ? 0u : c;
+      sum += (c << 16) | pc[r];
     }
     const uint32_t incl = wave_incl_scan(sum);
     if (lane == 63)
       s_wsum[wave] = incl;
     __syncthreads();  // (also: every thread has parked its part of the bitmap)
-    uint32_t run = incl - sum;
+    uint32_t run = (incl - sum) & 0xffffu, Vc = 0;  // Vc: voxels with a counter
     for (int w = 0; w < FR_THREADS / 64; w++)
     {
       const uint32_t x = s_wsum[w];
-      run += w < wave ? x : 0u;
-      V += x;
+      run += w < wave ? x & 0xffffu : 0u;
+      V += x >> 16;
+      Vc += x & 0xffffu;
     }
     if (V > g.vox_cap)
     {
@@ -1016,24 +1208,38 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     for (int r = 0; r < NPT; r++)
     {
       const uint32_t i = tid * NPT + r;
-      if (i < n)
+      if (i < n && !(lean_cnt && pc[r] == 0u))  // (a brick has a voxel: only a node marked "not counted" has none to count)
         s_vbase[i] = static_cast<uint16_t>(run);
       run += pc[r];
     }
-    for (uint32_t i = tid; i < (V + 15u) / 16u; i += FR_THREADS)
+    for (uint32_t i = tid; i < (Vc + 15u) / 16u; i += FR_THREADS)
       reinterpret_cast<uint4*>(s_bb)[i] = make_uint4(0u, 0u, 0u, 0u);
   }
   __syncthreads();
   {
     auto count = [&](uint32_t code, uint32_t add) {
       const uint32_t node = code >> 6, bit = code & 63u;
-      const uint32_t idx = s_vbase[node] + __popcll(s_word[node] & ((1ull << bit) - 1ull));
+      const uint32_t vb = s_vbase[node];
+      if (lean_cnt && vb == FR_VBASE_NONE)
+        return;  // lean: no record of this brick leaves, nothing reads its weights
+      const uint32_t idx = vb + __popcll(s_word[node] & ((1ull << bit) - 1ull));
       const uint32_t sh = 8u * (idx & 3u);
-      const uint32_t old = atomicAdd(&s_cnt32[idx >> 2], add << sh);
-      if (((old >> sh) & 0xffu) + add > 255u)
+      // The byte never passes 255, not even for a moment: compare-and-swap, and the points that do not fit go to the record list.
+      // (Until round 11 this was an add that was taken back on overflow: between the two the byte had WRAPPED, carrying into the
+      // next voxel's counter, and another lane adding to the same voxel in that window saw a small counter and stayed - 300 points
+      // in one voxel, 16 per lane, left 44 there and one too many next door; tests/test_gpu_lean_emit.py, counters beyond 255.)
+      uint32_t cur = __atomic_load_n(&s_cnt32[idx >> 2], __ATOMIC_RELAXED);
+      for (;;)
       {
-        atomicSub(&s_cnt32[idx >> 2], add << sh);
-        extras_g[atomicAdd(&s_ne, 1u)] = code | ((add - 1u) << 25);  // at most one record per point: the list holds pt_cap entries
+        if (((cur >> sh) & 0xffu) + add > 255u)
+        {
+          extras_g[atomicAdd(&s_ne, 1u)] = code | ((add - 1u) << 25);  // at most one record per point: the list holds pt_cap entries
+          break;
+        }
+        const uint32_t seen = atomicCAS(&s_cnt32[idx >> 2], cur, cur + (add << sh));
+        if (seen == cur)
+          break;
+        cur = seen;
       }
     };
     auto count_round = [&](const uint32_t (&c)[KPT]) {
@@ -1074,158 +1280,11 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     }
   }
   __syncthreads();
-  FR_STAMP(15);
-  // ---- close first (round 4).  The reference only ever uses the FAR clusters (findCloseFarClusters, vofod_nodelet.cpp:727-748:
-  // a cluster is close as soon as ONE member has a background voxel within hasCloseTo's stencil; close clusters feed nothing
-  // but a per-voxel map update, :946) - and on a warmed map the ground sheet and the buildings, one giant close component, are
-  // > 95 % of a frame.  The dilated map image answers hasCloseTo for a voxel with one bit, and a 4x4x4 brick is a clique under
-  // the tolerance (brick-level clustering is only planned then), so:
-  //   * a brick that holds a close voxel belongs to a close cluster as a whole;
-  //   * a far cluster is a connected component of bricks WITHOUT any close voxel ("pure-far" bricks) that has no edge to a
-  //     brick with one: walk from any of its voxels towards a close voxel - the last far voxel on the way has that edge.
-  // Here: which bricks are pure far (one lookup of the dilated image per occupied lattice row of a brick, until the first hit).
-  // Behind the emission: edges and unions around those few bricks only (tens to hundreds per frame instead of ~5 000).
-  // Same member lists, sizes, smallest members, hence the same candidates and detections as the full clustering; that one
-  // stays for the debug view of ALL clusters and for a frame with more than CF_MAX pure-far bricks (a cold map).
-  constexpr bool cf = CFM != 0;
-  if constexpr (cf)
+  if constexpr (!(cf && FR_LEAN_WEIGHTS))
   {
-    {
-      constexpr int NPT = LB_MAX / FR_THREADS;
-      const bool mapk_ok = s_mapk[3] != 0;
-      const int K0 = s_mapk[0], K1 = s_mapk[1], K2 = s_mapk[2];
-      // one voxel by itself (a brick that leaves the map, or a lattice that is no translate of the map's): as phase E; (k0, k1, k2): REFERENCE cell
-      auto voxel_close = [&](int k0, int k1, int k2) -> bool {
-        int mx_, my_, mz_;
-        if (mapk_ok)
-        {
-          mx_ = k0 + K0;
-          my_ = k1 + K1;
-          mz_ = k2 + K2;
-        }
-        else
-        {
-          const float cx = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(k0 + o0), 0.5f), g.leaf[0]), hoff0);
-          const float cy = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(k1 + o1), 0.5f), g.leaf[1]), hoff1);
-          const float cz = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(k2 + o2), 0.5f), g.leaf[2]), hoff2);
-          mx_ = static_cast<int>(floorf(__fmul_rn(__fsub_rn(cx, mg.off[0]), mg.vs_inv)));
-          my_ = static_cast<int>(floorf(__fmul_rn(__fsub_rn(cy, mg.off[1]), mg.vs_inv)));
-          mz_ = static_cast<int>(floorf(__fmul_rn(__fsub_rn(cz, mg.off[2]), mg.vs_inv)));
-        }
-        if (mx_ >= 0 && mx_ < mg.sx && my_ >= 0 && my_ < mg.sy && mz_ >= 0 && mz_ < mg.sz)
-        {
-          const uint64_t L = (static_cast<uint64_t>(mz_) * mg.sy + my_) * mg.sx + mx_;
-          return ((mapclose[L >> 6] >> (L & 63)) & 1ull) != 0ull;
-        }
-        bool hit = false;  // a centre outside the map (a point on the far face of the operation area): the clipped stencil sweep
-        for (int rr = 0; rr < n_crows && !hit; rr++)
-          hit = close_row_hit(mg, mapbits, crows[rr], mx_, my_, mz_);
-        return hit;
-      };
-      // Rounds: every round looks up ONE occupied lattice row (4 cells along x: 4 bits of the image, fetched as the two bytes
-      // that hold them) of each of the thread's bricks that is still undecided - the lookups of a round are in flight
-      // together, CF_G bricks per thread at a time.  Consecutive lanes hold consecutive nodes, i.e. neighbouring bricks of a
-      // brick row: their lookups fall into the same lines of the image.
-      const unsigned char* mc8 = reinterpret_cast<const unsigned char*>(mapclose);
-#pragma unroll
-      for (int g0 = 0; g0 < NPT; g0 += CF_G)
-      {
-        uint32_t rem[CF_G];  // bit r: lattice row r = yy + 4 zz of the brick is occupied and not looked up yet
-        uint32_t far_m = 0;  // bit j: the group's j-th brick has shown no close voxel so far
-#pragma unroll
-        for (int j = 0; j < CF_G; j++)
-        {
-          const uint32_t i = (g0 + j) * FR_THREADS + tid;
-          rem[j] = 0u;
-          if (g0 + j < NPT && i < n)
-          {
-            unsigned long long t = s_word[i];
-            t |= t >> 1;
-            t |= t >> 2;
-            uint32_t lo = static_cast<uint32_t>(t) & 0x11111111u, hi = static_cast<uint32_t>(t >> 32) & 0x11111111u;
-            lo = (lo | (lo >> 3) | (lo >> 6) | (lo >> 9)) & 0x000f000fu;
-            hi = (hi | (hi >> 3) | (hi >> 6) | (hi >> 9)) & 0x000f000fu;
-            rem[j] = (lo & 0xfu) | (lo >> 12) | ((hi & 0xfu) << 8) | ((hi >> 4) & 0xf000u);
-            far_m |= 1u << j;
-          }
-        }
-        for (;;)
-        {
-          uint32_t val[CF_G], meta[CF_G];  // meta: nibble | shift << 4 | looked up << 8
-          bool any = false;
-#pragma unroll
-          for (int j = 0; j < CF_G; j++)
-          {
-            val[j] = meta[j] = 0u;
-            if (!rem[j])
-              continue;
-            any = true;
-            const uint32_t i = (g0 + j) * FR_THREADS + tid;
-            const int row = __ffs(static_cast<int>(rem[j])) - 1;
-            rem[j] &= rem[j] - 1u;
-            const uint32_t xyz = s_xyz[i];
-            const uint32_t nib = static_cast<uint32_t>(s_word[i] >> (4 * row)) & 0xfu;
-            const int k0 = 4 * fr_bx(xyz), k1 = 4 * fr_by(xyz) + (row & 3), k2 = 4 * fr_bz(xyz) + (row >> 2);
-            const int mx0 = k0 + K0, my_ = k1 + K1, mz_ = k2 + K2;
-            if (mapk_ok && mx0 >= 0 && mx0 + 3 < mg.sx && my_ >= 0 && my_ < mg.sy && mz_ >= 0 && mz_ < mg.sz)
-            {
-              const uint64_t L = (static_cast<uint64_t>(mz_) * mg.sy + my_) * mg.sx + mx0;
-              meta[j] = nib | (static_cast<uint32_t>(L & 7u) << 4) | 0x100u;
-              const unsigned char* q = mc8 + (L >> 3);  // (the image ends with two guard words)
-              val[j] = static_cast<uint32_t>(q[0]) | (static_cast<uint32_t>(q[1]) << 8);
-            }
-            else
-            {
-              bool hit = false;
-              for (int xx = 0; xx < 4 && !hit; xx++)
-                if ((nib >> xx) & 1u)
-                  hit = voxel_close(k0 + xx, k1, k2);
-              if (hit)
-              {
-                rem[j] = 0u;
-                far_m &= ~(1u << j);
-              }
-            }
-          }
-          if (!any)
-            break;
-#pragma unroll
-          for (int j = 0; j < CF_G; j++)
-            if ((meta[j] & 0x100u) && ((val[j] >> ((meta[j] >> 4) & 7u)) & meta[j] & 0xfu))
-            {
-              rem[j] = 0u;
-              far_m &= ~(1u << j);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < CF_G; j++)
-        {
-          const bool pf = (far_m >> j) & 1u;
-          const unsigned long long m = __ballot(pf);
-          if (!m)
-            continue;
-          const int leader = __ffsll(static_cast<long long>(m)) - 1;
-          uint32_t base = 0;
-          if (lane == leader)
-            base = atomicAdd(&s_npf, static_cast<uint32_t>(__popcll(m)));
-          base = __builtin_amdgcn_readlane(base, leader);
-          const uint32_t pos = base + __popcll(m & ((1ull << lane) - 1ull));
-          if (pf && pos < static_cast<uint32_t>(CF_MAX))
-            s_pf[pos] = static_cast<uint16_t>((g0 + j) * FR_THREADS + tid);
-        }
-      }
-      __syncthreads();
-      if (s_npf > static_cast<uint32_t>(CF_MAX))
-      {
-        if (tid == 0)
-        {
-          h.status = CF_RETRY_STATUS;  // (a cold map: nearly every brick is pure far) the batch takes the full clustering
-          h.n_bricks = s_npf;
-          h.V = 0;
-        }
-        return;
-      }
-    }
+    FR_STAMP(15);
+    if (!closebits())
+      return;
   }
   FR_STAMP(14);
   // ---- 4: ranks in key order.  Pass a: one segmented scan per 64-node chunk; the per-node channel prefixes go to the
@@ -1450,8 +1509,11 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   };
   // Pass d: the voxel records leave at their ranks (voxel_grid_weighted.cpp:171-188): centre, weight 1 (+ extras below),
   // node of the brick (for the label pass); the lattice key only for the general kernels that may follow (!write_tables).
-  for (uint32_t i = tid; i < n; i += FR_THREADS)
+  // Lean: the bricks of the pure-far list only (in list order: every record has its own place).
+  const uint32_t n_emit = lean_on ? s_npf : n;
+  for (uint32_t e = tid; e < n_emit; e += FR_THREADS)
   {
+    const uint32_t i = lean_on ? static_cast<uint32_t>(s_pf[e]) : e;
     const uint32_t xyz = s_xyz[i];
     const uint32_t row = fr_row(xyz, nby);
     const unsigned long long W = s_word[i];
@@ -1542,6 +1604,8 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       {
         if (rec[u] == FR_CODE_NONE)
           continue;
+        if (lean_on && s_vbase[node[u]] == FR_VBASE_NONE)
+          continue;  // lean: the record of this voxel was not written
         const uint32_t add = (rec[u] >> 25) + 1u, p = rec[u] & 63u;
         const uint32_t zz = p >> 4, yy = (p >> 2) & 3u, xx = p & 3u;
         unsigned long long Mz = fr_excl16(tz[u]) + (az[u] & ~FR_BEGAN);

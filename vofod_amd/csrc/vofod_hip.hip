@@ -1401,10 +1401,12 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
     {
       // a close-first frame: its own phases behind the emission
       auto us = [&](int a, int b) { return (t[32 * f + b] - t[32 * f + a]) * 0.01; };
+      // (stamps 3 -> 15 -> 14: counting pass and closebits, in the order the kernel runs them)
+      const double t_count = FR_LEAN_WEIGHTS ? us(15, 14) : us(3, 15), t_closebits = FR_LEAN_WEIGHTS ? us(3, 15) : us(15, 14);
       std::fprintf(stderr,
                    "[k_frame_lds_far] frame %u: %.1f us | keys %llu V %llu bricks %llu pure-far bricks %llu far clusters %llu candidate members %llu | input+fragile %.1f prefix %.1f words %.1f count %.1f closebits "
                    "%.1f rank-a/b %.1f rank-c %.1f emit %.1f extras %.1f near+far %.1f open %.1f stats %.1f table %.1f members %.1f\n",
-                   f, byd[q].first, t[32 * f + 27], t[32 * f + 29], t[32 * f + 26], t[32 * f + 24], t[32 * f + 25], t[32 * f + 30], us(0, 1), us(1, 2), us(2, 3), us(3, 15), us(15, 14), us(14, 4), us(4, 5),
+                   f, byd[q].first, t[32 * f + 27], t[32 * f + 29], t[32 * f + 26], t[32 * f + 24], t[32 * f + 25], t[32 * f + 30], us(0, 1), us(1, 2), us(2, 3), t_count, t_closebits, us(14, 4), us(4, 5),
                    us(5, 6), us(6, 7), us(7, 8), us(8, 9), us(9, 10), us(10, 11), us(11, 13));
       continue;
     }
@@ -1421,7 +1423,8 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
   // frames, us), one JSON object per launch appended to the file - profiles/r05_frame_phases.json is made of these
   if (const char* jf = std::getenv("VOFOD_LDS_PROF_JSON"); jf && !byd.empty() && t[32 * byd[0].second + 31] == ~0ull)
   {
-    static const int cuts[][2] = {{0, 16}, {16, 17}, {17, 18}, {18, 19}, {19, 20}, {20, 1}, {1, 2}, {2, 3}, {3, 15}, {15, 14}, {14, 4}, {4, 5}, {5, 6}, {6, 7}, {7, 8}, {8, 9}, {9, 10}, {10, 11}, {11, 13}, {0, 13}};
+    // ("count" and "closebits" keep their names whichever runs first: FR_LEAN_WEIGHTS puts closebits in front)
+    static const int cuts[][2] = {{0, 16}, {16, 17}, {17, 18}, {18, 19}, {19, 20}, {20, 1}, {1, 2}, {2, 3}, {FR_LEAN_WEIGHTS ? 15 : 3, FR_LEAN_WEIGHTS ? 14 : 15}, {FR_LEAN_WEIGHTS ? 3 : 15, FR_LEAN_WEIGHTS ? 15 : 14}, {14, 4}, {4, 5}, {5, 6}, {6, 7}, {7, 8}, {8, 9}, {9, 10}, {10, 11}, {11, 13}, {0, 13}};
     static const char* cnames[] = {"input", "input_wait", "grid", "grid_wait", "fragile", "fragile_wait", "prefix", "words", "count", "closebits", "rank_ab", "rank_c", "emit", "extras_restore", "cf_edges", "cf_open", "cf_stats", "cf_table", "cf_members", "total"};
     if (FILE* fp = std::fopen(jf, "a"))
     {
@@ -1532,23 +1535,27 @@ int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridPa
         lf.far_ran = up_tables && mapclose && ws.close_first;
         // (four instantiations: close first or not, packed 16-byte column loads or strided ones; the profile names the algorithmic
         // variant, k_frame_lds_far / k_frame_lds_full, and the strided input pass by the suffix _strided)
-#define VOFOD_FRAME_LAUNCH(label, kern, UP, WT, CF)                                                                                                                                          \
+#define VOFOD_FRAME_LAUNCH(label, kern, UP, WT, CF, LEAN)                                                                                                                                         \
   KLAUNCH_AS(h, label, kern, dim3(n), dim3(FR_THREADS), g, bp, ct->d_lbtab, ws.d_hdrs, ws.sa, ws.pt_cap, ws.va, ws.d_labels, lb_limit, reinterpret_cast<uint32_t*>(ws.d_table.p), ws.fs, h->mg, mapclose, \
-          h->d_mapbits, h->d_crows, h->closetab.n_rows, UP, ws.d_table, ws.d_cand, WT, d_prof, lf.ref_lattice, ws.d_args, CF)
+          h->d_mapbits, h->d_crows, h->closetab.n_rows, UP, ws.d_table, ws.d_cand, WT, d_prof, lf.ref_lattice, ws.d_args, CF, LEAN)
         const UpdateParams up_none{};
         if (lf.far_ran)  // read-only batches: cluster the far voxels only (the close-first instantiation)
         {
+          // Lean emission: a production batch reads the voxel records of the candidates' members only - voxels of pure-far bricks -,
+          // so the kernel writes (and, built with FR_LEAN_WEIGHTS, counts the points of) those bricks' voxels alone.  The far-only debug view reads the whole
+          // cloud and keeps the full emission; VOFOD_LEAN_EMIT=0 keeps it everywhere.
+          const int lean = (ws.close_first == 1 && !switch_off("VOFOD_LEAN_EMIT")) ? 1 : 0;
           if (lf.in_packed)
-            VOFOD_FRAME_LAUNCH("k_frame_lds_far", k_frame_lds_far_p, *up_tables, 1, ws.close_first);
+            VOFOD_FRAME_LAUNCH("k_frame_lds_far", k_frame_lds_far_p, *up_tables, 1, ws.close_first, lean);
           else
-            VOFOD_FRAME_LAUNCH("k_frame_lds_far_strided", k_frame_lds_far, *up_tables, 1, ws.close_first);
+            VOFOD_FRAME_LAUNCH("k_frame_lds_far_strided", k_frame_lds_far, *up_tables, 1, ws.close_first, lean);
         }
         else
         {
           if (lf.in_packed)
-            VOFOD_FRAME_LAUNCH("k_frame_lds_full", k_frame_lds_full_p, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0);
+            VOFOD_FRAME_LAUNCH("k_frame_lds_full", k_frame_lds_full_p, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0, 0);
           else
-            VOFOD_FRAME_LAUNCH("k_frame_lds_full_strided", k_frame_lds_full, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0);
+            VOFOD_FRAME_LAUNCH("k_frame_lds_full_strided", k_frame_lds_full, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0, 0);
         }
 #undef VOFOD_FRAME_LAUNCH
         lf.finalize_fused = up_tables && mapclose;
