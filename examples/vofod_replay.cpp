@@ -73,7 +73,7 @@ struct Cloud
 
 int main(int argc, char** argv)
 {
-  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0;
+  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0;
   float voxel = 0.5f;
   std::string apriori;
   for (int i = 1; i + 1 < argc; i += 2)
@@ -91,6 +91,8 @@ int main(int argc, char** argv)
       apriori = argv[i + 1];
     else if (k == "--period-ms")
       period_ms = std::atoi(argv[i + 1]);
+    else if (k == "--extents")  // 1: after each scan, the member count and the AABB of every detection (vofod_detection_points)
+      extents = std::atoi(argv[i + 1]);
   }
   const float vfov = 45.0f * 3.14159265f / 180.0f;
   vofod_static_params sp;
@@ -209,6 +211,25 @@ int main(int argc, char** argv)
       std::fprintf(stderr, "process_scan: status %d (%s)\n", st, vofod_last_error_string(h));
       stop = true;
       break;
+    }
+    if (extents && n_det)
+    {
+      // what detection_t::aabb and cluster_t::pc hold in the nodelet (:110-130): asked for before anything else takes the workspace
+      size_t n_ext = 0, n_pts = 0;
+      if (vofod_detection_points(h, VOFOD_POINTS_SYNC, nullptr, 0, &n_ext, nullptr, nullptr, 0, &n_pts, VOFOD_MEM_HOST) == VOFOD_OK)
+      {
+        std::vector<vofod_detection_extent> ext(n_ext);
+        std::vector<vofod_point_xyzr> pts(n_pts);
+        if (vofod_detection_points(h, VOFOD_POINTS_SYNC, ext.data(), n_ext, &n_ext, pts.data(), nullptr, n_pts, &n_pts, VOFOD_MEM_HOST) == VOFOD_OK)
+          for (const vofod_detection_extent& e : ext)
+          {
+            uint64_t hits = 0;
+            for (uint32_t i = e.first; i < e.first + e.count; i++)
+              hits += pts[i].range;
+            std::printf("scan %3d detection id %u extent: %u voxels (%llu returns), aabb (%.2f, %.2f, %.2f) - (%.2f, %.2f, %.2f)\n", k, e.id, e.count, static_cast<unsigned long long>(hits),
+                        e.aabb_min[0], e.aabb_min[1], e.aabb_min[2], e.aabb_max[0], e.aabb_max[1], e.aabb_max[2]);
+          }
+      }
     }
     detection_cv.notify_one();  // :951
     if (!raycast_running.exchange(true))  // :953-957

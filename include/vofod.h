@@ -418,6 +418,46 @@ int vofod_serialize_profiling_info(uint32_t stamp_sec, uint32_t stamp_nsec, uint
  * VOFOD_ERR_INVALID_ARG: `scan` is no range image; VOFOD_ERR_SIZE_MISMATCH: its width or height differ from the handle's. */
 int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, float* y, float* z, int32_t out_memspace);
 
+/* ------------------------------------------------- member voxels and AABB of the detections (product library only)
+ *
+ * What the reference keeps beside a detection's position: detection_t::aabb (vofod_nodelet.cpp:121-130) and the cluster's points
+ * cluster_t::pc / pc_indices (:110-119), for a tracker, a camera cue or a logger downstream.  Gathered on the device (k_det_points)
+ * from what the production paths leave in the workspace the frames ran in - no debug view, no read-back of the weighted cloud.
+ *
+ * source     VOFOD_POINTS_SYNC, or a ticket 0..7 whose vofod_batch_collect has returned its detections.
+ * ext        one record per detection, in the order of the detections returned; always host memory.
+ * points     the members of detection 0, then those of detection 1, and so on.  Within a detection they ascend by the member's
+ *            index in the frame's weighted cloud - the order of vofod_scan_debug::weighted and the order the labels of the debug
+ *            view define.  Each record is the voxel's record bit for bit: centre and weight.
+ * index      optional: that weighted-cloud index per point.
+ * points and index live in points_memspace: VOFOD_MEM_HOST, or VOFOD_MEM_DEVICE on the handle's device with 4-byte alignment.
+ *
+ * Size query: with ext == NULL && points == NULL the call sets *n_ext and *n_points, launches nothing and returns VOFOD_OK (both
+ * numbers are known on the host from the collected detections).  A NULL ext or a NULL points alone leaves that output out.
+ * VOFOD_ERR_CAPACITY: ext_cap or points_cap is too small; both counts are set and nothing is written to any buffer.
+ *
+ * Validity: the answer belongs to the workspace the frames ran in.  It is valid from the return of that collect, or of the
+ * synchronous call, until the next call on the handle that runs frames or stages inputs in the same workspace: ticket 0 shares its
+ * workspace with the synchronous entry points and with vofod_range_to_points; vofod_reset and vofod_map_apply end the validity of
+ * every source.  A call that did not return VOFOD_OK leaves nothing valid - in particular a collect that returned
+ * VOFOD_ERR_CAPACITY and left its ticket pending - and so does a vofod_process_batch of more frames than max_batch_frames (its
+ * launch groups overwrite each other).  The library tracks all this itself: when the source is not valid the call returns
+ * VOFOD_ERR_NOT_PENDING, never stale data.  VOFOD_ERR_INVALID_ARG: a source outside -1..7, a bad memspace or alignment, NULL
+ * count pointers, index without points.  VOFOD_ERR_DEVICE: a HIP error, or a cluster whose member list does not hold n_points
+ * entries (vofod_last_error_string names the detection).
+ * The call only reads the workspace and may run beside other batches in flight; it takes the handle's mutex like every call, runs
+ * on the workspace's own chain stream and waits for that stream only.  With zero detections there is no launch. */
+enum { VOFOD_POINTS_SYNC = -1 };   /* source: the last synchronous vofod_process_scan / vofod_process_batch */
+typedef struct vofod_detection_extent {   /* 40 bytes, one per detection, in the order of the detections returned */
+  uint32_t id, frame;          /* as in the vofod_detection it belongs to */
+  uint32_t first, count;       /* its members are points[first .. first + count); count == vofod_detection::n_points */
+  float aabb_min[3], aabb_max[3];   /* float min / max of the members' centres: cluster_t::aabb, getMinMax3D */
+} vofod_detection_extent;
+int vofod_detection_points(vofod_handle* h, int source,
+                           vofod_detection_extent* ext, size_t ext_cap, size_t* n_ext,
+                           vofod_point_xyzr* points, uint32_t* index /* nullable */, size_t points_cap, size_t* n_points,
+                           int32_t points_memspace);
+
 /* ------------------------------------------------- batched mode: the collective (product library only)
  *
  * one process per GPU runs vofod_process_batch / vofod_batch_submit+collect on its own block of frames; the only

@@ -66,6 +66,8 @@ sub = {
     "SHARE32_STATUS": f"**not met**: {k(s32['frames_per_s'])} frames/s (round 4: 246 k in the driver's line); `host_us_per_submit` / `_per_collect` are in the line now ({s32.get('host_us_per_submit', 0):.0f} / {s32.get('host_us_per_collect', 0):.0f} µs, the latter mostly waiting); one launch less per batch (`k_key1` gone); no graph replay, no multi-batch submit",
     "LOADED": f"{k(lt['frames_per_s'])} frames/s on this box (round 4: 494 k; 557-648 k over the round's boxes): workgroup-scope fences, eight frames per tail workgroup, fill loads issued together, member centres in LDS; the four-waves-per-frame tail of the verdict was not built",
 }
+# §5.9: which figures of profiles/r12_detection_points.txt were measured (its first line says so)
+sub["R12_STATUS"] = (P / "r12_detection_points.txt").read_text().splitlines()[0].removeprefix("status: ")
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

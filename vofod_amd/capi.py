@@ -37,6 +37,7 @@ MAP_VOXELS, MAP_FLAGS, MAP_RAYCAST = 0, 1, 2
 SCAN_DEFAULT, SCAN_NO_MAP_UPDATE, SCAN_AUTO_RAYCAST = 0, 1, 2
 CLASS_MAV, CLASS_UNKNOWN, CLASS_INVALID, CLASS_NONE = 0, 1, 2, -1
 SNAPSHOT_DELTA, SNAPSHOT_FULL = 0, 1
+POINTS_SYNC = -1
 MAPS_ALL = (1 << MAP_VOXELS) | (1 << MAP_FLAGS) | (1 << MAP_RAYCAST)
 
 
@@ -181,6 +182,20 @@ class GridDesc(C.Structure):
     ]
 
 
+class DetectionExtent(C.Structure):
+    _fields_ = [
+        ("id", C.c_uint32),
+        ("frame", C.c_uint32),
+        ("first", C.c_uint32),
+        ("count", C.c_uint32),
+        ("aabb_min", C.c_float * 3),
+        ("aabb_max", C.c_float * 3),
+    ]
+
+
+DETECTION_EXTENT = np.dtype([("id", "<u4"), ("frame", "<u4"), ("first", "<u4"), ("count", "<u4"), ("aabb_min", "<f4", 3), ("aabb_max", "<f4", 3)])
+assert DETECTION_EXTENT.itemsize == C.sizeof(DetectionExtent) == 40
+
 POINT_XYZR = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("range", "<u4")])
 DETECTION = np.dtype(
     [
@@ -272,12 +287,13 @@ _SIGS = {
     "map_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
     "broadcast_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_size_t)]),
     "range_to_points": (C.c_int, [C.c_void_p, _P(Scan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "detection_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_int32]),
 }
 
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
-                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points")
+                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points")
 
 
 class MsgHeader(C.Structure):

@@ -842,6 +842,8 @@ int vofod_reset(vofod_handle* h)
   h->background_pts_sufficient = false;
   h->last_detection_id = 0;
   h->cf_off = false;
+  for (int t = 0; t < vofod_handle::MAX_INFLIGHT; t++)
+    h->slot(t)->det_valid = false;  // (vofod_detection_points: the ids start again, nothing collected before answers any more)
   return r;
 }
 
@@ -1029,6 +1031,8 @@ int vofod_process_batch(vofod_handle* h, const vofod_scan* scans, const float* t
     if (r != VOFOD_OK)
       ret = r;
   }
+  if (n > h->ws.F)
+    h->ws.det_valid = false;  // (successive launch groups overwrite each other's lists: vofod_detection_points has nothing to answer from)
   *n_out = total;
   return ret;
 }
@@ -1143,6 +1147,86 @@ int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, flo
     HIPCHK(hipMemcpyAsync(out[c], ws.d_stage + static_cast<size_t>(c) * ws.pt_cap, npts * sizeof(float), out_memspace == VOFOD_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                           h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return VOFOD_OK;
+}
+
+int vofod_detection_points(vofod_handle* h, int source, vofod_detection_extent* ext, size_t ext_cap, size_t* n_ext, vofod_point_xyzr* points, uint32_t* index, size_t points_cap, size_t* n_points,
+                           int32_t points_memspace)
+{
+  if (!h || !n_ext || !n_points || source < VOFOD_POINTS_SYNC || source >= vofod_handle::MAX_INFLIGHT || (points_memspace != VOFOD_MEM_HOST && points_memspace != VOFOD_MEM_DEVICE) ||
+      (index && !points))
+    return VOFOD_ERR_INVALID_ARG;
+  if (points_memspace == VOFOD_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(index)) & 3))
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  (void)hipSetDevice(h->device);
+  const int t = source == VOFOD_POINTS_SYNC ? 0 : source;
+  Workspace& ws = *h->slot(t);
+  if (!ws.det_valid || ws.det_submitted != (source != VOFOD_POINTS_SYNC))
+    return VOFOD_ERR_NOT_PENDING;
+  // counts and offsets: known on the host from the collected detections
+  const size_t n = ws.det_refs.size();
+  std::vector<vdp::DetDesc> descs(n);
+  size_t total = 0;
+  for (size_t i = 0; i < n; i++)
+  {
+    const Workspace::DetRef& r = ws.det_refs[i];
+    descs[i] = vdp::DetDesc{r.frame, r.root, static_cast<uint32_t>(total), r.n_points};
+    total += r.n_points;
+  }
+  *n_ext = n;
+  *n_points = total;
+  if (!ext && !points)
+    return VOFOD_OK;  // size query
+  if ((ext && ext_cap < n) || (points && points_cap < total))
+    return VOFOD_ERR_CAPACITY;
+  if (n == 0)
+    return VOFOD_OK;
+  if (total > 0xffffffffull)
+  {
+    h->err = "detection points: more than 2^32 member voxels";
+    return VOFOD_ERR_DEVICE;
+  }
+  // on the workspace's own chain stream (everything that wrote the workspace has been waited for by its collect half)
+  VCHK(ensure_chain_stream(h, t));
+  StreamScope scope(h, h->chain_stream[t]);
+  HIPCHK(ws.d_detdesc.reserve(n));
+  HIPCHK(ws.d_detbox.reserve(n));
+  HIPCHK(ws.d_detpts.reserve(total));
+  HIPCHK(ws.d_detidx.reserve(total));
+  std::vector<vdp::DetBox> boxes(n);
+  HIPCHK(hipMemcpyAsync(ws.d_detdesc, descs.data(), sizeof(vdp::DetDesc) * n, hipMemcpyHostToDevice, h->stream));
+  KLAUNCH(h, vdp::k_det_points, dim3(static_cast<uint32_t>(n)), dim3(vdp::DP_THREADS), ws.d_hdrs, ws.d_cand, ws.va.pts, ws.det_vox_cap, ws.d_detdesc, ws.d_detpts, ws.d_detidx, ws.d_detbox);
+  HIPCHK(hipMemcpyAsync(boxes.data(), ws.d_detbox, sizeof(vdp::DetBox) * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < n; i++)
+    if (boxes[i].found != descs[i].n_points)
+    {
+      h->err = "detection points: detection " + std::to_string(ws.det_refs[i].id) + " has " + std::to_string(descs[i].n_points) + " points, its cluster " + std::to_string(boxes[i].found) +
+               " entries in the frame's member list";
+      return VOFOD_ERR_DEVICE;
+    }
+  // (the staging buffers are 16-byte aligned for the kernel's stores; the caller's need not be)
+  static_assert(sizeof(vofod_point_xyzr) == sizeof(float4), "a voxel record is a vofod_point_xyzr");
+  const hipMemcpyKind kind = points_memspace == VOFOD_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  if (points && total)
+    HIPCHK(hipMemcpyAsync(points, ws.d_detpts, sizeof(float4) * total, kind, h->stream));
+  if (index && total)
+    HIPCHK(hipMemcpyAsync(index, ws.d_detidx, sizeof(uint32_t) * total, kind, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (size_t i = 0; ext && i < n; i++)
+  {
+    vofod_detection_extent& e = ext[i];
+    e.id = ws.det_refs[i].id;
+    e.frame = ws.det_refs[i].frame;
+    e.first = descs[i].first;
+    e.count = descs[i].n_points;
+    for (int a = 0; a < 3; a++)
+    {
+      e.aabb_min[a] = boxes[i].aabb_min[a];
+      e.aabb_max[a] = boxes[i].aabb_max[a];
+    }
+  }
   return VOFOD_OK;
 }
 

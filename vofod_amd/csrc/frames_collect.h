@@ -92,6 +92,7 @@ int device_tail_records(vofod_handle* h, Workspace& ws, const FrameCall& call, v
       return VOFOD_ERR_CAPACITY;
     }
   }
+  ws.det_begin(call.submitted, call.g.vox_cap);
   for (uint32_t f = 0; f < n; f++)
   {
     const vtd::FrameDets& D = ws.h_dets[f];
@@ -101,6 +102,7 @@ int device_tail_records(vofod_handle* h, Workspace& ws, const FrameCall& call, v
     {
       const vtd::DetRaw& R = D.d[i];
       const vofod_detection det = vt::make_detection(h->last_detection_id++, call.tfs + 12 * f, R.center, R.n_points, R.conf_sum, f, h->sp, *call.dp);
+      ws.det_refs.push_back({det.id, f, R.root, R.n_points});
       if (out && total < cap)
         out[total] = det;
       total++;
@@ -113,6 +115,7 @@ int device_tail_records(vofod_handle* h, Workspace& ws, const FrameCall& call, v
   *n_out = total;
   if (total > cap)
     ret = VOFOD_ERR_CAPACITY;
+  ws.det_valid = ret == VOFOD_OK;
   return ret;
 }
 
@@ -131,11 +134,13 @@ int device_tail_overflow_records(vofod_handle* h, Workspace& ws, const FrameCall
   HIPCHK(hipMemcpy(tc.data(), ws.d_tailc, sizeof(vtd::TailCluster) * vtd::TP_MAXC, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(res.data(), h->explore.d_results, sizeof(vc::ExploreResult) * vtd::TP_MAXC, hipMemcpyDeviceToHost));  // (frame 0: result slots 0..TP_MAXC-1)
   size_t total = 0;
+  ws.det_begin(call.submitted, call.g.vox_cap);
   for (int c = 0; c < vtd::TP_MAXC; c++)
   {
     if (tc[c].job < 0 || tc[c].job >= vtd::TP_MAXC || !res[tc[c].job].floating)
       continue;
     const vofod_detection det = vt::make_detection(h->last_detection_id++, call.tfs, tc[c].obb_center, tc[c].n_members, res[tc[c].job].conf_sum, 0, h->sp, *call.dp);
+    ws.det_refs.push_back({det.id, 0u, tc[c].root, tc[c].n_members});
     if (out && total < cap)
       out[total] = det;
     total++;
@@ -143,6 +148,7 @@ int device_tail_overflow_records(vofod_handle* h, Workspace& ws, const FrameCall
   if (n_out_per_frame)
     n_out_per_frame[0] = static_cast<uint32_t>(total);
   *n_out = total;
+  ws.det_valid = total <= cap;
   return total > cap ? VOFOD_ERR_CAPACITY : VOFOD_OK;
 }
 
@@ -366,8 +372,8 @@ int explore_on_device(vofod_handle* h, const FrameCall& call, ExploreWork& w, fl
 }
 
 // extractDetections :834-879 for one frame; returns the number of its detections
-uint32_t extract_detections(vofod_handle* h, const FrameTail& T, uint32_t f, const float* tf, const vofod_dyn_params& dp, const std::vector<vc::ExploreResult>& results, vofod_detection* out, size_t cap,
-                            size_t& total)
+uint32_t extract_detections(vofod_handle* h, Workspace& ws, const FrameTail& T, uint32_t f, const float* tf, const vofod_dyn_params& dp, const std::vector<vc::ExploreResult>& results, vofod_detection* out,
+                            size_t cap, size_t& total)
 {
   uint32_t n_det_frame = 0;
   for (size_t ci = 0; ci < T.cl.size(); ci++)
@@ -377,6 +383,7 @@ uint32_t extract_detections(vofod_handle* h, const FrameTail& T, uint32_t f, con
       continue;
     const vt::MemberSpan mem = T.by_root.of(c.rec.root);
     const vofod_detection det = vt::make_detection(h->last_detection_id++, tf, c.boxes.obb_center, mem.size(), results[T.job_of[ci]].conf_sum, f, h->sp, dp);
+    ws.det_refs.push_back({det.id, f, c.rec.root, static_cast<uint32_t>(mem.size())});
     if (out && total < cap)
       out[total] = det;
     total++;
@@ -481,6 +488,7 @@ int host_tail(vofod_handle* h, Workspace& ws, const FrameCall& call, const doubl
   const double tr_explore = ms_since(call.t0);
 
   size_t total = 0;
+  ws.det_begin(call.submitted, call.g.vox_cap);
   for (uint32_t f = 0; f < n; f++)
   {
     FrameTail& T = tails[f];
@@ -492,7 +500,7 @@ int host_tail(vofod_handle* h, Workspace& ws, const FrameCall& call, const doubl
     for (size_t ci = 0; ci < T.cl.size(); ci++)
       if (const int ji = T.job_of[ci]; ji >= 0)
         T.cl[ci].cclass = w.results[ji].floating ? VOFOD_CLASS_MAV : VOFOD_CLASS_UNKNOWN;
-    const uint32_t n_det_frame = extract_detections(h, T, f, call.tfs + 12 * f, dp, w.results, out, cap, total);
+    const uint32_t n_det_frame = extract_detections(h, ws, T, f, call.tfs + 12 * f, dp, w.results, out, cap, total);
     if (n_out_per_frame)
       n_out_per_frame[f] = n_det_frame;
     if (dbg)
@@ -521,6 +529,7 @@ int host_tail(vofod_handle* h, Workspace& ws, const FrameCall& call, const doubl
   *n_out = total;
   if (total > cap)
     ret = VOFOD_ERR_CAPACITY;
+  ws.det_valid = ret == VOFOD_OK;
   return ret;
 }
 
@@ -529,7 +538,11 @@ int collect_frames(vofod_handle* h, Workspace& ws, FrameCall& call, vofod_detect
 {
   const uint32_t n = call.n;
   if (n == 0)
-    return VOFOD_OK;  // (*n_out is zero already: the entry points clear it)
+  {
+    ws.det_begin(call.submitted, ws.vox_cap);
+    ws.det_valid = true;  // (no frames, no detections: vofod_detection_points answers 0 / 0)
+    return VOFOD_OK;      // (*n_out is zero already: the entry points clear it)
+  }
   const bool no_update = call.flags & VOFOD_SCAN_NO_MAP_UPDATE;
   // ---- wait for the chain
   if (call.submitted)

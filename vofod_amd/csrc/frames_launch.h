@@ -172,6 +172,7 @@ inline bool is_range_image(const vofod_scan& s) { return !s.x && !s.y && !s.z &&
 int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const float* tfs, uint32_t n, size_t npts, bool& host_copies)
 {
   bool staged_2d = false;
+  ws.det_valid = false;  // (the workspace is taken: what vofod_detection_points answered from is about to be overwritten)
   ws.n_rjobs = 0;
   auto slot = [&](uint32_t f) { return ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5; };
   // the frame's arguments point at the packed x | y | z columns of its staging slot (copied there, or decoded there by k_range_decode)
@@ -489,6 +490,7 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   const bool submitted = call.submitted;
   const uint32_t n = call.n;
   vofod_scan_debug* dbg = call.dbg;
+  ws.det_valid = false;  // (as in stage_inputs: a re-run does not stage, an empty batch launches nothing)
   if (submitted && !ws.rerun)
     ws.job_dp = h->dp;
   call.dp = submitted ? &ws.job_dp : &h->dp;

@@ -241,6 +241,8 @@ int ms_apply_locked(vofod_handle* h, const vms::WireHeader& hd, const uint8_t* d
   if (maps & (1 << VOFOD_MAP_RAYCAST))
     h->ray_dirty = true;  // (the next raycast_begin clears the accumulator unless a finish sweeps it)
   h->sep_pending = false;  // a sepclusters pass of this handle belongs to the map it replaced
+  for (int t = 0; t < vofod_handle::MAX_INFLIGHT; t++)
+    h->slot(t)->det_valid = false;  // ... and so do the detections vofod_detection_points would answer for
   h->mapbits_valid = false;  // occupancy image, dilated image and nVoxelsOver are rebuilt on next use (as after write_map)
   HIPCHK(hipStreamSynchronize(h->stream));
   s.applied_gen = hd.new_gen;

@@ -33,6 +33,7 @@
 #include "kernels_voxelize.h"
 #include "mapsync.h"
 #include "range_decode.h"
+#include "detection_points.h"
 
 using namespace vk;
 
@@ -374,6 +375,28 @@ struct Workspace
   vofod_dyn_params job_dp{};   // the dynamic parameters the pending batch was submitted with
   bool rerun = false;          // the next launch repeats this workspace's batch (LDS overflow): frame arguments and staged columns are kept
   DevBuf<CandMemberX> d_members_big;  // vox_cap gathered candidate members: read-back of a frame whose list exceeds the packed slot
+  // vofod_detection_points: what the record builders (frames_collect.h) returned last from this workspace - one entry per detection,
+  // in the order returned.  Valid from the builder's return until the workspace is taken again (launch_frames, stage_inputs), the
+  // map is replaced (vofod_reset, vofod_map_apply) or a failed call leaves nothing to answer for.
+  struct DetRef
+  {
+    uint32_t id, frame, root, n_points;
+  };
+  std::vector<DetRef> det_refs;
+  bool det_valid = false;
+  bool det_submitted = false;  // ... by vofod_batch_collect (the ticket's source) rather than a synchronous call (VOFOD_POINTS_SYNC)
+  uint32_t det_vox_cap = 0;    // stride of the frame slots the batch ran with
+  void det_begin(bool submitted, uint32_t stride)
+  {
+    det_refs.clear();
+    det_valid = false;
+    det_submitted = submitted;
+    det_vox_cap = stride;
+  }
+  DevBuf<vdp::DetDesc> d_detdesc;  // staging of a query, grown on use
+  DevBuf<vdp::DetBox> d_detbox;
+  DevBuf<float4> d_detpts;
+  DevBuf<uint32_t> d_detidx;
   // state of a submitted, not yet collected batch (vofod_batch_submit / vofod_batch_collect)
   bool pending = false;
   uint32_t job_n = 0;

@@ -334,6 +334,32 @@ class VoFOD:
         self._check(self.lib.range_to_points(self.h, C.byref(cs), *(capi.ptr(a) for a in xyz), capi.MEM_HOST), "vofod_range_to_points", allow)
         return tuple(xyz)
 
+    def detection_points(self, source: int = capi.POINTS_SYNC, device_out=None, allow: Sequence[int] = ()):
+        """Member voxels and AABB of the detections returned last from `source` (vofod_detection_points): capi.POINTS_SYNC for the
+        last synchronous process_scan / process_batch, or the ticket of a collected batch.  Returns (ext, points, index): one
+        capi.DETECTION_EXTENT record per detection in the order returned, the members as capi.POINT_XYZR - detection by detection,
+        ascending by their index in the frame's weighted cloud - and that index.  `device_out` = (points address, index address or
+        None, capacity in points) on the handle's device: the points go there and (ext, None, None) comes back.  A status in
+        `allow` is returned in place of the tuple."""
+        n_ext, n_pts = C.c_size_t(0), C.c_size_t(0)
+        st = self.lib.detection_points(self.h, int(source), None, 0, C.byref(n_ext), None, None, 0, C.byref(n_pts), capi.MEM_HOST)
+        if st != capi.OK:
+            return self._check(st, "vofod_detection_points", allow)
+        ext = np.zeros(n_ext.value, dtype=capi.DETECTION_EXTENT)
+        if device_out is not None:
+            d_pts, d_idx, cap = device_out
+            st = self.lib.detection_points(self.h, int(source), capi.ptr(ext), ext.size, C.byref(n_ext), C.c_void_p(int(d_pts)), None if d_idx is None else C.c_void_p(int(d_idx)), int(cap),
+                                           C.byref(n_pts), capi.MEM_DEVICE)
+            if st != capi.OK:
+                return self._check(st, "vofod_detection_points", allow)
+            return ext, None, None
+        pts = np.zeros(n_pts.value, dtype=capi.POINT_XYZR)
+        idx = np.zeros(n_pts.value, dtype=np.uint32)
+        st = self.lib.detection_points(self.h, int(source), capi.ptr(ext), ext.size, C.byref(n_ext), capi.ptr(pts), capi.ptr(idx), pts.size, C.byref(n_pts), capi.MEM_HOST)
+        if st != capi.OK:
+            return self._check(st, "vofod_detection_points", allow)
+        return ext, pts, idx
+
     # ------------------------------------------------- stateless L4 helpers
     def voxel_grid_weighted(self, x, y, z, leaf: float, align_center=None):
         return voxel_grid_weighted(self.lib, x, y, z, leaf, align_center, handle=self.h)
