@@ -123,6 +123,20 @@ constexpr int IN_PPT = 8;                                  // consecutive points
 constexpr uint32_t IN_ROUND = FR_THREADS * IN_PPT;         // points per round and workgroup
 constexpr uint32_t IN_SEG_ALIGN = 16u * 64u * IN_PPT;      // the code list of a frame: 16 per-wave segments, each a whole number of rounds
 
+// The per-node arrays of the frame kernel as one LDS block.  Until phase 2 writes the first of them the input pass keeps one
+// queue of live lane units per wave here: 64 units of IN_PPT raw points - six planes of 64 float4 (x, x, y, y, z, z: every
+// access a 16-byte one at consecutive addresses) - and the low halves of the units' indices.
+struct FrNodeLds
+{
+  unsigned long long word[LB_MAX];
+  uint32_t xyz[LB_MAX];
+  uint32_t x2[FR_EREC];
+};
+constexpr uint32_t IN_Q_UNITS = 64;                                       // units a wave's queue holds: one per lane of a drain
+constexpr uint32_t IN_Q_PLANES = 3 * IN_PPT / 4;                          // float4 planes of a queue
+constexpr uint32_t IN_Q_BYTES = IN_Q_UNITS * (IN_PPT * 12 + 2);           // a queue: the planes, then 16 bits per unit
+static_assert(IN_PPT % 4 == 0 && IN_Q_BYTES % 16 == 0 && IN_Q_BYTES * (FR_THREADS / 64) <= sizeof(FrNodeLds), "the input pass's unit queues live in the per-node arrays");
+
 // v_min3_f32 / v_max3_f32: two new points per instruction.  A quiet NaN operand is ignored (the other operands decide), which
 // makes qNaN the neutral element of both: dropped points are replaced by it once and need no second select.
 __device__ __forceinline__ float min3_raw(float a, float b, float c)
@@ -358,9 +372,11 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) unsigned long long s_bb[FR_BB64];  // brick-lattice bitmap (bit = linear brick id) + exclusive popcount prefix per
                                                                             // 64-bit word; during the counting / rank phases: one byte counter per voxel
-  __shared__ unsigned long long s_word[LB_MAX];                                      // node -> occupancy word; phase E: component minima / statistics
-  __shared__ uint32_t s_xyz[LB_MAX];                                                 // node -> brick coordinates, 10 bits each
-  __shared__ __attribute__((aligned(8))) uint32_t s_x2[FR_EREC];                     // extras records (phases 3-4), then the 16-bit union-find
+  // (one block: none of the three is touched before phase 2, and the input pass keeps its per-wave unit queues in their storage)
+  __shared__ __attribute__((aligned(16))) FrNodeLds s_nodes;
+  unsigned long long (&s_word)[LB_MAX] = s_nodes.word;                               // node -> occupancy word; phase E: component minima / statistics
+  uint32_t (&s_xyz)[LB_MAX] = s_nodes.xyz;                                           // node -> brick coordinates, 10 bits each
+  uint32_t (&s_x2)[FR_EREC] = s_nodes.x2;                                            // extras records (phases 3-4), then the 16-bit union-find
   __shared__ LbTables s_tab;
   __shared__ unsigned long long s_cin[FR_CHUNKS + 1][4];  // per chunk: tail sums of its last brick row, then the carry into the chunk
   __shared__ uint32_t s_cflag[FR_CHUNKS + 1];
@@ -516,27 +532,96 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
         }
       }
     };
-    for (uint32_t r = 0; r < in_rounds; r++)
+    // Lane units.  A lane's IN_PPT consecutive points are almost always all returns or all "no return" (the survivors of a scan
+    // come in runs of hundreds of points), and in the pieces that hold any return about half of the lanes hold none.  A round is
+    // therefore split: the light FRONT loads a piece and pushes the live units - a unit that starts inside the cloud and, where
+    // zeros are dropped, holds a point that is not zero - into the wave's queue in LDS, at their rank among the live lanes (unit
+    // order is kept); the heavy BACK runs when the queue holds a unit for every lane, and once at the end for the rest: every lane
+    // pops one unit and works on it exactly as it did on its own (crops, transform, cell, run merge, append - per point, so
+    // mixed units, non-finite values and cropped points are dropped where they always were).  A push that does not fit is split
+    // around the drain.  Where zeros are ordinary points every unit is live and the queue passes the pieces through.
+    static_assert(sizeof(uint16_t) * CF_MAX >= 2u * IN_Q_UNITS * (FR_THREADS / 64), "the high halves of the queued units' indices borrow the close-first union-find");
+    float4* const q_pl = reinterpret_cast<float4*>(reinterpret_cast<char*>(&s_nodes) + static_cast<uint32_t>(wave) * IN_Q_BYTES);  // [IN_Q_PLANES][IN_Q_UNITS]
+    uint16_t* const q_lo = reinterpret_cast<uint16_t*>(q_pl + IN_Q_PLANES * IN_Q_UNITS);                                             // unit index (round << 6 | lane): low half ...
+    uint16_t* const q_hi = s_pfpar + static_cast<uint32_t>(wave) * IN_Q_UNITS;                                                       // ... and high half
+    uint32_t q_fill = 0;  // units in the queue (wave-uniform)
+    for (uint32_t r = 0;; r++)
     {
       // (No software prefetch of the next round.  Round 4: with the codes' stores between a prefetch and its use every round ended
       // with a full drain of its own stores - vmcnt counts loads and stores alike.  Round 5: the clean form - wait at the top of the
       // iteration, where this round's loads are the youngest operations in flight, then the previous round's stores, held in
       // registers, then the next round's loads, then the work - compiles as intended (one s_waitcnt vmcnt(0) per round, at the
       // top) and measures the same: 274.1 / 277.1 / 278.2 us against 276.1 / 279.3 / 279.1 us per 256 frames, interleaved on one box.
-      // The pass is not waiting for its loads: ~60 branches and ~540 vector instructions per wave and round are what it costs.)
-      float px[IN_PPT], py[IN_PPT], pz[IN_PPT];
-      load_round(r, px, py, pz);
-      // (the waves take the round's 512-point pieces in turn: a wave sees every azimuth sector and ring parity - even load)
-      const uint32_t i0 = r * IN_ROUND + ((static_cast<uint32_t>(wave) + r) & (FR_THREADS / 64 - 1)) * (64u * IN_PPT) + static_cast<uint32_t>(lane) * IN_PPT;
-      if (zero_dropped)
+      // The pass is not waiting for its loads: its instruction stream is what it costs.)
+      const bool flush = r >= in_rounds;  // behind the last round: the rest of the queue
+      if (flush && q_fill == 0u)
+        break;
+      // ---- front
+      float lx[IN_PPT], ly[IN_PPT], lz[IN_PPT];
+      bool live = false;
+      uint32_t slot = 0, n_live = 0;
+      if (!flush)
       {
-        uint32_t nz_bits = 0;
+        load_round(r, lx, ly, lz);
+        // (the waves take the round's 512-point pieces in turn: a wave sees every azimuth sector and ring parity - even load)
+        const uint32_t l0 = r * IN_ROUND + ((static_cast<uint32_t>(wave) + r) & (FR_THREADS / 64 - 1)) * (64u * IN_PPT) + static_cast<uint32_t>(lane) * IN_PPT;
+        live = l0 < n_pts;
+        if (zero_dropped)
+        {
+          uint32_t nz_bits = 0;
 #pragma unroll
-        for (int j = 0; j < IN_PPT; j++)
-          nz_bits |= (__float_as_uint(px[j]) | __float_as_uint(py[j]) | __float_as_uint(pz[j])) & 0x7fffffffu;  // (-0.0 is zero too)
-        if (!__any(nz_bits != 0u))
-          continue;
+          for (int j = 0; j < IN_PPT; j++)
+            nz_bits |= (__float_as_uint(lx[j]) | __float_as_uint(ly[j]) | __float_as_uint(lz[j])) & 0x7fffffffu;  // (-0.0 is zero too)
+          live &= nz_bits != 0u;
+        }
+        const unsigned long long lb = __ballot(live);
+        if (lb == 0ull)
+          continue;  // a ring that looks at the sky
+        n_live = static_cast<uint32_t>(__popcll(lb));
+        slot = q_fill + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(lb >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(lb), 0u));
       }
+      auto push = [&](uint32_t s) {
+#pragma unroll
+        for (int q = 0; q < IN_PPT / 4; q++)
+        {
+          q_pl[(0 * (IN_PPT / 4) + q) * IN_Q_UNITS + s] = make_float4(lx[4 * q], lx[4 * q + 1], lx[4 * q + 2], lx[4 * q + 3]);
+          q_pl[(1 * (IN_PPT / 4) + q) * IN_Q_UNITS + s] = make_float4(ly[4 * q], ly[4 * q + 1], ly[4 * q + 2], ly[4 * q + 3]);
+          q_pl[(2 * (IN_PPT / 4) + q) * IN_Q_UNITS + s] = make_float4(lz[4 * q], lz[4 * q + 1], lz[4 * q + 2], lz[4 * q + 3]);
+        }
+        const uint32_t id = (r << 6) | static_cast<uint32_t>(lane);
+        q_lo[s] = static_cast<uint16_t>(id);
+        q_hi[s] = static_cast<uint16_t>(id >> 16);
+      };
+      if (live && slot < IN_Q_UNITS)
+        push(slot);
+      const uint32_t q_tot = q_fill + n_live;
+      if (!flush && q_tot < IN_Q_UNITS)
+      {
+        q_fill = q_tot;
+        continue;
+      }
+      // ---- back: a unit for every lane (the flush: for the first q_fill lanes; the others get a unit behind the cloud's end)
+      float px[IN_PPT], py[IN_PPT], pz[IN_PPT];
+      uint32_t i0;
+      {
+#pragma unroll
+        for (int q = 0; q < IN_PPT / 4; q++)
+        {
+          const float4 x0 = q_pl[(0 * (IN_PPT / 4) + q) * IN_Q_UNITS + lane], y0 = q_pl[(1 * (IN_PPT / 4) + q) * IN_Q_UNITS + lane], z0 = q_pl[(2 * (IN_PPT / 4) + q) * IN_Q_UNITS + lane];
+          px[4 * q] = x0.x, px[4 * q + 1] = x0.y, px[4 * q + 2] = x0.z, px[4 * q + 3] = x0.w;
+          py[4 * q] = y0.x, py[4 * q + 1] = y0.y, py[4 * q + 2] = y0.z, py[4 * q + 3] = y0.w;
+          pz[4 * q] = z0.x, pz[4 * q + 1] = z0.y, pz[4 * q + 2] = z0.z, pz[4 * q + 3] = z0.w;
+        }
+        const uint32_t id = static_cast<uint32_t>(q_lo[lane]) | (static_cast<uint32_t>(q_hi[lane]) << 16);
+        const uint32_t ur = id >> 6;
+        i0 = ur * IN_ROUND + ((static_cast<uint32_t>(wave) + ur) & (FR_THREADS / 64 - 1)) * (64u * IN_PPT) + (id & 63u) * IN_PPT;
+        if (flush && static_cast<uint32_t>(lane) >= q_fill)
+          i0 = n_pts;
+      }
+      // the rest of a push that did not fit goes into the empty queue
+      if (live && slot >= IN_Q_UNITS)
+        push(slot - IN_Q_UNITS);
+      q_fill = flush ? 0u : q_tot - IN_Q_UNITS;
       uint32_t code[IN_PPT];
       uint32_t cnt = 0, frag_mask = 0;
       float sq0 = 0.0f, sq1 = 0.0f, sq2 = 0.0f;  // transformed coordinates of the thread's FIRST fragile point of the round (8 % of the threads have one, 0.3 % a second)
