@@ -532,6 +532,36 @@ int vofod_map_apply(vofod_handle* h, const void* buf, size_t n_bytes, int32_t me
  * (VOFOD_ERR_DEVICE) can end the call on one rank alone. */
 int vofod_broadcast_map(vofod_comm* comm, vofod_handle* h, int32_t root, int32_t maps, int32_t kind, size_t* n_bytes);
 
+/* ------------------------------------------------- rolling operation area (product library only)
+ *
+ * Moves the operation area by a whole number of voxels and keeps what the maps hold about the overlap: for a vehicle that leaves
+ * the box the maps were allocated for.  The reference has no counterpart (its maps are sized once, in onInit).  Afterwards the
+ * handle behaves exactly like a handle created with the same static parameters except oparea_offset = new_oparea_offset, whose
+ * three maps hold, with s = shift_voxels, sizes S and x fastest as everywhere,
+ *     new[ix, iy, iz] = old[ix + s0, iy + s1, iz + s2]   where every i + s lies in [0, S),
+ *     the map's init value elsewhere (score_init for the voxel map, +0.0f for flags and raycast).
+ * Values move as 32-bit patterns (+inf, -0.0f and NaN payloads survive bit for bit).  |s[a]| >= S[a] on any axis is legal and
+ * leaves all three maps at init; s == 0 with an unchanged offset is a no-op that returns VOFOD_OK.  One streaming pass per map on
+ * the device (k_map_shift), out of place into a spare buffer of 4 * M bytes that is allocated by the first shift and freed by
+ * vofod_destroy; map sizes do not change.
+ *
+ * Geometry: the library derives everything from new_oparea_offset with the expressions vofod_create uses, then checks per axis
+ *     | map_offset_new[a] - (map_offset_old[a] + s[a] * voxel_size) | < voxel_size / 4
+ * (map_offset as in vofod_status_info) and returns VOFOD_ERR_INVALID_ARG with nothing changed when shift and offset disagree - a
+ * wrong sign or axis is off by a voxel or more.  Offsets chosen as base + k * voxel_size from an INTEGER k that the caller keeps
+ * (k += s per shift) do not drift: every offset is then one rounding away from the exact value, however many shifts led to it,
+ * whereas offset += s * voxel_size accumulates a rounding per shift.
+ *
+ * State: VOFOD_ERR_BUSY, with nothing changed, while a submitted batch is pending, a raycast pass is pending (raycast_pending of
+ * vofod_status_info: finish it first) or a sepclusters pass is pending between begin and finish.  Kept: detection_its,
+ * last_detection_id, both background latches, the dynamic parameters, workspaces, streams and tickets' buffers.  Derived state
+ * (occupancy images, nVoxelsOver) is rebuilt on next use, as after vofod_write_map.  vofod_detection_points answers
+ * VOFOD_ERR_NOT_PENDING for every source until the next production call.  The snapshot chain ends on both sides: the next
+ * VOFOD_SNAPSHOT_DELTA export or apply answers VOFOD_ERR_DELTA_BASE, a full export starts a new chain, and a snapshot taken
+ * before the shift is refused by apply's geometry check (VOFOD_ERR_SIZE_MISMATCH: the header carries the offset).  A replica
+ * shifts first and then takes a full snapshot. */
+int vofod_map_shift(vofod_handle* h, const int32_t shift_voxels[3], const float new_oparea_offset[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,16 @@ sub = {
 }
 # §5.9: which figures of profiles/r12_detection_points.txt were measured (its first line says so)
 sub["R12_STATUS"] = (P / "r12_detection_points.txt").read_text().splitlines()[0].removeprefix("status: ")
+# §5.10: the figures of profiles/r14_map_shift.json
+r14 = json.loads((P / "r14_map_shift.json").read_text())
+parts = []
+for c in r14["configs"]:
+    a, u, y, h = c["aligned"], c["unaligned"], c["memcpy_d2d_one_map"], c["host_round_trip"]
+    parts.append(f"at {c['config']} ({c['sensor']}, M = {c['M'] / 1e6:.1f} M) `k_map_shift` takes {a['k_map_shift_ms_per_map']:.4f} ms per map ({a['tbs']:.2f} TB/s on `8 * M` bytes) with aligned and "
+                 f"{u['k_map_shift_ms_per_map']:.4f} ms ({u['tbs']:.2f} TB/s) with 4-byte aligned loads, `hipMemcpyAsync` device to device of one map {y['ms_median']:.4f} ms ({y['tbs']:.2f} TB/s): "
+                 f"aligned / copy = **{c['aligned_over_memcpy']:.3f}** (condition: <= {r14['gate']}: {'met' if c['pass'] else '**missed**'}), unaligned / copy = {c['unaligned_over_memcpy']:.3f}; the whole call "
+                 f"{a['call_wall_ms_median']:.3f} ms against {h['total_ms']:.0f} ms for `read_map` x 3 + numpy + `write_map` x 3 ({c['host_round_trip_over_call']:.0f} x)")
+sub["R14_MEASURED"] = "; ".join(parts) + "."
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

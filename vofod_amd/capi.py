@@ -288,12 +288,13 @@ _SIGS = {
     "broadcast_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_size_t)]),
     "range_to_points": (C.c_int, [C.c_void_p, _P(Scan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "detection_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_int32]),
+    "map_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
-                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points")
+                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift")
 
 
 class MsgHeader(C.Structure):

@@ -397,6 +397,27 @@ int copy_grid_out(vofod_handle* h, Workspace& ws, const GridParams& g, const Fra
   return VOFOD_OK;
 }
 
+// every copy of the geometry the handle keeps, from h->sp (vsh::area_geometry: vofod_create and vofod_map_shift)
+void set_area_geometry(vofod_handle* h)
+{
+  vsh::AreaGeometry g;
+  vsh::area_geometry(h->sp, g);
+  for (int a = 0; a < 3; a++)
+  {
+    h->exclude_center[a] = g.exclude_center[a];
+    h->oparea_center[a] = g.oparea_center[a];
+    h->mg.off[a] = h->hg.off[a] = g.map_off[a];
+    h->hg.s[a] = g.map_size[a];
+  }
+  h->background_min_sufficient_pts = g.background_min_sufficient_pts;
+  h->mg.vs = h->hg.vs = h->sp.voxel_size;
+  h->mg.vs_inv = h->hg.vs_inv = 1.0f / h->sp.voxel_size;
+  h->mg.sx = g.map_size[0];
+  h->mg.sy = g.map_size[1];
+  h->mg.sz = g.map_size[2];
+  h->mg.n = static_cast<uint64_t>(g.map_size[0]) * g.map_size[1] * g.map_size[2];
+}
+
 }  // namespace
 
 // =============================================================================== extern "C"
@@ -724,35 +745,13 @@ int vofod_create(const vofod_static_params* sp, const vofod_dyn_params* dp, vofo
   // theirs when they are first taken: streams that merely exist are not free)
   for (int t = 1; t < 4; t++)
     CREATE_CHK(h->chain_stream[t].create(hipStreamCreateWithFlags, hipStreamNonBlocking));
-  for (int a = 0; a < 3; a++)
-  {
-    h->exclude_center[a] = sp->exclude_offset[a];
-    h->oparea_center[a] = sp->oparea_offset[a];
-  }
-  h->exclude_center[2] = sp->exclude_offset[2] + sp->exclude_size[2] / 2.0f;  // vofod_nodelet.cpp:204
-  h->oparea_center[2] = sp->oparea_offset[2] + sp->oparea_size[2] / 2.0f;     // :212
-  const float n_voxels_xy = sp->oparea_size[0] / sp->voxel_size * sp->oparea_size[1] / sp->voxel_size;  // :229
-  h->background_min_sufficient_pts = static_cast<uint64_t>(n_voxels_xy * sp->background_sufficient_points_ratio);
-  // VoxelMap::resize voxel_map.cpp:11-48
-  const float inv = 1.0f / sp->voxel_size;
-  int sizes[3];
-  for (int a = 0; a < 3; a++)
-  {
-    h->mg.off[a] = h->oparea_center[a] - sp->oparea_size[a] / 2.0f;
-    sizes[a] = static_cast<int>(std::ceil(inv * sp->oparea_size[a])) + 1;
-    h->hg.off[a] = h->mg.off[a];
-    h->hg.s[a] = sizes[a];
-  }
-  h->mg.vs = h->hg.vs = sp->voxel_size;
-  h->mg.vs_inv = h->hg.vs_inv = 1.0f / sp->voxel_size;
-  h->mg.sx = sizes[0];
-  h->mg.sy = sizes[1];
-  h->mg.sz = sizes[2];
-  h->mg.n = static_cast<uint64_t>(sizes[0]) * sizes[1] * sizes[2];
+  set_area_geometry(h);
+  const int* sizes = h->hg.s;
   const size_t M = h->mg.n;
-  CREATE_CHK(h->d_map.alloc(M));
-  CREATE_CHK(h->d_flags.alloc(M));
-  CREATE_CHK(h->d_ray.alloc(M));
+  const size_t M4 = std::max<size_t>(M, 4);  // (k_map_shift's clamped 16-byte load reads the first four voxels of any map)
+  CREATE_CHK(h->d_map.alloc(M4));
+  CREATE_CHK(h->d_flags.alloc(M4));
+  CREATE_CHK(h->d_ray.alloc(M4));
   CREATE_CHK(h->d_mapbits.alloc((M + 63) / 64 + 2));
   CREATE_CHK(hipMemset(h->d_mapbits, 0, ((M + 63) / 64 + 2) * sizeof(unsigned long long)));
   CREATE_CHK(h->d_mapclose.alloc((M + 63) / 64 + 2));
@@ -992,6 +991,86 @@ int vofod_write_map(vofod_handle* h, int which, const float* src, size_t n)
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(m, src, n * sizeof(float), hipMemcpyHostToDevice));
   h->mapbits_valid = false;
+  return VOFOD_OK;
+}
+
+// Rolling operation area (contract: include/vofod.h; kernel, geometry function and the account of the scratch buffers: map_shift.h).
+// Everything is checked before anything changes; the maps move out of place into the spare buffer, whose owner is then swapped with
+// the map's - nothing holds a map pointer between calls (map_shift.h), so there is nothing to refresh behind the swap.
+int vofod_map_shift(vofod_handle* h, const int32_t shift_voxels[3], const float new_oparea_offset[3])
+{
+  if (!h || !shift_voxels || !new_oparea_offset)
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  (void)hipSetDevice(h->device);
+  VCHK(busy_check(h, false, true));
+  if (h->raycast_pending || h->sep_pending)
+  {
+    h->err = h->raycast_pending ? "map shift: a raycast pass is pending: finish it first" : "map shift: a sepclusters pass is pending: finish it first";
+    return VOFOD_ERR_BUSY;
+  }
+  // the geometry a handle created at the new offset would hold
+  vofod_static_params nsp = h->sp;
+  vsh::AreaGeometry ng;
+  bool same_offset = true;
+  for (int a = 0; a < 3; a++)
+  {
+    if (!std::isfinite(new_oparea_offset[a]))
+      return VOFOD_ERR_INVALID_ARG;
+    nsp.oparea_offset[a] = new_oparea_offset[a];
+    same_offset &= std::memcmp(&nsp.oparea_offset[a], &h->sp.oparea_offset[a], 4) == 0;
+  }
+  vsh::area_geometry(nsp, ng);
+  const int S[3] = {h->mg.sx, h->mg.sy, h->mg.sz};
+  for (int a = 0; a < 3; a++)
+  {
+    const double want = static_cast<double>(h->mg.off[a]) + static_cast<double>(shift_voxels[a]) * static_cast<double>(h->mg.vs);
+    if (!(std::fabs(static_cast<double>(ng.map_off[a]) - want) < static_cast<double>(h->mg.vs) / 4.0))
+    {
+      h->err = "map shift: new_oparea_offset does not move the map origin by shift_voxels * voxel_size on axis " + std::to_string(a);
+      return VOFOD_ERR_INVALID_ARG;
+    }
+  }
+  if (same_offset && shift_voxels[0] == 0 && shift_voxels[1] == 0 && shift_voxels[2] == 0)
+    return VOFOD_OK;
+  const size_t M = h->mg.n;
+  HIPCHK(h->d_shift_spare.reserve(std::max<size_t>(M, 4)));  // (it becomes a map: sized as vofod_create sizes them)
+  vsh::ShiftParams p{};
+  p.n = M;
+  p.sx = S[0];
+  p.sy = S[1];
+  p.sz = S[2];
+  int32_t s[3];
+  for (int a = 0; a < 3; a++)
+    s[a] = std::min(std::max(shift_voxels[a], -S[a]), S[a]);  // (a shift of a whole map size or more: nothing is valid either way)
+  p.s0 = s[0];
+  p.s1 = s[1];
+  p.s2 = s[2];
+  p.delta = static_cast<int64_t>(s[0]) + static_cast<int64_t>(s[1]) * S[0] + static_cast<int64_t>(s[2]) * S[0] * S[1];
+  p.ntiles = static_cast<uint32_t>((M + vsh::SH_TILE - 1) / vsh::SH_TILE);
+  const dim3 grid(std::min<uint32_t>(p.ntiles, vsh::SH_GRID));
+  DevBuf<float>* maps[3] = {&h->d_map, &h->d_flags, &h->d_ray};
+  for (int m = 0; m < 3; m++)
+  {
+    const float init = m == VOFOD_MAP_VOXELS ? h->sp.score_init : 0.0f;
+    std::memcpy(&p.init, &init, 4);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(maps[m]->p);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(h->d_shift_spare.p);
+    KLAUNCH_AS(h, "k_map_shift", vsh::k_map_shift, grid, dim3(vsh::SH_THREADS), src, dst, p);
+    HIPCHK(hipGetLastError());
+    std::swap(*maps[m], h->d_shift_spare);  // (stream order: the next launch writes the buffer this one has read)
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->sp = nsp;
+  set_area_geometry(h);
+  h->mapbits_valid = false;  // occupancy image, dilated image and nVoxelsOver are rebuilt on next use (as after write_map)
+  for (int t = 0; t < vofod_handle::MAX_INFLIGHT; t++)
+    h->slot(t)->det_valid = false;  // the detections vofod_detection_points would answer for belong to the old area
+  // the snapshot chain ends on both sides (the shadows hold the unshifted maps; a full export rewrites them)
+  h->msync.chain_gen = 0;
+  h->msync.chain_mask = 0;
+  h->msync.applied_gen = 0;
+  h->msync.applied_mask = 0;
   return VOFOD_OK;
 }
 

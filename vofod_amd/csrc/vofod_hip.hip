@@ -34,6 +34,7 @@
 #include "mapsync.h"
 #include "range_decode.h"
 #include "detection_points.h"
+#include "map_shift.h"
 
 using namespace vk;
 
@@ -566,6 +567,7 @@ struct vofod_handle
   MapGeom mg{};
   vt::Geom hg{};
   DevBuf<float> d_map, d_flags, d_ray;
+  DevBuf<float> d_shift_spare;  // vofod_map_shift: destination of the out-of-place shift, swapped with the map it received (allocated on the first shift)
   DevBuf<unsigned long long> d_mapbits;
   DevBuf<unsigned long long> d_mapclose;  // d_mapbits dilated by hasCloseTo's stencil (k_dilate), valid while gens match
   uint64_t mapbits_gen = 0, mapclose_gen = ~0ull;

@@ -171,6 +171,19 @@ class VoFOD:
         a = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1)
         self._check(self.lib.write_map(self.h, which, capi.ptr(a), a.size), "vofod_write_map")
 
+    def map_shift(self, shift_voxels, new_oparea_offset, allow: Sequence[int] = ()):
+        """Move the operation area by whole voxels (vofod_map_shift): new[ix, iy, iz] = old[ix + s0, iy + s1, iz + s2] inside the
+        overlap, the maps' init values elsewhere; afterwards the handle is one created at `new_oparea_offset`.  Returns the status
+        (one in `allow` leaves the handle as it was)."""
+        s = np.ascontiguousarray(shift_voxels, dtype=np.int32).reshape(3)
+        o = np.ascontiguousarray(new_oparea_offset, dtype=np.float32).reshape(3)
+        st = self._check(self.lib.map_shift(self.h, capi.ptr(s), capi.ptr(o)), "vofod_map_shift", allow)
+        if st == capi.OK:
+            for a in range(3):
+                self.sp.oparea_offset[a] = o[a]
+            self.map_offset = tuple(self.status().map_offset)
+        return st
+
     # ------------------------------------------------- snapshots and deltas
     def export_map(self, maps: int = capi.MAPS_ALL, full: bool = True) -> np.ndarray:
         """A full snapshot or a delta of the maps in `maps` (bitmask of 1 << capi.MAP_*) in the wire format of
