@@ -138,6 +138,26 @@ enum { VOFOD_MEM_HOST = 0, VOFOD_MEM_DEVICE = 1 };
  * of x, y, z NULL is VOFOD_ERR_INVALID_ARG, and so is all three NULL without `range`.  A device-resident range column needs a
  * base and a stride that are multiples of 4 bytes.  vofod_check_sensor_params compares points against the LUT and takes no
  * range image.  The CPU oracle has no range input: it returns VOFOD_ERR_INVALID_ARG for one. */
+/* MOTION COMPENSATION.  A spinning sensor takes a whole period for one scan and delivers a timestamp per measurement column; a
+ * range image may carry one pose per column, `col_tfs` (vofod_column_poses builds the table from two poses).  Pixel i = row * width
+ * + col of the handle's LUT order was measured in column m = (col + shift_by_row[row]) mod width (vofod_set_column_shift; the mod is
+ * mathematical, m in [0, width)), and the point of the pixel is DEFINED as (IEEE float32, each operation rounded once, nothing fused)
+ *     r     = float(range[i]) * 0.001f
+ *     q[a]  = (lut_directions[3i+a] * r) + lut_offsets[3i+a]                     (the definition above)
+ *     p     = (+0, +0, +0)                          when range[i] == 0           (no pose applied: as above)
+ *     p     = (qNaN, qNaN, qNaN), bits 0x7fc00000   when lo[a] <= q[a] <= hi[a] on all three axes, lo / hi = the bounds of the
+ *                                                   exclude box as the first crop uses them (vofod_nodelet.cpp:626-629)
+ *     p[k]  = T[k][0]*q[0] + (T[k][1]*q[1] + (T[k][2]*q[2] + T[k][3]))           otherwise, T = col_tfs[m]
+ * - PCL's association, the one the pipeline's own transform uses.  The call's `tf` is applied afterwards by the unchanged pipeline;
+ * the two matrices are never multiplied together.  The NaN rule keeps the airframe out: a return from the vehicle's own body lies
+ * inside the exclude box in the frame of the instant it was measured, and after compensation it need not; both crops drop
+ * non-finite points.  A return that enters the box only through the compensation is removed by the unchanged first crop.
+ * vofod_process_scan, vofod_process_batch, vofod_batch_submit and vofod_range_to_points accept such scans (a batch may mix them with
+ * plain range images and point scans); the caller may overwrite its pose tables when the call returns, as it may its scans.
+ * vofod_raycast_begin and the raycast half of VOFOD_SCAN_AUTO_RAYCAST IGNORE col_tfs: they cast the rigid rays the reference casts,
+ * from `range` and the LUT.  col_tfs on a point scan (x, y, z given) is VOFOD_ERR_INVALID_ARG, and so is a device-resident table
+ * that is not 4-byte aligned.  sizeof(vofod_scan) is 80 (72 before the field): callers recompile; a zero-initialised scan
+ * (`vofod_scan s{}`) is rigid.  The CPU oracle has no motion input: it rejects range images as before and ignores the field. */
 typedef struct vofod_scan {
   const void* x;          /* float */
   const void* y;          /* float */
@@ -148,6 +168,10 @@ typedef struct vofod_scan {
   int32_t width, height;
   int32_t memspace;       /* VOFOD_MEM_HOST or VOFOD_MEM_DEVICE (device pointers on the handle's device) */
   double stamp;           /* seconds; carried through, not interpreted */
+  const float* col_tfs;   /* NULL: the scan is rigid (everything as today).  Otherwise width * 12 floats in the scan's memspace:
+                             col_tfs[12*m ..] is the row-major 3x4 [R|t] that takes a point from the sensor frame at the time of
+                             measurement column m into the scan's reference sensor frame - the frame the call's `tf` starts from.
+                             Range images only; see MOTION COMPENSATION above */
 } vofod_scan;
 
 /* payload of vofod::PointXYZR (point_types.h:51-56): voxel centre + weight */
@@ -417,6 +441,27 @@ int vofod_serialize_profiling_info(uint32_t stamp_sec, uint32_t stamp_nsec, uint
  * (VOFOD_MEM_HOST or VOFOD_MEM_DEVICE).  For debug clouds and for holding the kernel to the definition.
  * VOFOD_ERR_INVALID_ARG: `scan` is no range image; VOFOD_ERR_SIZE_MISMATCH: its width or height differ from the handle's. */
 int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, float* y, float* z, int32_t out_memspace);
+
+/* ------------------------------------------------- motion compensation of range images (product library only)
+ *
+ * See MOTION COMPENSATION at vofod_scan.  With scan->col_tfs vofod_range_to_points returns the compensated cloud, decoded by the
+ * kernel the per-scan entry points use for such scans (k_range_decode_motion).
+ *
+ * vofod_set_column_shift: a sensor property, set once after vofod_create.  Pixel (row, col) of the handle's LUT order was measured
+ * in column m = (col + shift_by_row[row]) mod width; any int32 shift is legal.  shift_by_row: sensor_vrays ints, NULL = zeros (the
+ * state after vofod_create).  This is the direction of the reference's mask mangling (vofod_nodelet.cpp:537) for a DESTAGGERED
+ * image - pixel_shift_by_row of the sensor's metadata; a staggered image (columns are measurement columns) needs zeros.  Kept
+ * across vofod_reset, vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch is pending. */
+int vofod_set_column_shift(vofod_handle* h, const int32_t* shift_by_row /* height ints; NULL = zeros */);
+/* Host helper (no handle, no device): the pose table of a scan from two sensor->world poses.
+ *     col_tfs[m] = tf_ref^-1 o P(frac[m]),   m = 0 .. n-1,   frac == NULL: frac[m] = m / (n - 1) (0 when n == 1)
+ * P(f) interpolates tf_begin (f = 0) and tf_end (f = 1): translation linear, rotation R0 * exp(f * log(R0^T R1)) on the shortest
+ * arc; f outside [0, 1] extrapolates (constant twist).  tf_ref is the pose the call's `tf` will be (usually tf_end, or the pose at
+ * the scan's stamp).  Computed in double, cast to float at the end.  Rotation parts are taken as orthonormal: each is replaced
+ * by the rotation nearest to it (a float matrix is orthonormal to 1e-7 only), the inverse is the transpose.  n <= 0 or a NULL pointer (frac excepted) is
+ * VOFOD_ERR_INVALID_ARG. */
+int vofod_column_poses(const float tf_begin[12], const float tf_end[12], const float tf_ref[12],
+                       const double* frac /* n, NULL = m / (n - 1) */, int32_t n, float* col_tfs);
 
 /* ------------------------------------------------- member voxels and AABB of the detections (product library only)
  *

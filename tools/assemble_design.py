@@ -78,6 +78,8 @@ for c in r14["configs"]:
                  f"aligned / copy = **{c['aligned_over_memcpy']:.3f}** (condition: <= {r14['gate']}: {'met' if c['pass'] else '**missed**'}), unaligned / copy = {c['unaligned_over_memcpy']:.3f}; the whole call "
                  f"{a['call_wall_ms_median']:.3f} ms against {h['total_ms']:.0f} ms for `read_map` x 3 + numpy + `write_map` x 3 ({c['host_round_trip_over_call']:.0f} x)")
 sub["R14_MEASURED"] = "; ".join(parts) + "."
+# §5.11: the first line of profiles/r15_range_motion.txt
+sub["R15_MEASURED"] = (P / "r15_range_motion.txt").read_text().splitlines()[0].removeprefix("measured: ")
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

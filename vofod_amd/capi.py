@@ -99,7 +99,11 @@ class Scan(C.Structure):
         ("height", C.c_int32),
         ("memspace", C.c_int32),
         ("stamp", C.c_double),
+        ("col_tfs", C.c_void_p),  # float[width * 12]: a pose per measurement column (range images only); NULL = rigid
     ]
+
+
+assert C.sizeof(Scan) == 80
 
 
 class Detection(C.Structure):
@@ -289,12 +293,14 @@ _SIGS = {
     "range_to_points": (C.c_int, [C.c_void_p, _P(Scan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "detection_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_int32]),
     "map_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "set_column_shift": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "column_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
-                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift")
+                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift", "set_column_shift", "column_poses")
 
 
 class MsgHeader(C.Structure):

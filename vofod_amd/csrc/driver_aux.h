@@ -452,6 +452,98 @@ struct WireOut
 };
 }  // namespace
 
+// ---- vofod_column_poses: host only, double throughout
+namespace colposes
+{
+struct Quat
+{
+  double x, y, z, w;
+};
+inline Quat mul(const Quat& a, const Quat& b)
+{
+  return Quat{a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w,
+              a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
+}
+inline Quat conj(const Quat& q) { return Quat{-q.x, -q.y, -q.z, q.w}; }
+// The unit quaternion of the rotation part of a float[12].  A matrix that is orthonormal only to float precision is first replaced
+// by the rotation nearest to it - the orthogonal factor of its polar decomposition, by Newton's iteration X <- (X + X^-T) / 2, which
+// converges quadratically from 1e-7 away - then Markley 2008: the largest of the trace and the diagonal picks the well-conditioned
+// formula.
+inline Quat from_tf(const float tf[12])
+{
+  double m[3][3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++)
+      m[i][j] = tf[4 * i + j];
+  for (int it = 0; it < 6; it++)
+  {
+    double c[3][3];  // cofactors: X^-T = c / det
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++)
+      {
+        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+        c[i][j] = m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1];
+      }
+    const double det = m[0][0] * c[0][0] + m[0][1] * c[0][1] + m[0][2] * c[0][2];
+    if (!(std::abs(det) > 1e-300))
+      break;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++)
+        m[i][j] = 0.5 * (m[i][j] + c[i][j] / det);
+  }
+  const double tr = m[0][0] + m[1][1] + m[2][2];
+  double q[4];
+  int c = 3;
+  double best = tr;
+  for (int i = 0; i < 3; i++)
+    if (m[i][i] > best)
+      best = m[i][i], c = i;
+  if (c != 3)
+  {
+    const int i = c, j = (i + 1) % 3, k = (j + 1) % 3;
+    q[i] = 1.0 - tr + 2.0 * m[i][i];
+    q[j] = m[j][i] + m[i][j];
+    q[k] = m[k][i] + m[i][k];
+    q[3] = m[k][j] - m[j][k];
+  }
+  else
+  {
+    q[0] = m[2][1] - m[1][2];
+    q[1] = m[0][2] - m[2][0];
+    q[2] = m[1][0] - m[0][1];
+    q[3] = 1.0 + tr;
+  }
+  const double nrm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  return Quat{q[0] / nrm, q[1] / nrm, q[2] / nrm, q[3] / nrm};
+}
+inline void to_matrix(const Quat& q, double R[3][3])
+{
+  const double x2 = q.x * q.x, y2 = q.y * q.y, z2 = q.z * q.z, w2 = q.w * q.w;
+  const double xy = q.x * q.y, zw = q.z * q.w, xz = q.x * q.z, yw = q.y * q.w, yz = q.y * q.z, xw = q.x * q.w;
+  R[0][0] = x2 - y2 - z2 + w2, R[0][1] = 2 * (xy - zw), R[0][2] = 2 * (xz + yw);
+  R[1][0] = 2 * (xy + zw), R[1][1] = -x2 + y2 - z2 + w2, R[1][2] = 2 * (yz - xw);
+  R[2][0] = 2 * (xz - yw), R[2][1] = 2 * (yz + xw), R[2][2] = -x2 - y2 + z2 + w2;
+}
+// log on the shortest arc: the rotation vector of q, angle in [0, pi]
+inline void rotvec(Quat q, double v[3])
+{
+  if (q.w < 0)
+    q = Quat{-q.x, -q.y, -q.z, -q.w};
+  const double s = std::sqrt(q.x * q.x + q.y * q.y + q.z * q.z);
+  const double angle = 2.0 * std::atan2(s, q.w);
+  // angle / sin(angle / 2); its series where the angle is small
+  const double k = angle <= 1e-3 ? 2.0 + angle * angle / 12.0 + 7.0 * angle * angle * angle * angle / 2880.0 : angle / std::sin(angle / 2.0);
+  v[0] = k * q.x, v[1] = k * q.y, v[2] = k * q.z;
+}
+inline Quat from_rotvec(const double v[3])
+{
+  const double angle = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  const double a2 = angle * angle;
+  const double k = angle <= 1e-3 ? 0.5 - a2 / 48.0 + a2 * a2 / 3840.0 : std::sin(angle / 2.0) / angle;
+  return Quat{k * v[0], k * v[1], k * v[2], std::cos(angle / 2.0)};
+}
+}  // namespace colposes
+
 extern "C" {
 
 void vofod_default_params(vofod_static_params* sp, vofod_dyn_params* dp)
@@ -779,6 +871,8 @@ int vofod_create(const vofod_static_params* sp, const vofod_dyn_params* dp, vofo
   CREATE_CHK(hipMemcpy(h->d_lut_dirs, dirs.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice));
   CREATE_CHK(hipMemcpy(h->d_lut_offs, offs.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice));
   CREATE_CHK(hipMemcpy(h->d_mask, mask.data(), n, hipMemcpyHostToDevice));
+  CREATE_CHK(h->d_col_shift.alloc(static_cast<size_t>(sp->sensor_vrays)));
+  CREATE_CHK(hipMemset(h->d_col_shift, 0, sizeof(uint32_t) * std::max(sp->sensor_vrays, 1)));
   // per-frame workspace: the crops bound the voxel-grid lattice by the map lattice plus one cell per side
   const uint64_t cells = static_cast<uint64_t>(sizes[0] + 2) * (sizes[1] + 2) * (sizes[2] + 2);
   if (cells > 0x7fffffffull)
@@ -1213,8 +1307,10 @@ int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, flo
   (void)hipSetDevice(h->device);
   if (scan->height != h->sp.sensor_vrays || scan->width != h->sp.sensor_hrays)
     return VOFOD_ERR_SIZE_MISMATCH;
+  VCHK(check_col_tfs(h, *scan));
   VCHK(busy_check(h, true, false));
-  // one frame through the batch path's staging and kernel: frame slot 0 of the synchronous workspace
+  // one frame through the batch path's staging and kernel (k_range_decode, or k_range_decode_motion for a scan with col_tfs): frame
+  // slot 0 of the synchronous workspace
   Workspace& ws = h->ws;
   const size_t npts = static_cast<size_t>(scan->width) * scan->height;
   const float tf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -1226,6 +1322,54 @@ int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, flo
     HIPCHK(hipMemcpyAsync(out[c], ws.d_stage + static_cast<size_t>(c) * ws.pt_cap, npts * sizeof(float), out_memspace == VOFOD_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                           h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  return VOFOD_OK;
+}
+
+// A sensor property: the measurement column of pixel (row, col) is (col + shift_by_row[row]) mod width.  The device table holds the
+// shifts reduced to [0, width), so the kernel's mod is one compare.
+int vofod_set_column_shift(vofod_handle* h, const int32_t* shift_by_row)
+{
+  if (!h)
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  (void)hipSetDevice(h->device);
+  VCHK(busy_check(h, true, true));  // (a batch in flight may not have run its decode yet)
+  const int64_t w = h->sp.sensor_hrays;
+  std::vector<uint32_t> red(static_cast<size_t>(std::max(h->sp.sensor_vrays, 1)), 0u);
+  if (shift_by_row && w > 0)
+    for (int32_t r = 0; r < h->sp.sensor_vrays; r++)
+      red[r] = static_cast<uint32_t>(((static_cast<int64_t>(shift_by_row[r]) % w) + w) % w);
+  HIPCHK(hipMemcpyAsync(h->d_col_shift, red.data(), sizeof(uint32_t) * red.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VOFOD_OK;
+}
+
+int vofod_column_poses(const float tf_begin[12], const float tf_end[12], const float tf_ref[12], const double* frac, int32_t n, float* col_tfs)
+{
+  using namespace colposes;
+  if (!tf_begin || !tf_end || !tf_ref || !col_tfs || n <= 0)
+    return VOFOD_ERR_INVALID_ARG;
+  const Quat q0 = from_tf(tf_begin), q1 = from_tf(tf_end), qr_inv = conj(from_tf(tf_ref));
+  double w[3], Rr_inv[3][3];
+  rotvec(mul(conj(q0), q1), w);
+  to_matrix(qr_inv, Rr_inv);
+  for (int32_t m = 0; m < n; m++)
+  {
+    const double f = frac ? frac[m] : (n > 1 ? static_cast<double>(m) / (n - 1) : 0.0);
+    const double fw[3] = {f * w[0], f * w[1], f * w[2]};
+    double R[3][3];
+    to_matrix(mul(qr_inv, mul(q0, from_rotvec(fw))), R);
+    double d[3];
+    for (int a = 0; a < 3; a++)
+      d[a] = (static_cast<double>(tf_begin[4 * a + 3]) + f * (static_cast<double>(tf_end[4 * a + 3]) - tf_begin[4 * a + 3])) - tf_ref[4 * a + 3];
+    float* out = col_tfs + 12 * static_cast<size_t>(m);
+    for (int i = 0; i < 3; i++)
+    {
+      for (int j = 0; j < 3; j++)
+        out[4 * i + j] = static_cast<float>(R[i][j]);
+      out[4 * i + 3] = static_cast<float>(Rr_inv[i][0] * d[0] + Rr_inv[i][1] * d[1] + Rr_inv[i][2] * d[2]);
+    }
+  }
   return VOFOD_OK;
 }
 

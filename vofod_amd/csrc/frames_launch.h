@@ -160,6 +160,65 @@ int route_submitted(vofod_handle* h, const Workspace& ws, uint32_t n, LaunchRout
 // a range image (include/vofod.h): no point columns, only the sensor's range column
 inline bool is_range_image(const vofod_scan& s) { return !s.x && !s.y && !s.z && s.range; }
 
+// a pose per column (vofod_scan::col_tfs): range images only; a device-resident table is read in place with 4-byte loads at least
+inline int check_col_tfs(vofod_handle* h, const vofod_scan& s)
+{
+  if (!s.col_tfs)
+    return VOFOD_OK;
+  if (!is_range_image(s))
+  {
+    h->err = "col_tfs: only a range image (x == y == z == NULL) may carry a pose per column";
+    return VOFOD_ERR_INVALID_ARG;
+  }
+  if (s.memspace == VOFOD_MEM_DEVICE && reinterpret_cast<uintptr_t>(s.col_tfs) % 4 != 0)
+  {
+    h->err = "device-resident col_tfs: the table must be 4-byte aligned";
+    return VOFOD_ERR_INVALID_ARG;
+  }
+  return VOFOD_OK;
+}
+
+// Pose tables of the batch's motion jobs (in frame order, as the jobs are): device-resident tables are read where they lie,
+// host-resident ones go to the workspace's pose block - table j of the list into slot j - with ONE 2-D copy when they lie at a
+// constant pitch (one numpy block per batch), otherwise one copy each.  On the stream of the staging copies, in front of the event
+// vofod_batch_submit waits for: the caller may overwrite its tables when submit returns.
+int stage_pose_tables(vofod_handle* h, Workspace& ws, const vofod_scan* scans, uint32_t n)
+{
+  const size_t tab = static_cast<size_t>(h->sp.sensor_hrays) * 12;  // floats per table
+  std::vector<const float*> host;                                     // the host tables, and the job each belongs to
+  std::vector<uint32_t> job_of;
+  uint32_t j = 0;
+  for (uint32_t f = 0; f < n; f++)
+  {
+    if (!scans[f].col_tfs)
+      continue;
+    if (scans[f].memspace != VOFOD_MEM_DEVICE)
+    {
+      host.push_back(scans[f].col_tfs);
+      job_of.push_back(j);
+    }
+    j++;
+  }
+  if (!host.empty())
+  {
+    if (!ws.d_poses)
+      HIPCHK(ws.d_poses.alloc(static_cast<size_t>(ws.F) * tab));
+    for (uint32_t k = 0; k < host.size(); k++)
+      ws.h_mjobs.p[job_of[k]].poses = ws.d_poses + static_cast<size_t>(k) * tab;
+    const ptrdiff_t pitch = host.size() >= 2 ? reinterpret_cast<const char*>(host[1]) - reinterpret_cast<const char*>(host[0]) : 0;
+    bool constant = pitch >= static_cast<ptrdiff_t>(tab * sizeof(float));
+    for (size_t k = 2; k < host.size() && constant; k++)
+      constant = reinterpret_cast<const char*>(host[k]) == reinterpret_cast<const char*>(host[0]) + static_cast<ptrdiff_t>(k) * pitch;
+    if (constant)
+      HIPCHK(hipMemcpy2DAsync(ws.d_poses, tab * sizeof(float), host[0], static_cast<size_t>(pitch), tab * sizeof(float), host.size(), hipMemcpyHostToDevice, h->stream));
+    else
+      for (size_t k = 0; k < host.size(); k++)
+        HIPCHK(hipMemcpyAsync(ws.d_poses + k * tab, host[k], tab * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  }
+  HIPCHK(hipMemcpyAsync(ws.d_mjobs, ws.h_mjobs, sizeof(vrm::MotionJob) * ws.n_mjobs, hipMemcpyHostToDevice, h->stream));
+  return VOFOD_OK;
+}
+
 // ---- stage inputs (filterAndTransform :621-684 reads them)
 // (the re-run of a batch that overflowed the LDS kernels keeps the frame arguments and the staged columns of its first
 // launch: the caller's host buffers need not outlive vofod_batch_submit)
@@ -173,8 +232,16 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
 {
   bool staged_2d = false;
   ws.det_valid = false;  // (the workspace is taken: what vofod_detection_points answered from is about to be overwritten)
-  ws.n_rjobs = 0;
+  ws.n_rjobs = ws.n_mjobs = 0;
   auto slot = [&](uint32_t f) { return ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5; };
+  // a range image goes to one of the two job lists: with a pose per column to k_range_decode_motion's (its table: the caller's, for
+  // now), without to k_range_decode's
+  auto add_job = [&](const vofod_scan& s, const vrd::RangeJob& job) {
+    if (s.col_tfs)
+      ws.h_mjobs.p[ws.n_mjobs++] = vrm::MotionJob{job.src, job.dst, job.stride, s.col_tfs};
+    else
+      ws.h_rjobs.p[ws.n_rjobs++] = job;
+  };
   // the frame's arguments point at the packed x | y | z columns of its staging slot (copied there, or decoded there by k_range_decode)
   auto slot_args = [&](uint32_t f) {
     float* base = slot(f);
@@ -218,7 +285,7 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
       for (uint32_t f = 0; f < n; f++)
       {
         VCHK(slot_args(f));
-        ws.h_rjobs.p[ws.n_rjobs++] = vrd::RangeJob{reinterpret_cast<const char*>(slot(f) + 4 * static_cast<size_t>(ws.pt_cap)), slot(f), 4, 0};
+        add_job(scans[f], vrd::RangeJob{reinterpret_cast<const char*>(slot(f) + 4 * static_cast<size_t>(ws.pt_cap)), slot(f), 4, 0});
       }
       staged_2d = true;
     }
@@ -247,16 +314,56 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
       return VOFOD_ERR_INVALID_ARG;
     }
     VCHK(slot_args(f));
-    ws.h_rjobs.p[ws.n_rjobs++] = job;
+    add_job(s, job);
   }
   if (ws.n_rjobs)
     HIPCHK(hipMemcpyAsync(ws.d_rjobs, ws.h_rjobs, sizeof(vrd::RangeJob) * ws.n_rjobs, hipMemcpyHostToDevice, h->stream));
+  if (ws.n_mjobs)
+    VCHK(stage_pose_tables(h, ws, scans, n));
+  return VOFOD_OK;
+}
+
+// k_range_decode_motion over the second job list (range images with a pose per column): one launch per batch that has such a frame
+int decode_ranges_motion(vofod_handle* h, Workspace& ws, size_t npts)
+{
+  if (!ws.n_mjobs)
+    return VOFOD_OK;
+  bool vec = npts % 4 == 0 && ws.pt_cap % 4 == 0, pose16 = true;
+  for (uint32_t j = 0; j < ws.n_mjobs; j++)
+  {
+    const vrm::MotionJob& job = ws.h_mjobs.p[j];
+    vec = vec && job.stride == 4 && reinterpret_cast<uintptr_t>(job.src) % 16 == 0;
+    pose16 = pose16 && reinterpret_cast<uintptr_t>(job.poses) % 16 == 0;
+  }
+  vrm::MotionBox box;
+  for (int a = 0; a < 3; a++)  // the bounds of the first crop: the expressions of fill_grid_params
+  {
+    box.hi[a] = h->exclude_center[a] + h->sp.exclude_size[a] / 2;
+    box.lo[a] = h->exclude_center[a] - h->sp.exclude_size[a] / 2;
+  }
+  const uint32_t chunk = std::min(std::max(ws.n_mjobs / 16u, 1u), vrm::RM_CHUNK_MAX);
+  const uint32_t n_px = static_cast<uint32_t>(npts), threads = vec ? n_px / 4u : n_px, width = static_cast<uint32_t>(h->sp.sensor_hrays);
+  const dim3 grid((threads + vrm::RM_THREADS - 1) / vrm::RM_THREADS, (ws.n_mjobs + chunk - 1) / chunk);
+#define VOFOD_MOTION_LAUNCH(V, P)                                                                                                                                                   \
+  KLAUNCH_AS(h, "k_range_decode_motion", (vrm::k_range_decode_motion<V, P>), grid, dim3(vrm::RM_THREADS), ws.d_mjobs.p, ws.n_mjobs, chunk, n_px, width, ws.pt_cap, h->d_lut_dirs.p, \
+             h->d_lut_offs.p, h->d_col_shift.p, box)
+  if (vec && pose16)
+    VOFOD_MOTION_LAUNCH(true, true);
+  else if (vec)
+    VOFOD_MOTION_LAUNCH(true, false);
+  else if (pose16)
+    VOFOD_MOTION_LAUNCH(false, true);
+  else
+    VOFOD_MOTION_LAUNCH(false, false);
+#undef VOFOD_MOTION_LAUNCH
+  HIPCHK(hipGetLastError());
   return VOFOD_OK;
 }
 
 // k_range_decode over the job list stage_inputs left in the workspace: one launch per batch, on the stream of the staging copies
 int decode_ranges(vofod_handle* h, Workspace& ws, size_t npts)
 {
+  VCHK(decode_ranges_motion(h, ws, npts));
   if (!ws.n_rjobs)
     return VOFOD_OK;
   bool vec = npts % 4 == 0 && ws.pt_cap % 4 == 0;
@@ -508,6 +615,7 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
     const vofod_scan& s = call.scans[f];
     if ((!s.x || !s.y || !s.z) && !is_range_image(s))  // (one or two of the three NULL, or no range column either)
       return VOFOD_ERR_INVALID_ARG;
+    VCHK(check_col_tfs(h, s));
     if (static_cast<size_t>(s.width) * s.height != npts)  // :895-899
       return VOFOD_ERR_SIZE_MISMATCH;
   }

@@ -33,6 +33,7 @@
 #include "kernels_voxelize.h"
 #include "mapsync.h"
 #include "range_decode.h"
+#include "range_motion.h"
 #include "detection_points.h"
 #include "map_shift.h"
 
@@ -341,6 +342,12 @@ struct Workspace
   DevBuf<vrd::RangeJob> d_rjobs;
   PinBuf<vrd::RangeJob> h_rjobs;
   uint32_t n_rjobs = 0;
+  // ... and those that carry a pose per column (range_motion.h): a job list of their own, and the block host-resident pose tables are
+  // staged into - F * width * 12 floats, allocated on the first such scan of this workspace
+  DevBuf<vrm::MotionJob> d_mjobs;
+  PinBuf<vrm::MotionJob> h_mjobs;
+  uint32_t n_mjobs = 0;
+  DevBuf<float> d_poses;
   DevBuf<PackedFrame> d_packed;
   PinBuf<PackedFrame> h_packed;
   DevBuf<PackedLite> d_lite;
@@ -468,6 +475,8 @@ private:
     HIP_TRY(d_stage.alloc(5 * static_cast<size_t>(F_) * pt_cap_));
     HIP_TRY(d_rjobs.alloc(F_));
     HIP_TRY(h_rjobs.alloc(F_));
+    HIP_TRY(d_mjobs.alloc(F_));
+    HIP_TRY(h_mjobs.alloc(F_));
     HIP_TRY(d_packed.alloc(F_));
     HIP_TRY(d_lite.alloc(F_));
     HIP_TRY(d_tailc.alloc(vtd::TP_MAXC * static_cast<size_t>(F_)));
@@ -587,6 +596,7 @@ struct vofod_handle
 
   DevBuf<float> d_lut_dirs, d_lut_offs;
   DevBuf<uint8_t> d_mask;
+  DevBuf<uint32_t> d_col_shift;  // vofod_set_column_shift: one shift per row, reduced to [0, width); zeros until set
 
   Workspace ws, aux, sepws;
   ExploreBufs explore;

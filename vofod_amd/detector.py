@@ -38,12 +38,17 @@ class ScanData:
     stride_bytes: int = 4
     memspace: int = capi.MEM_HOST
     stamp: float = 0.0
+    col_tfs: object = None  # range images only: float32 [width, 3, 4] (or a device address), a pose per measurement column
 
     @classmethod
-    def range_image(cls, range, width: int, height: int, intensity=None, stride_bytes: int = 4, memspace: int = capi.MEM_HOST, stamp: float = 0.0) -> "ScanData":
+    def range_image(cls, range, width: int, height: int, intensity=None, stride_bytes: int = 4, memspace: int = capi.MEM_HOST, stamp: float = 0.0, col_tfs=None) -> "ScanData":
         """A range image (include/vofod.h): no point columns, only the sensor's uint32 millimetres (`width * height` of them at
-        `stride_bytes`, pixel order of the handle's LUT); the product library rebuilds the points on the device."""
-        return cls(x=None, y=None, z=None, width=width, height=height, intensity=intensity, range=range, stride_bytes=stride_bytes, memspace=memspace, stamp=stamp)
+        `stride_bytes`, pixel order of the handle's LUT); the product library rebuilds the points on the device.  `col_tfs`: a
+        C-contiguous float32 array of `width` row-major 3x4 poses in the scan's memspace (or a device address) - the scan is
+        motion-compensated column by column (include/vofod.h, MOTION COMPENSATION)."""
+        if isinstance(col_tfs, np.ndarray):
+            assert col_tfs.dtype == np.float32 and col_tfs.flags["C_CONTIGUOUS"] and col_tfs.size == 12 * width, "col_tfs: float32, C order, width * 12 values"
+        return cls(x=None, y=None, z=None, width=width, height=height, intensity=intensity, range=range, stride_bytes=stride_bytes, memspace=memspace, stamp=stamp, col_tfs=col_tfs)
 
     def as_c(self) -> capi.Scan:
         def p(a):
@@ -60,6 +65,7 @@ class ScanData:
         s.width, s.height = self.width, self.height
         s.memspace = self.memspace
         s.stamp = self.stamp
+        s.col_tfs = p(self.col_tfs)
         return s
 
 
@@ -183,6 +189,11 @@ class VoFOD:
                 self.sp.oparea_offset[a] = o[a]
             self.map_offset = tuple(self.status().map_offset)
         return st
+
+    def set_column_shift(self, shift_by_row=None, allow: Sequence[int] = ()):
+        """vofod_set_column_shift: pixel (row, col) was measured in column (col + shift_by_row[row]) mod width; None = zeros"""
+        sh = None if shift_by_row is None else np.ascontiguousarray(shift_by_row, dtype=np.int32).reshape(self.sp.sensor_vrays)
+        return self._check(self.lib.set_column_shift(self.h, capi.ptr(sh)), "vofod_set_column_shift", allow)
 
     # ------------------------------------------------- snapshots and deltas
     def export_map(self, maps: int = capi.MAPS_ALL, full: bool = True) -> np.ndarray:
@@ -434,6 +445,18 @@ def cluster(lib, pts, keys, grid, tolerance, handle=None):
     if st != capi.OK:
         raise VofodError(st, "vofod_cluster")
     return labels[: p.size].copy(), nc.value
+
+
+def column_poses(lib, tf_begin, tf_end, tf_ref, n: int, frac=None) -> np.ndarray:
+    """vofod_column_poses: [n, 3, 4] float32, col_tfs[m] = tf_ref^-1 o P(frac[m]) with P interpolating the two sensor->world poses
+    (frac None: m / (n - 1)); what ScanData.range_image(col_tfs=...) takes"""
+    a, b, r = (np.ascontiguousarray(t, dtype=np.float32).reshape(12) for t in (tf_begin, tf_end, tf_ref))
+    fr = None if frac is None else np.ascontiguousarray(frac, dtype=np.float64).reshape(n)
+    out = np.zeros((max(n, 0), 3, 4), dtype=np.float32)
+    st = lib.column_poses(capi.ptr(a), capi.ptr(b), capi.ptr(r), capi.ptr(fr), n, capi.ptr(out))
+    if st != capi.OK:
+        raise VofodError(st, "vofod_column_poses")
+    return out
 
 
 def load_cloud(lib, filename: str) -> np.ndarray:

@@ -102,21 +102,14 @@ class SynthScan:
     keep: list = field(default_factory=list)
 
 
-def make_scan(scene: Scene, tf: np.ndarray, sensor="os1-128", seed: int = 0, noise_sigma: float = 0.02) -> SynthScan:
-    """`sensor`: a name of SENSORS, or (vrays, hrays, vfov_deg, max_range_m) itself"""
-    h, w, vfov_deg, max_range = SENSORS[sensor] if isinstance(sensor, str) else sensor
-    vfov = np.float32(np.deg2rad(vfov_deg))
-    rng = np.random.default_rng(seed + 104729)
-    dirs_s = sim_lut(w, h, float(vfov)).astype(np.float64)
-    R = tf[:, :3].astype(np.float64)
-    o = tf[:, 3].astype(np.float64)
-    d = dirs_s @ R.T  # world directions
+def _cast_rays(scene: Scene, o: np.ndarray, d: np.ndarray) -> np.ndarray:
+    """exact distance along each ray `o + t d` to the nearest surface of the scene (inf: none); `o`: one origin [3] or one per ray [n, 3]"""
     n = d.shape[0]
     best = np.full(n, np.inf)
     # ground sheet z = 0
     with np.errstate(divide="ignore", invalid="ignore"):
-        tg = -o[2] / d[:, 2]
-        gx, gy = o[0] + tg * d[:, 0], o[1] + tg * d[:, 1]
+        tg = -o[..., 2] / d[:, 2]
+        gx, gy = o[..., 0] + tg * d[:, 0], o[..., 1] + tg * d[:, 1]
         x0, x1, y0, y1 = scene.ground_rect
         ok = (tg > 0) & (gx >= x0) & (gx <= x1) & (gy >= y0) & (gy <= y1)
         best = np.where(ok, tg, best)
@@ -129,6 +122,12 @@ def make_scan(scene: Scene, tf: np.ndarray, sensor="os1-128", seed: int = 0, noi
             tmax = np.nanmin(np.maximum(t1, t2), axis=1)
             hit = (tmax >= np.maximum(tmin, 0.0)) & (tmin > 0)
             best = np.where(hit & (tmin < best), tmin, best)
+    return best
+
+
+def _measure(best, dirs_s, max_range, rng, noise_sigma):
+    """noise, validity, quantisation to uint32 millimetres, and the rigid points ouster_ros publishes for those ranges"""
+    n = best.shape[0]
     rng_m = best + rng.normal(0.0, noise_sigma, size=n)
     valid = np.isfinite(best) & (rng_m > 0.3) & (rng_m <= max_range)
     range_mm = np.where(valid, np.round(rng_m * 1000.0), 0).astype(np.uint32)
@@ -138,8 +137,49 @@ def make_scan(scene: Scene, tf: np.ndarray, sensor="os1-128", seed: int = 0, noi
     y = (dirs32[:, 1] * r32).astype(np.float32)
     z = (dirs32[:, 2] * r32).astype(np.float32)
     intensity = rng.uniform(0.0, 1000.0, size=n).astype(np.float32)
+    return range_mm, x, y, z, intensity
+
+
+def make_scan(scene: Scene, tf: np.ndarray, sensor="os1-128", seed: int = 0, noise_sigma: float = 0.02) -> SynthScan:
+    """`sensor`: a name of SENSORS, or (vrays, hrays, vfov_deg, max_range_m) itself"""
+    h, w, vfov_deg, max_range = SENSORS[sensor] if isinstance(sensor, str) else sensor
+    vfov = np.float32(np.deg2rad(vfov_deg))
+    rng = np.random.default_rng(seed + 104729)
+    dirs_s = sim_lut(w, h, float(vfov)).astype(np.float64)
+    R = tf[:, :3].astype(np.float64)
+    o = tf[:, 3].astype(np.float64)
+    d = dirs_s @ R.T  # world directions
+    best = _cast_rays(scene, o, d)
+    range_mm, x, y, z, intensity = _measure(best, dirs_s, max_range, rng, noise_sigma)
     scan = ScanData(x=x, y=y, z=z, width=w, height=h, intensity=intensity, range=range_mm, stride_bytes=4)
     return SynthScan(scan=scan, tf=tf.astype(np.float32), x=x, y=y, z=z, intensity=intensity, range=range_mm)
+
+
+def measurement_columns(w: int, h: int, col_shift=None) -> np.ndarray:
+    """[h * w] measurement column of every pixel: m = (col + col_shift[row]) mod w (vofod_set_column_shift)"""
+    sh = np.zeros(h, dtype=np.int64) if col_shift is None else np.asarray(col_shift, dtype=np.int64).reshape(h)
+    return ((np.arange(w, dtype=np.int64)[None, :] + sh[:, None]) % w).reshape(-1)
+
+
+def make_moving_scan(scene: Scene, tf_ref: np.ndarray, col_tfs: np.ndarray, sensor="os1-128", col_shift=None, seed: int = 0, noise_sigma: float = 0.02) -> SynthScan:
+    """A scan taken while the sensor moves: the ray of pixel (row, col) is cast from the pose `tf_ref o col_tfs[m]`, m its
+    measurement column (`col_tfs`: [w, 3, 4], as vofod_column_poses builds it; `tf_ref`: the scan's reference sensor -> world
+    pose).  Returns the range image and intensity the sensor delivers and the RIGID x, y, z ouster_ros would publish for them -
+    the points a caller without a pose per column hands over; `tf` of the result is `tf_ref`."""
+    h, w, vfov_deg, max_range = SENSORS[sensor] if isinstance(sensor, str) else sensor
+    vfov = np.float32(np.deg2rad(vfov_deg))
+    rng = np.random.default_rng(seed + 104729)
+    dirs_s = sim_lut(w, h, float(vfov)).astype(np.float64)
+    T = np.asarray(col_tfs, dtype=np.float64).reshape(w, 3, 4)
+    Rr, tr = np.asarray(tf_ref, dtype=np.float64)[:, :3], np.asarray(tf_ref, dtype=np.float64)[:, 3]
+    Rw = np.einsum("ij,mjk->mik", Rr, T[:, :, :3])  # sensor at column m -> world
+    ow = T[:, :, 3] @ Rr.T + tr
+    m = measurement_columns(w, h, col_shift)
+    d = np.einsum("nij,nj->ni", Rw[m], dirs_s)
+    best = _cast_rays(scene, ow[m], d)
+    range_mm, x, y, z, intensity = _measure(best, dirs_s, max_range, rng, noise_sigma)
+    scan = ScanData(x=x, y=y, z=z, width=w, height=h, intensity=intensity, range=range_mm, stride_bytes=4)
+    return SynthScan(scan=scan, tf=np.asarray(tf_ref, dtype=np.float32), x=x, y=y, z=z, intensity=intensity, range=range_mm)
 
 
 def apriori_points(scene: Scene, voxel_size: float, n_voxels: int | None = None, seed: int = 0, solid_ground_to: float | None = None) -> np.ndarray:
