@@ -154,10 +154,29 @@ enum { VOFOD_MEM_HOST = 0, VOFOD_MEM_DEVICE = 1 };
  * non-finite points.  A return that enters the box only through the compensation is removed by the unchanged first crop.
  * vofod_process_scan, vofod_process_batch, vofod_batch_submit and vofod_range_to_points accept such scans (a batch may mix them with
  * plain range images and point scans); the caller may overwrite its pose tables when the call returns, as it may its scans.
- * vofod_raycast_begin and the raycast half of VOFOD_SCAN_AUTO_RAYCAST IGNORE col_tfs: they cast the rigid rays the reference casts,
- * from `range` and the LUT.  col_tfs on a point scan (x, y, z given) is VOFOD_ERR_INVALID_ARG, and so is a device-resident table
+ * vofod_raycast_begin and the raycast half of VOFOD_SCAN_AUTO_RAYCAST IGNORE col_tfs unless vofod_set_raycast_motion has switched
+ * the compensated rays on (below): by default they cast the rigid rays the reference casts, from `range` and the LUT.  col_tfs on a
+ * point scan (x, y, z given) is VOFOD_ERR_INVALID_ARG, and so is a device-resident table
  * that is not 4-byte aligned.  sizeof(vofod_scan) is 80 (72 before the field): callers recompile; a zero-initialised scan
  * (`vofod_scan s{}`) is rigid.  The CPU oracle has no motion input: it rejects range images as before and ignores the field. */
+/* MOTION-COMPENSATED RAYS.  With vofod_set_raycast_motion(h, 1) the raycast role casts the ray of every pixel of a scan that carries
+ * col_tfs from that pixel's own pose.  For pixel i = row * width + col, with m = (col + shift_by_row[row]) mod width as above,
+ * T = col_tfs[m], d = lut_directions[3i..] and o = lut_offsets[3i..] (zeros when the handle has none), the beam is DEFINED as (IEEE
+ * float32, each operation rounded once, nothing fused)
+ *     d'[k] = ((T[k][0]*d[0]) + (T[k][1]*d[1])) + (T[k][2]*d[2])
+ *     o'[k] = (((T[k][0]*o[0]) + (T[k][1]*o[1])) + (T[k][2]*o[2])) + T[k][3]                 k = 0, 1, 2
+ * and everything else is the rigid pass with d', o' in place of the LUT entries: dir = R d' and start = (R o') + t with the call's
+ * `tf` in the same association, the intensity gate and the `!mask && range == 0` rule, length = range == 0 ? max_distance :
+ * min(range * 0.001f - voxel_size, max_distance), the in-limits test of each ray's own start, VOFOD_ERR_SENSOR_OUTSIDE_MAP decided
+ * by the origin of the call's `tf`, and the walk of VoxelMap::forEachRay with its running tmax.  The two matrices are never
+ * multiplied together.  The association is the rigid pass's own, so an identity table gives d' == d and o' == o as values (a zero
+ * may change its sign; the walk reads only the magnitude of a zero component and compares it) - the rigid rays.  No exclude-box rule
+ * applies: the reference casts the airframe's short rays too, and length <= 0 stops them.  The rotation part of T is taken as
+ * given: a T that is not orthonormal scales d' and with it the walk's parameter (lengths are then measured in units of |d'|).
+ * The table lives in the scan's memspace; a device-resident table must be 4-byte aligned (VOFOD_ERR_INVALID_ARG).  With the switch on
+ * vofod_raycast_begin accepts col_tfs on a point scan too - the role reads `range` and `intensity` only, and a caller that deskews
+ * its own points still wants the rays; vofod_process_scan keeps rejecting col_tfs on point scans.  A scan without col_tfs, and any
+ * scan while the switch is off, is cast rigidly exactly as before. */
 typedef struct vofod_scan {
   const void* x;          /* float */
   const void* y;          /* float */
@@ -453,6 +472,11 @@ int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, flo
  * image - pixel_shift_by_row of the sensor's metadata; a staggered image (columns are measurement columns) needs zeros.  Kept
  * across vofod_reset, vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch is pending. */
 int vofod_set_column_shift(vofod_handle* h, const int32_t* shift_by_row /* height ints; NULL = zeros */);
+/* vofod_set_raycast_motion: a handle property like the column shifts; `on` is taken as on != 0.  Off after vofod_create: the raycast
+ * role ignores col_tfs.  On: vofod_raycast_begin and the raycast half of VOFOD_SCAN_AUTO_RAYCAST cast a scan that carries col_tfs
+ * ray by ray from the columns' poses (MOTION-COMPENSATED RAYS at vofod_scan; k_raycast_motion).  Kept across vofod_reset,
+ * vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch or a raycast pass is pending. */
+int vofod_set_raycast_motion(vofod_handle* h, int on);
 /* Host helper (no handle, no device): the pose table of a scan from two sensor->world poses.
  *     col_tfs[m] = tf_ref^-1 o P(frac[m]),   m = 0 .. n-1,   frac == NULL: frac[m] = m / (n - 1) (0 when n == 1)
  * P(f) interpolates tf_begin (f = 0) and tf_end (f = 1): translation linear, rotation R0 * exp(f * log(R0^T R1)) on the shortest

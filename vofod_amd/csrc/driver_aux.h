@@ -65,7 +65,9 @@ int sep_ensure_pts(vofod_handle* h, size_t n)
 
 // ------------------------------------------------------------------ raycast_cloud :1397-1605
 
-int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf[12])
+// d_staged_poses: the device copy of the scan's pose table where the caller has staged it already (VOFOD_SCAN_AUTO_RAYCAST: the decode
+// of this very scan read it), nullptr otherwise
+int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf[12], const float* d_staged_poses)
 {
   const vofod_dyn_params& dp = h->dp;
   if (h->raycast_pending)
@@ -76,6 +78,14 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
     return VOFOD_ERR_INVALID_ARG;
   if (scan->height != h->sp.sensor_vrays || scan->width != h->sp.sensor_hrays)
     return VOFOD_ERR_SIZE_MISMATCH;
+  // vofod_set_raycast_motion: a scan with a pose per column casts each ray from its own pose (k_raycast_motion); a point scan may
+  // carry the table here (the role reads range and intensity only)
+  const bool motion = h->raycast_motion && scan->col_tfs;
+  if (motion && scan->memspace == VOFOD_MEM_DEVICE && reinterpret_cast<uintptr_t>(scan->col_tfs) % 4 != 0)
+  {
+    h->err = "device-resident col_tfs: the table must be 4-byte aligned";
+    return VOFOD_ERR_INVALID_ARG;
+  }
   h->raycast_start_its = h->detection_its;
   h->raycast_pending = true;
   const uint32_t n = static_cast<uint32_t>(scan->width) * scan->height;
@@ -132,10 +142,33 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
   int o[3];
   h->hg.coordToIdx(rp.origin, o);
   int ret = VOFOD_OK;
-  if (h->hg.inLimits(o))  // :1432
-    KLAUNCH(h, vr::k_raycast, dim3((n + 255) / 256), dim3(256), rp, h->mg, d_int, d_rng, stride, h->d_lut_dirs, h->d_lut_offs, h->d_mask, h->d_ray, reinterpret_cast<uint32_t*>(h->d_counter + 1));
-  else
+  if (!h->hg.inLimits(o))  // :1432
     ret = VOFOD_ERR_SENSOR_OUTSIDE_MAP;
+  else if (motion)
+  {
+    // the table on the device: a device table where it lies, a host table in slot 0 of the synchronous workspace's pose block
+    // (copied on the stream, in front of the kernel; the call waits for both, so the caller's table is free when it returns)
+    const float* d_tab = scan->memspace == VOFOD_MEM_DEVICE ? scan->col_tfs : d_staged_poses;
+    if (!d_tab)
+    {
+      const size_t tab = static_cast<size_t>(h->sp.sensor_hrays) * 12;
+      if (!h->ws.d_poses)
+        HIPCHK(h->ws.d_poses.alloc(static_cast<size_t>(h->ws.F) * tab));
+      HIPCHK(hipMemcpyAsync(h->ws.d_poses, scan->col_tfs, tab * sizeof(float), hipMemcpyHostToDevice, h->stream));
+      d_tab = h->ws.d_poses;
+    }
+    const uint32_t width = static_cast<uint32_t>(scan->width);
+#define VOFOD_RAYCAST_MOTION_LAUNCH(P)                                                                                                                                                    \
+  KLAUNCH_AS(h, "k_raycast_motion", (vr::k_raycast_motion<P>), dim3((n + 255) / 256), dim3(256), rp, h->mg, d_int, d_rng, stride, h->d_lut_dirs.p, h->d_lut_offs.p, h->d_mask.p, d_tab, \
+             h->d_col_shift.p, width, h->d_ray.p, reinterpret_cast<uint32_t*>(h->d_counter + 1))
+    if (reinterpret_cast<uintptr_t>(d_tab) % 16 == 0)
+      VOFOD_RAYCAST_MOTION_LAUNCH(true);
+    else
+      VOFOD_RAYCAST_MOTION_LAUNCH(false);
+#undef VOFOD_RAYCAST_MOTION_LAUNCH
+  }
+  else
+    KLAUNCH(h, vr::k_raycast, dim3((n + 255) / 256), dim3(256), rp, h->mg, d_int, d_rng, stride, h->d_lut_dirs, h->d_lut_offs, h->d_mask, h->d_ray, reinterpret_cast<uint32_t*>(h->d_counter + 1));
   HIPCHK(hipStreamSynchronize(h->stream));
   return ret;
 }
@@ -1460,7 +1493,23 @@ int vofod_raycast_begin(vofod_handle* h, const vofod_scan* scan, const float tf[
   std::scoped_lock lck(h->mtx);
   (void)hipSetDevice(h->device);
   VCHK(busy_check(h, true, false));
-  return raycast_begin_locked(h, scan, tf);
+  return raycast_begin_locked(h, scan, tf, nullptr);
+}
+
+// A handle property, as the column shifts: off after vofod_create, kept across vofod_reset, vofod_map_apply and vofod_map_shift.
+int vofod_set_raycast_motion(vofod_handle* h, int on)
+{
+  if (!h)
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  VCHK(busy_check(h, true, true));
+  if (h->raycast_pending)
+  {
+    h->err = "a raycast pass is pending: finish it first";
+    return VOFOD_ERR_BUSY;
+  }
+  h->raycast_motion = on != 0;
+  return VOFOD_OK;
 }
 
 int vofod_raycast_finish(vofod_handle* h)

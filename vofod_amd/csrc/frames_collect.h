@@ -569,7 +569,7 @@ int collect_frames(vofod_handle* h, Workspace& ws, FrameCall& call, vofod_detect
       if (h->raycast_pending)
         raycast_finish_locked(h);
       else
-        raycast_begin_locked(h, &call.scans[0], call.tfs);
+        raycast_begin_locked(h, &call.scans[0], call.tfs, staged_pose_table(ws, call.scans[0]));
     }
   }
   double dev_ms[4] = {0, 0, 0, 0};

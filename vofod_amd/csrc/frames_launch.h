@@ -219,6 +219,10 @@ int stage_pose_tables(vofod_handle* h, Workspace& ws, const vofod_scan* scans, u
   return VOFOD_OK;
 }
 
+// the device copy of the pose table of the call's FIRST scan as stage_pose_tables left it in the workspace's job list (the jobs are in
+// frame order: a first scan with a table owns job 0); nullptr when the scan has none.  A re-run keeps the list of its first launch.
+inline const float* staged_pose_table(const Workspace& ws, const vofod_scan& s) { return s.col_tfs && ws.n_mjobs ? ws.h_mjobs.p[0].poses : nullptr; }
+
 // ---- stage inputs (filterAndTransform :621-684 reads them)
 // (the re-run of a batch that overflowed the LDS kernels keeps the frame arguments and the staged columns of its first
 // launch: the caller's host buffers need not outlive vofod_batch_submit)
@@ -507,7 +511,7 @@ int raycast_ahead_of_tail(vofod_handle* h, Workspace& ws, FrameCall& call)
     if (h->raycast_pending)
       raycast_finish_locked(h);
     else
-      raycast_begin_locked(h, &call.scans[0], call.tfs);
+      raycast_begin_locked(h, &call.scans[0], call.tfs, staged_pose_table(ws, call.scans[0]));
     call.rc_done = true;
   }
   return VOFOD_OK;

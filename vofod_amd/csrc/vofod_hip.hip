@@ -34,6 +34,7 @@
 #include "mapsync.h"
 #include "range_decode.h"
 #include "range_motion.h"
+#include "raycast_motion.h"
 #include "detection_points.h"
 #include "map_shift.h"
 
@@ -597,6 +598,7 @@ struct vofod_handle
   DevBuf<float> d_lut_dirs, d_lut_offs;
   DevBuf<uint8_t> d_mask;
   DevBuf<uint32_t> d_col_shift;  // vofod_set_column_shift: one shift per row, reduced to [0, width); zeros until set
+  bool raycast_motion = false;   // vofod_set_raycast_motion: the raycast role casts a scan with col_tfs ray by ray from the columns' poses (k_raycast_motion)
 
   Workspace ws, aux, sepws;
   ExploreBufs explore;
@@ -1699,7 +1701,7 @@ float map_cmax(const vofod_handle* h)
   return c + 2 * h->mg.vs;
 }
 
-int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf[12]);
+int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf[12], const float* d_staged_poses);
 int raycast_finish_locked(vofod_handle* h);
 
 int ensure_explore(vofod_handle* h, ExploreBufs& eb, uint32_t F, size_t n_jobs, size_t n_members)

@@ -195,6 +195,11 @@ class VoFOD:
         sh = None if shift_by_row is None else np.ascontiguousarray(shift_by_row, dtype=np.int32).reshape(self.sp.sensor_vrays)
         return self._check(self.lib.set_column_shift(self.h, capi.ptr(sh)), "vofod_set_column_shift", allow)
 
+    def set_raycast_motion(self, on: bool = True, allow: Sequence[int] = ()):
+        """vofod_set_raycast_motion: with it on, raycast_begin and the raycast half of SCAN_AUTO_RAYCAST cast a scan that carries
+        `col_tfs` ray by ray from the columns' poses; off (the state after creation) they cast the rigid rays"""
+        return self._check(self.lib.set_raycast_motion(self.h, int(bool(on))), "vofod_set_raycast_motion", allow)
+
     # ------------------------------------------------- snapshots and deltas
     def export_map(self, maps: int = capi.MAPS_ALL, full: bool = True) -> np.ndarray:
         """A full snapshot or a delta of the maps in `maps` (bitmask of 1 << capi.MAP_*) in the wire format of
