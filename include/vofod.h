@@ -177,6 +177,36 @@ enum { VOFOD_MEM_HOST = 0, VOFOD_MEM_DEVICE = 1 };
  * vofod_raycast_begin accepts col_tfs on a point scan too - the role reads `range` and `intensity` only, and a caller that deskews
  * its own points still wants the rays; vofod_process_scan keeps rejecting col_tfs on point scans.  A scan without col_tfs, and any
  * scan while the switch is off, is cast rigidly exactly as before. */
+/* EXACT RAYCAST ACCUMULATION.  With vofod_set_raycast_exact(h, 1) a raycast pass sums the in-voxel path lengths as fixed-point units
+ * in uint32 instead of floats, in the raycast map's own buffer: the sum does not depend on the order in which the rays arrive, so two
+ * passes of one scan - and the passes of two handles fed the same scans - end with the same bits.  The rays, their gates and their
+ * walk are those of the pass the other switches select (rigid, or MOTION-COMPENSATED RAYS); only what is added changes.
+ *   Scale.  S = log2(units per metre) is fixed per handle at vofod_create: the largest integer in [0, 24] with
+ *             n_pixels * (floor(2 * vs * 2^S) + 1) <= 2^32 - 1,     n_pixels = sensor_hrays * sensor_vrays,
+ *           vs = the float voxel_size widened to double, the rule evaluated in double on the host.  QMAX = floor(2 * vs * 2^S).
+ *           (OS1-128 at 0.25 m: S = 15; at 0.5 m: 14; 128 x 2048 at 0.1 m: 16; OS1-16 at 0.5 m: 17; a sensor of a hundred pixels: 24.)
+ *   Piece.  dd = the float min(dist, length) - prev of the walk's step (VoxelMap::forEachRay with its running tmax), unchanged.  Its
+ *           units are q = min(rint(dd * 2^S), QMAX): the product is exact (2^S is a power of two), rint rounds to nearest, ties to
+ *           even.  A piece with q == 0 leaves no trace.  The clamp can only bite when a pose table of the motion pass is not a
+ *           rotation (the walk's parameter is then not metres): an in-voxel piece stays below sqrt(3) * vs plus the drift of tmax.
+ *           It exists so that no voxel can overflow: every ray lays at most one piece into a voxel.
+ *   Sum.    U[v] = the sum of q over the pieces laid into voxel v, as uint32: exact, independent of order and grouping.
+ *   View.   r[v] = float(U[v]) * 2^-S: the uint32 -> float conversion rounds to nearest even, the scaling is exact.  While an exact
+ *           pass is pending vofod_read_map(VOFOD_MAP_RAYCAST) returns r (converted in the caller's copy; the device keeps U), and
+ *           vofod_raycast_finish sweeps with the same r, the old update rule's max_val being float(max U) * 2^-S.
+ *           VOFOD_ERR_RAYCAST_EMPTY means that all of U is zero.
+ * The representation belongs to the PASS: vofod_raycast_begin records the switch, vofod_raycast_finish sweeps what begin laid, and
+ * VOFOD_SCAN_AUTO_RAYCAST inherits both.  While an exact pass is pending, vofod_write_map and vofod_voxels_as_pc on
+ * VOFOD_MAP_RAYCAST return VOFOD_ERR_BUSY (the buffer holds units, not floats); vofod_map_shift refuses any pending pass already.
+ * Units never outlive their pass: a vofod_raycast_finish that abandons an exact pass (VOFOD_ERR_RAYCAST_NO_DETECTION) clears the
+ * raycast map to zeros, where an abandoned float pass leaves its lengths readable until the next begin; after
+ * VOFOD_ERR_RAYCAST_EMPTY the map is zero in both.  So outside a pending exact pass vofod_read_map, vofod_voxels_as_pc and
+ * vofod_map_export always see floats.
+ * Snapshots: the raycast map's bits travel as they are; byte 0 of the header's 16 reserved bytes holds S + 1 when the snapshot
+ * carries a pending exact pass with the raycast map in its mask, and 0 otherwise (such snapshots are byte for byte what they were).
+ * vofod_map_apply adopts the pass's representation with the bits and returns VOFOD_ERR_SIZE_MISMATCH when S is not the applying
+ * handle's own; the other 15 reserved bytes must be zero.  Against the float pass the view differs by at most 2^-(S+1) m per piece
+ * (the rounding of q) plus the float pass's own summation error.  With the switch off every launch and every bit is as before. */
 typedef struct vofod_scan {
   const void* x;          /* float */
   const void* y;          /* float */
@@ -477,6 +507,15 @@ int vofod_set_column_shift(vofod_handle* h, const int32_t* shift_by_row /* heigh
  * ray by ray from the columns' poses (MOTION-COMPENSATED RAYS at vofod_scan; k_raycast_motion).  Kept across vofod_reset,
  * vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch or a raycast pass is pending. */
 int vofod_set_raycast_motion(vofod_handle* h, int on);
+/* vofod_set_raycast_exact: a handle property with the rules of vofod_set_raycast_motion; `on` is taken as on != 0.  Off after
+ * vofod_create: raycast passes sum floats.  On: the passes vofod_raycast_begin and VOFOD_SCAN_AUTO_RAYCAST begin from now on sum
+ * fixed-point units (EXACT RAYCAST ACCUMULATION at vofod_scan; k_raycast_exact, k_ray_sweep_exact).  Kept across vofod_reset,
+ * vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch or a raycast pass is pending;
+ * VOFOD_ERR_INDEX_OVERFLOW when no S in [0, 24] satisfies the rule (a voxel size of hundreds of thousands of kilometres). */
+int vofod_set_raycast_exact(vofod_handle* h, int on);
+/* vofod_raycast_units: the raw U of the pending exact pass (n = the map's voxel count, x fastest as vofod_read_map) and S.
+ * VOFOD_ERR_NOT_PENDING: no exact pass is pending (none at all, or a float one); VOFOD_ERR_SIZE_MISMATCH: a wrong n. */
+int vofod_raycast_units(vofod_handle* h, uint32_t* units, size_t n, int32_t* log2_units_per_m);
 /* Host helper (no handle, no device): the pose table of a scan from two sensor->world poses.
  *     col_tfs[m] = tf_ref^-1 o P(frac[m]),   m = 0 .. n-1,   frac == NULL: frac[m] = m / (n - 1) (0 when n == 1)
  * P(f) interpolates tf_begin (f = 0) and tf_end (f = 1): translation linear, rotation R0 * exp(f * log(R0^T R1)) on the shortest
@@ -575,7 +614,8 @@ int vofod_allgather_detections(vofod_comm* comm, const vofod_detection* local, c
  *   28 f32[3] map offset (as vofod_status_info) | 40 f32 voxel size | 44 f32 score_init | 48 u64 base_gen (0 for full) |
  *   56 u64 new_gen | 64 i32 detection_its, u32 last_detection_id, i32 background_pts_sufficient, i32 sure_background_sufficient |
  *   80 i32 raycast_pending, i32 raycast_start_its | 88 u64[3] records per map (voxels, flags, raycast; 0 when not selected) |
- *   112 16 zero bytes
+ *   112 u8 S + 1 of a pending exact raycast pass that travels with the raycast map (EXACT RAYCAST ACCUMULATION at vofod_scan: the
+ *       raycast records are then uint32 units, 2^S per metre), else 0 | 113 15 zero bytes
  * followed, per selected map in that order, by u32 idx[n] and u32 bits[n].  Size = 128 + 8 * sum(n).
  *
  * Apply always restores detection_its, last_detection_id and both background latches; raycast_pending and raycast_start_its

@@ -82,6 +82,8 @@ sub["R14_MEASURED"] = "; ".join(parts) + "."
 sub["R15_MEASURED"] = (P / "r15_range_motion.txt").read_text().splitlines()[0].removeprefix("measured: ")
 # §5.12: the first line of profiles/r16_raycast_motion.txt
 sub["R16_MEASURED"] = (P / "r16_raycast_motion.txt").read_text().splitlines()[0].removeprefix("measured: ")
+# §5.13: the first line of profiles/r17_raycast_exact.txt
+sub["R17_MEASURED"] = (P / "r17_raycast_exact.txt").read_text().splitlines()[0].removeprefix("measured: ")
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

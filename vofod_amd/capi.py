@@ -296,12 +296,14 @@ _SIGS = {
     "set_column_shift": (C.c_int, [C.c_void_p, C.c_void_p]),
     "column_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "set_raycast_motion": (C.c_int, [C.c_void_p, C.c_int]),
+    "set_raycast_exact": (C.c_int, [C.c_void_p, C.c_int]),
+    "raycast_units": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_int32)]),
 }
 
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
-                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift", "set_column_shift", "column_poses", "set_raycast_motion")
+                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units")
 
 
 class MsgHeader(C.Structure):

@@ -88,6 +88,8 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
   }
   h->raycast_start_its = h->detection_its;
   h->raycast_pending = true;
+  const bool exact = h->raycast_exact;  // vofod_set_raycast_exact
+  const vr::ExactScale xs{exact ? std::ldexp(1.0f, h->ray_log2_units) : 0.0f, h->ray_qmax};
   const uint32_t n = static_cast<uint32_t>(scan->width) * scan->height;
   // stage intensity/range if they live on the host
   const char *d_int, *d_rng;
@@ -126,6 +128,10 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
     VCHK(fill_map(h, h->d_ray, 0.0f));
   }
   h->ray_dirty = true;
+  // The representation belongs to the pass: recorded here, behind the staging that can still fail and beside the clear - from here on
+  // the accumulator holds what this pass lays (read by finish, vofod_read_map, vofod_raycast_units and the snapshots).  A begin that
+  // failed above leaves a pending FLOAT pass over whatever floats the accumulator held, as it always did.
+  h->ray_pass_exact = exact;
   HIPCHK(hipMemsetAsync(h->d_counter + 1, 0, sizeof(unsigned long long), h->stream));
   vr::RayParams rp{};
   // [3P] Affine3f::rotation() == the linear part up to rounding for rigid transforms
@@ -161,14 +167,29 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
 #define VOFOD_RAYCAST_MOTION_LAUNCH(P)                                                                                                                                                    \
   KLAUNCH_AS(h, "k_raycast_motion", (vr::k_raycast_motion<P>), dim3((n + 255) / 256), dim3(256), rp, h->mg, d_int, d_rng, stride, h->d_lut_dirs.p, h->d_lut_offs.p, h->d_mask.p, d_tab, \
              h->d_col_shift.p, width, h->d_ray.p, reinterpret_cast<uint32_t*>(h->d_counter + 1))
-    if (reinterpret_cast<uintptr_t>(d_tab) % 16 == 0)
+#define VOFOD_RAYCAST_EXACT_LAUNCH(M, A, tab, shift, w)                                                                                                                                  \
+  KLAUNCH_AS(h, "k_raycast_exact", (vr::k_raycast_exact<M, A>), dim3((n + 255) / 256), dim3(256), rp, h->mg, xs, d_int, d_rng, stride, h->d_lut_dirs.p, h->d_lut_offs.p, h->d_mask.p, tab, \
+             shift, w, reinterpret_cast<uint32_t*>(h->d_ray.p), reinterpret_cast<uint32_t*>(h->d_counter + 1))
+    const bool aligned16 = reinterpret_cast<uintptr_t>(d_tab) % 16 == 0;
+    if (exact && aligned16)
+      VOFOD_RAYCAST_EXACT_LAUNCH(true, true, d_tab, h->d_col_shift.p, width);
+    else if (exact)
+      VOFOD_RAYCAST_EXACT_LAUNCH(true, false, d_tab, h->d_col_shift.p, width);
+    else if (aligned16)
       VOFOD_RAYCAST_MOTION_LAUNCH(true);
     else
       VOFOD_RAYCAST_MOTION_LAUNCH(false);
 #undef VOFOD_RAYCAST_MOTION_LAUNCH
   }
+  else if (exact)
+  {
+    const float* no_tab = nullptr;
+    const uint32_t* no_shift = nullptr;
+    VOFOD_RAYCAST_EXACT_LAUNCH(false, true, no_tab, no_shift, 0u);
+  }
   else
     KLAUNCH(h, vr::k_raycast, dim3((n + 255) / 256), dim3(256), rp, h->mg, d_int, d_rng, stride, h->d_lut_dirs, h->d_lut_offs, h->d_mask, h->d_ray, reinterpret_cast<uint32_t*>(h->d_counter + 1));
+#undef VOFOD_RAYCAST_EXACT_LAUNCH
   HIPCHK(hipStreamSynchronize(h->stream));
   return ret;
 }
@@ -178,9 +199,21 @@ int raycast_finish_locked(vofod_handle* h)
   if (!h->raycast_pending)
     return VOFOD_ERR_NOT_PENDING;
   h->raycast_pending = false;
+  const bool exact = h->ray_pass_exact;  // (what begin laid: units or floats)
+  h->ray_pass_exact = false;
   const vofod_dyn_params& dp = h->dp;
   if (h->detection_its == h->raycast_start_its)  // :1531-1537
+  {
+    // an abandoned exact pass takes its units with it: outside a pending exact pass the raycast map never holds anything but floats
+    // (vofod_read_map, vofod_voxels_as_pc and vofod_map_export read it as such)
+    if (exact)
+    {
+      VCHK(fill_map(h, h->d_ray, 0.0f));
+      HIPCHK(hipStreamSynchronize(h->stream));
+      h->ray_dirty = false;
+    }
     return VOFOD_ERR_RAYCAST_NO_DETECTION;
+  }
   vr::SweepParams sp{};
   sp.its_diff = static_cast<float>(h->detection_its - h->raycast_start_its);
   sp.ray_score = static_cast<float>(dp.voxel_map__scores__ray);
@@ -194,7 +227,16 @@ int raycast_finish_locked(vofod_handle* h)
   HIPCHK(hipStreamSynchronize(h->stream));
   if (static_cast<uint32_t>(h->h_counter[1]) == 0)
     return VOFOD_ERR_RAYCAST_EMPTY;  // :1544-1548 (flags stay as they are)
-  if (!sp.new_rule)
+  if (!sp.new_rule && exact)
+  {
+    // the integer max of U, converted by the rule of the float view: float(U) rounds to nearest even, the scaling is exact
+    HIPCHK(hipMemsetAsync(h->d_counter + 2, 0, sizeof(unsigned long long), h->stream));
+    KLAUNCH_AS(h, "k_max_units", vr::k_max_units, dim3(2048), dim3(256), reinterpret_cast<const uint32_t*>(h->d_ray.p), h->mg.n, reinterpret_cast<uint32_t*>(h->d_counter + 2));
+    HIPCHK(hipMemcpyAsync(h->h_counter + 2, h->d_counter + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    sp.max_val = std::ldexp(static_cast<float>(static_cast<uint32_t>(h->h_counter[2])), -h->ray_log2_units);
+  }
+  else if (!sp.new_rule)
   {
     HIPCHK(hipMemsetAsync(h->d_counter + 2, 0, sizeof(unsigned long long), h->stream));
     KLAUNCH(h, vr::k_max_nonneg, dim3(2048), dim3(256), h->d_ray, h->mg.n, reinterpret_cast<uint32_t*>(h->d_counter + 2));
@@ -203,7 +245,11 @@ int raycast_finish_locked(vofod_handle* h)
     const uint32_t bits = static_cast<uint32_t>(h->h_counter[2]);
     std::memcpy(&sp.max_val, &bits, 4);
   }
-  KLAUNCH(h, vr::k_ray_sweep, dim3(256 * 8), dim3(256), sp, h->mg.n, h->d_map, h->d_flags, h->d_ray);
+  if (exact)
+    KLAUNCH_AS(h, "k_ray_sweep_exact", vr::k_ray_sweep_exact, dim3(256 * 8), dim3(256), sp, std::ldexp(1.0f, -h->ray_log2_units), h->mg.n, h->d_map.p, h->d_flags.p,
+               reinterpret_cast<uint32_t*>(h->d_ray.p));
+  else
+    KLAUNCH(h, vr::k_ray_sweep, dim3(256 * 8), dim3(256), sp, h->mg.n, h->d_map, h->d_flags, h->d_ray);
   HIPCHK(hipStreamSynchronize(h->stream));
   h->ray_dirty = false;
   h->mapbits_valid = false;
@@ -904,6 +950,8 @@ int vofod_create(const vofod_static_params* sp, const vofod_dyn_params* dp, vofo
   CREATE_CHK(hipMemcpy(h->d_lut_dirs, dirs.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice));
   CREATE_CHK(hipMemcpy(h->d_lut_offs, offs.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice));
   CREATE_CHK(hipMemcpy(h->d_mask, mask.data(), n, hipMemcpyHostToDevice));
+  if (!vr::ray_exact_scale(sp->voxel_size, sp->sensor_hrays, sp->sensor_vrays, h->ray_log2_units, h->ray_qmax))
+    h->ray_log2_units = -1;
   CREATE_CHK(h->d_col_shift.alloc(static_cast<size_t>(sp->sensor_vrays)));
   CREATE_CHK(hipMemset(h->d_col_shift, 0, sizeof(uint32_t) * std::max(sp->sensor_vrays, 1)));
   // per-frame workspace: the crops bound the voxel-grid lattice by the map lattice plus one cell per side
@@ -1046,6 +1094,17 @@ int vofod_read_map(vofod_handle* h, int which, float* dst, size_t n)
     return VOFOD_ERR_SIZE_MISMATCH;
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(dst, m, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (which == VOFOD_MAP_RAYCAST && h->raycast_pending && h->ray_pass_exact)
+  {
+    // the float view of a pending exact pass, formed in the caller's copy (the device keeps the units)
+    const float inv = std::ldexp(1.0f, -h->ray_log2_units);
+    for (size_t i = 0; i < n; i++)
+    {
+      uint32_t u;
+      std::memcpy(&u, &dst[i], 4);
+      dst[i] = static_cast<float>(u) * inv;
+    }
+  }
   return VOFOD_OK;
 }
 
@@ -1058,6 +1117,11 @@ int vofod_voxels_as_pc(vofod_handle* h, int which, float threshold, int greater_
   const float* m = pick_map(h, which);
   if (!m)
     return VOFOD_ERR_INVALID_ARG;
+  if (which == VOFOD_MAP_RAYCAST && h->raycast_pending && h->ray_pass_exact)
+  {
+    h->err = "the raycast map holds the units of a pending exact pass: finish it first (vofod_read_map returns its float view)";
+    return VOFOD_ERR_BUSY;
+  }
   *n_out = 0;
   vr::SepState& s = h->sep;
   const uint32_t ncol = static_cast<uint32_t>(h->mg.sx) * h->mg.sy;
@@ -1115,6 +1179,11 @@ int vofod_write_map(vofod_handle* h, int which, const float* src, size_t n)
   float* m = pick_map(h, which);
   if (!m || n != h->mg.n)
     return VOFOD_ERR_SIZE_MISMATCH;
+  if (which == VOFOD_MAP_RAYCAST && h->raycast_pending && h->ray_pass_exact)
+  {
+    h->err = "the raycast map holds the units of a pending exact pass: finish it first";
+    return VOFOD_ERR_BUSY;
+  }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(m, src, n * sizeof(float), hipMemcpyHostToDevice));
   h->mapbits_valid = false;
@@ -1509,6 +1578,44 @@ int vofod_set_raycast_motion(vofod_handle* h, int on)
     return VOFOD_ERR_BUSY;
   }
   h->raycast_motion = on != 0;
+  return VOFOD_OK;
+}
+
+// A handle property with the rules of vofod_set_raycast_motion.  The switch chooses the representation of the NEXT pass; a pending
+// pass keeps its own (raycast_begin_locked records it), which is why the switch is refused while one is pending.
+int vofod_set_raycast_exact(vofod_handle* h, int on)
+{
+  if (!h)
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  VCHK(busy_check(h, true, true));
+  if (h->raycast_pending)
+  {
+    h->err = "a raycast pass is pending: finish it first";
+    return VOFOD_ERR_BUSY;
+  }
+  if (on && h->ray_log2_units < 0)
+  {
+    h->err = "exact raycast accumulation: sensor_hrays * sensor_vrays * (2 * voxel_size + 1) does not fit in 32 bits";
+    return VOFOD_ERR_INDEX_OVERFLOW;
+  }
+  h->raycast_exact = on != 0;
+  return VOFOD_OK;
+}
+
+int vofod_raycast_units(vofod_handle* h, uint32_t* units, size_t n, int32_t* log2_units_per_m)
+{
+  if (!h || !units || !log2_units_per_m)
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  (void)hipSetDevice(h->device);
+  if (!h->raycast_pending || !h->ray_pass_exact)
+    return VOFOD_ERR_NOT_PENDING;
+  if (n != h->mg.n)
+    return VOFOD_ERR_SIZE_MISMATCH;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(units, h->d_ray.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  *log2_units_per_m = h->ray_log2_units;
   return VOFOD_OK;
 }
 

@@ -146,6 +146,9 @@ int ms_export_locked(vofod_handle* h, int maps, int kind, uint8_t* d_dst, size_t
   hd.sure_background_sufficient = h->sure_background_sufficient;
   hd.raycast_pending = h->raycast_pending;
   hd.raycast_start_its = h->raycast_start_its;
+  // a pending exact pass whose units travel: byte 0 of the reserved block holds S + 1 (include/vofod.h, EXACT RAYCAST ACCUMULATION)
+  if (h->raycast_pending && h->ray_pass_exact && (maps >> VOFOD_MAP_RAYCAST & 1))
+    hd.zero[0] = static_cast<uint8_t>(h->ray_log2_units + 1);
   size_t off = sizeof(vms::WireHeader);
   const uint32_t nt = s.ntiles;
   const dim3 grid(std::min<uint32_t>(nt, vms::MS_GRID));
@@ -239,7 +242,10 @@ int ms_apply_locked(vofod_handle* h, const vms::WireHeader& hd, const uint8_t* d
     }
   }
   if (maps & (1 << VOFOD_MAP_RAYCAST))
+  {
+    h->ray_pass_exact = h->raycast_pending && hd.zero[0] != 0;  // (the representation travels with the bits; S was checked)
     h->ray_dirty = true;  // (the next raycast_begin clears the accumulator unless a finish sweeps it)
+  }
   h->sep_pending = false;  // a sepclusters pass of this handle belongs to the map it replaced
   for (int t = 0; t < vofod_handle::MAX_INFLIGHT; t++)
     h->slot(t)->det_valid = false;  // ... and so do the detections vofod_detection_points would answer for
@@ -268,12 +274,15 @@ int ms_check_header(vofod_handle* h, const vms::WireHeader& hd, size_t n_bytes)
     }
     total += hd.n_records[m];
   }
-  for (uint8_t z : hd.zero)
-    if (z)
-    {
-      h->err = "map apply: reserved header bytes are not zero";
-      return VOFOD_ERR_INVALID_ARG;
-    }
+  // byte 0 of the reserved block: S + 1 of a pending exact raycast pass that travels with its units, else 0; the other 15 are zero
+  bool reserved_ok = hd.zero[0] == 0 || (hd.raycast_pending != 0 && (hd.maps >> VOFOD_MAP_RAYCAST & 1) && hd.zero[0] <= vr::RX_MAX_LOG2 + 1);
+  for (size_t k = 1; k < sizeof(hd.zero); k++)
+    reserved_ok &= hd.zero[k] == 0;
+  if (!reserved_ok)
+  {
+    h->err = "map apply: reserved header bytes are not zero (byte 0 may hold S + 1 of a pending exact raycast pass)";
+    return VOFOD_ERR_INVALID_ARG;
+  }
   if (n_bytes != sizeof(vms::WireHeader) + 8 * total)
   {
     h->err = "map apply: length does not match the header's record counts";
@@ -286,6 +295,11 @@ int ms_check_header(vofod_handle* h, const vms::WireHeader& hd, size_t n_bytes)
   if (!same)
   {
     h->err = "map apply: map geometry (size, offset, voxel size, score_init) differs from this handle's";
+    return VOFOD_ERR_SIZE_MISMATCH;
+  }
+  if (hd.zero[0] != 0 && static_cast<int>(hd.zero[0]) - 1 != h->ray_log2_units)
+  {
+    h->err = "map apply: the pending exact raycast pass counts 2^" + std::to_string(static_cast<int>(hd.zero[0]) - 1) + " units per metre, this handle 2^" + std::to_string(h->ray_log2_units);
     return VOFOD_ERR_SIZE_MISMATCH;
   }
   if (hd.kind == VOFOD_SNAPSHOT_DELTA && (hd.base_gen == 0 || hd.base_gen != h->msync.applied_gen || static_cast<int>(hd.maps) != h->msync.applied_mask))

@@ -35,6 +35,7 @@
 #include "range_decode.h"
 #include "range_motion.h"
 #include "raycast_motion.h"
+#include "raycast_exact.h"
 #include "detection_points.h"
 #include "map_shift.h"
 
@@ -599,6 +600,10 @@ struct vofod_handle
   DevBuf<uint8_t> d_mask;
   DevBuf<uint32_t> d_col_shift;  // vofod_set_column_shift: one shift per row, reduced to [0, width); zeros until set
   bool raycast_motion = false;   // vofod_set_raycast_motion: the raycast role casts a scan with col_tfs ray by ray from the columns' poses (k_raycast_motion)
+  bool raycast_exact = false;    // vofod_set_raycast_exact: the next raycast pass accumulates fixed-point units (k_raycast_exact, raycast_exact.h)
+  bool ray_pass_exact = false;   // the pass between begin and finish holds units in d_ray (the representation belongs to the pass: begin records it)
+  int32_t ray_log2_units = -1;   // S and QMAX of EXACT RAYCAST ACCUMULATION, fixed at create (-1: no S fits, the switch is refused)
+  uint32_t ray_qmax = 0;
 
   Workspace ws, aux, sepws;
   ExploreBufs explore;
@@ -987,6 +992,7 @@ int do_reset(vofod_handle* h)
   HIPCHK(hipStreamSynchronize(h->stream));
   h->detection_its = 0;
   h->raycast_pending = false;
+  h->ray_pass_exact = false;
   h->sep_pending = false;
   h->mapbits_valid = false;
   return VOFOD_OK;

@@ -200,6 +200,22 @@ class VoFOD:
         `col_tfs` ray by ray from the columns' poses; off (the state after creation) they cast the rigid rays"""
         return self._check(self.lib.set_raycast_motion(self.h, int(bool(on))), "vofod_set_raycast_motion", allow)
 
+    def set_raycast_exact(self, on: bool = True, allow: Sequence[int] = ()):
+        """vofod_set_raycast_exact: with it on, the raycast passes begun from now on sum fixed-point units in uint32 (order
+        independent, bit-identical between handles fed the same scans); off (the state after creation) they sum floats"""
+        return self._check(self.lib.set_raycast_exact(self.h, int(bool(on))), "vofod_set_raycast_exact", allow)
+
+    def raycast_units(self, allow: Sequence[int] = ()):
+        """vofod_raycast_units: (U as uint32 [sz, sy, sx], S) of the pending exact pass - a voxel holds U * 2**-S metres; with a
+        status in `allow` returned by the call: (None, status)"""
+        out = np.empty(self.n_voxels, dtype=np.uint32)
+        s = C.c_int32(-1)
+        st = self._check(self.lib.raycast_units(self.h, capi.ptr(out), out.size, C.byref(s)), "vofod_raycast_units", allow)
+        if st != capi.OK:
+            return None, st
+        sx, sy, sz = self.map_size
+        return out.reshape(sz, sy, sx), int(s.value)
+
     # ------------------------------------------------- snapshots and deltas
     def export_map(self, maps: int = capi.MAPS_ALL, full: bool = True) -> np.ndarray:
         """A full snapshot or a delta of the maps in `maps` (bitmask of 1 << capi.MAP_*) in the wire format of

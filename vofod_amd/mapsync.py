@@ -2,6 +2,9 @@
 
 Independent of the library: `encode` builds the bytes the library writes, `decode` reads and checks them.  Little endian: a
 128-byte header, then for each selected map (voxels, flags, raycast in that order) u32 idx[n] followed by u32 bits[n].
+Byte 112, the first of the header's 16 reserved bytes, holds S + 1 when the snapshot carries a pending EXACT raycast pass with the
+raycast map in its mask (include/vofod.h, EXACT RAYCAST ACCUMULATION: the raycast records are then uint32 units, 2^S per metre) and
+0 otherwise; the other 15 are zero.  `Snapshot.raycast_log2_units` carries it (None: no such pass).
 """
 from __future__ import annotations
 
@@ -45,6 +48,7 @@ class Snapshot:
     sure_background_sufficient: int = 0
     raycast_pending: int = 0
     raycast_start_its: int = 0
+    raycast_log2_units: int | None = None  # S of a pending exact raycast pass whose units travel in the raycast records; None: floats
     records: dict = field(default_factory=dict)  # map -> (idx uint32[n], bits uint32[n]) for every selected map
 
     @property
@@ -92,6 +96,10 @@ def encode(s: Snapshot) -> np.ndarray:
         counts[m] = idx.size
         parts += [idx.view(np.uint8), bits.view(np.uint8)]
     h["n_records"] = counts
+    if s.raycast_log2_units is not None:
+        if not (s.raycast_pending and (s.maps >> MAP_RAYCAST) & 1 and 0 <= int(s.raycast_log2_units) <= 24):
+            raise ValueError("map snapshot: raycast_log2_units needs a pending pass, the raycast map in the mask and S in [0, 24]")
+        h["zero"][0, 0] = int(s.raycast_log2_units) + 1
     return np.concatenate([h.view(np.uint8).reshape(-1)] + parts)
 
 
@@ -117,6 +125,10 @@ def decode(buf, check: bool = True) -> Snapshot:
                  voxel_size=float(h["voxel_size"]), score_init=float(h["score_init"]), base_gen=int(h["base_gen"]), new_gen=int(h["new_gen"]))
     for k in STATE_FIELDS:
         setattr(s, k, int(h[k]))
+    tag = int(h["zero"][0])
+    if np.any(h["zero"][1:]) or (tag and not (s.raycast_pending and (maps >> MAP_RAYCAST) & 1 and tag <= 25)):
+        raise ValueError("map snapshot: reserved header bytes are not zero (byte 112 may hold S + 1 of a pending exact raycast pass)")
+    s.raycast_log2_units = tag - 1 if tag else None
     off = HEADER_BYTES
     n_vox = s.n_voxels
     for m in range(3):
