@@ -504,12 +504,12 @@ int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, flo
 int vofod_set_column_shift(vofod_handle* h, const int32_t* shift_by_row /* height ints; NULL = zeros */);
 /* vofod_set_raycast_motion: a handle property like the column shifts; `on` is taken as on != 0.  Off after vofod_create: the raycast
  * role ignores col_tfs.  On: vofod_raycast_begin and the raycast half of VOFOD_SCAN_AUTO_RAYCAST cast a scan that carries col_tfs
- * ray by ray from the columns' poses (MOTION-COMPENSATED RAYS at vofod_scan; k_raycast_motion).  Kept across vofod_reset,
+ * ray by ray from the columns' poses (MOTION-COMPENSATED RAYS at vofod_scan; profiled as k_raycast_motion).  Kept across vofod_reset,
  * vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch or a raycast pass is pending. */
 int vofod_set_raycast_motion(vofod_handle* h, int on);
 /* vofod_set_raycast_exact: a handle property with the rules of vofod_set_raycast_motion; `on` is taken as on != 0.  Off after
  * vofod_create: raycast passes sum floats.  On: the passes vofod_raycast_begin and VOFOD_SCAN_AUTO_RAYCAST begin from now on sum
- * fixed-point units (EXACT RAYCAST ACCUMULATION at vofod_scan; k_raycast_exact, k_ray_sweep_exact).  Kept across vofod_reset,
+ * fixed-point units (EXACT RAYCAST ACCUMULATION at vofod_scan; profiled as k_raycast_exact, k_ray_sweep_exact).  Kept across vofod_reset,
  * vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch or a raycast pass is pending;
  * VOFOD_ERR_INDEX_OVERFLOW when no S in [0, 24] satisfies the rule (a voxel size of hundreds of thousands of kilometres). */
 int vofod_set_raycast_exact(vofod_handle* h, int on);

@@ -1,5 +1,5 @@
-"""Exact raycast accumulation on the GPU (include/vofod.h, EXACT RAYCAST ACCUMULATION; vofod_set_raycast_exact, vofod_raycast_units,
-k_raycast_exact and k_ray_sweep_exact in vofod_amd/csrc/raycast_exact.h).  The small operation area and sensors of
+"""Exact raycast accumulation on the GPU (include/vofod.h, EXACT RAYCAST ACCUMULATION; vofod_set_raycast_exact, vofod_raycast_units;
+the AccUnits policy of k_raycast_t / k_ray_sweep_t in vofod_amd/csrc/kernels_raycast.h, launched as k_raycast_exact / k_ray_sweep_exact).  The small operation area and sensors of
 raycast_motion_cases / range_motion_cases.SHAPES: 5x20 (one partial block, one wave over all rows), 3x21 (odd width), OS1-16 with only
 rows 3 and 11 above the intensity gate (2 x 1024 consecutive pixels: full waves, long merge runs).
 

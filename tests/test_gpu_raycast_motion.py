@@ -1,9 +1,9 @@
-"""Motion-compensated rays on the GPU (include/vofod.h, MOTION-COMPENSATED RAYS; vofod_set_raycast_motion, k_raycast_motion in
-vofod_amd/csrc/raycast_motion.h).  All cases share one small operation area (24 x 24 x 12 m at 0.5 m: rays leave the map, start
+"""Motion-compensated rays on the GPU (include/vofod.h, MOTION-COMPENSATED RAYS; vofod_set_raycast_motion; k_raycast_t<MOTION = true, ...> in
+vofod_amd/csrc/kernels_raycast.h, launched as k_raycast_motion).  All cases share one small operation area (24 x 24 x 12 m at 0.5 m: rays leave the map, start
 inside it, and are clipped) and the small sensors of range_motion_cases.SHAPES - 5x20 (n = 100: one partial block, one wave that
 spans all rows), 3x21 (n = 63, odd width), OS1-16 (64 blocks) - with the three shift kinds (the wrap of m).
 
-(a) identity table, switch on, against the switch off on the same handle and scan: k_raycast_motion's restated walk against k_raycast;
+(a) identity table, switch on, against the switch off on the same handle and scan: the motion front against the rigid one (one walk);
 (b) quarter-turn tables against the sum of the oracle's gated rigid passes (raycast_motion_cases.oracle_quarter_sum), every input form;
 (c) rigid tables with real translation and rotation against the float64 geometry statement;
 (d) the switch as a handle property, and the argument rules;  (e) the sensor stream under VOFOD_SCAN_AUTO_RAYCAST (plumbing)."""

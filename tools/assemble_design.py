@@ -84,6 +84,8 @@ sub["R15_MEASURED"] = (P / "r15_range_motion.txt").read_text().splitlines()[0].r
 sub["R16_MEASURED"] = (P / "r16_raycast_motion.txt").read_text().splitlines()[0].removeprefix("measured: ")
 # §5.13: the first line of profiles/r17_raycast_exact.txt
 sub["R17_MEASURED"] = (P / "r17_raycast_exact.txt").read_text().splitlines()[0].removeprefix("measured: ")
+# §5.13: the first line of profiles/r18_raycast_one_walk.txt
+sub["R18_MEASURED"] = (P / "r18_raycast_one_walk.txt").read_text().splitlines()[0].removeprefix("measured: ")
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

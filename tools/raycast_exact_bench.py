@@ -5,7 +5,9 @@ One device-resident OS1-128 range image at 0.25 m on a map warmed by 32 scans, O
 profiler.  A leg is a whole pass - vofod_raycast_begin, one vofod_process_scan of the same scan (a finish needs a detection iteration),
 vofod_raycast_finish; the legs alternate between switch on and switch off, medians of ten after one warm-up pair:
   k_raycast_exact    against k_raycast    condition: ratio <= 1.00 (integer atomics on the same addresses were 0.81 x in a diagnostic build)
-  k_ray_sweep_exact  against k_ray_sweep  condition: ratio <= 1.05 (the same bytes; the margin covers run-to-run spread)"""
+  k_ray_sweep_exact  against k_ray_sweep  condition: ratio <= 1.05 (the same bytes; the margin covers run-to-run spread)
+Each pair is two instantiations of one template (k_raycast_t / k_ray_sweep_t in vofod_amd/csrc/kernels_raycast.h: the float and the
+units accumulator), told apart by profiler name."""
 import argparse
 import ctypes as C
 import json

@@ -5,6 +5,7 @@ One device-resident OS1-128 range image at 0.25 m on a warmed map, ONE process, 
   kernel   k_raycast_motion (switch on, a rigid twist table of 1 rad/s and 3 m/s, 16-byte aligned, device-resident) against
            k_raycast (switch off) on the same scan: the legs alternate, medians of ten after one warm-up pair.  The new front
            adds one 48-byte pose and about 40 flops to a walk of hundreds of steps.  Expectation: at most 1.10 x k_raycast's time.
+           Both are instantiations of one template (k_raycast_t in vofod_amd/csrc/kernels_raycast.h), told apart by profiler name.
   begin    the whole vofod_raycast_begin with a HOST scan (range, intensity and table staged by the call), wall clock, both legs."""
 import argparse
 import ctypes as C

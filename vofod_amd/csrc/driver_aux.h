@@ -150,46 +150,40 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
   int ret = VOFOD_OK;
   if (!h->hg.inLimits(o))  // :1432
     ret = VOFOD_ERR_SENSOR_OUTSIDE_MAP;
-  else if (motion)
-  {
-    // the table on the device: a device table where it lies, a host table in slot 0 of the synchronous workspace's pose block
-    // (copied on the stream, in front of the kernel; the call waits for both, so the caller's table is free when it returns)
-    const float* d_tab = scan->memspace == VOFOD_MEM_DEVICE ? scan->col_tfs : d_staged_poses;
-    if (!d_tab)
-    {
-      const size_t tab = static_cast<size_t>(h->sp.sensor_hrays) * 12;
-      if (!h->ws.d_poses)
-        HIPCHK(h->ws.d_poses.alloc(static_cast<size_t>(h->ws.F) * tab));
-      HIPCHK(hipMemcpyAsync(h->ws.d_poses, scan->col_tfs, tab * sizeof(float), hipMemcpyHostToDevice, h->stream));
-      d_tab = h->ws.d_poses;
-    }
-    const uint32_t width = static_cast<uint32_t>(scan->width);
-#define VOFOD_RAYCAST_MOTION_LAUNCH(P)                                                                                                                                                    \
-  KLAUNCH_AS(h, "k_raycast_motion", (vr::k_raycast_motion<P>), dim3((n + 255) / 256), dim3(256), rp, h->mg, d_int, d_rng, stride, h->d_lut_dirs.p, h->d_lut_offs.p, h->d_mask.p, d_tab, \
-             h->d_col_shift.p, width, h->d_ray.p, reinterpret_cast<uint32_t*>(h->d_counter + 1))
-#define VOFOD_RAYCAST_EXACT_LAUNCH(M, A, tab, shift, w)                                                                                                                                  \
-  KLAUNCH_AS(h, "k_raycast_exact", (vr::k_raycast_exact<M, A>), dim3((n + 255) / 256), dim3(256), rp, h->mg, xs, d_int, d_rng, stride, h->d_lut_dirs.p, h->d_lut_offs.p, h->d_mask.p, tab, \
-             shift, w, reinterpret_cast<uint32_t*>(h->d_ray.p), reinterpret_cast<uint32_t*>(h->d_counter + 1))
-    const bool aligned16 = reinterpret_cast<uintptr_t>(d_tab) % 16 == 0;
-    if (exact && aligned16)
-      VOFOD_RAYCAST_EXACT_LAUNCH(true, true, d_tab, h->d_col_shift.p, width);
-    else if (exact)
-      VOFOD_RAYCAST_EXACT_LAUNCH(true, false, d_tab, h->d_col_shift.p, width);
-    else if (aligned16)
-      VOFOD_RAYCAST_MOTION_LAUNCH(true);
-    else
-      VOFOD_RAYCAST_MOTION_LAUNCH(false);
-#undef VOFOD_RAYCAST_MOTION_LAUNCH
-  }
-  else if (exact)
-  {
-    const float* no_tab = nullptr;
-    const uint32_t* no_shift = nullptr;
-    VOFOD_RAYCAST_EXACT_LAUNCH(false, true, no_tab, no_shift, 0u);
-  }
   else
-    KLAUNCH(h, vr::k_raycast, dim3((n + 255) / 256), dim3(256), rp, h->mg, d_int, d_rng, stride, h->d_lut_dirs, h->d_lut_offs, h->d_mask, h->d_ray, reinterpret_cast<uint32_t*>(h->d_counter + 1));
-#undef VOFOD_RAYCAST_EXACT_LAUNCH
+  {
+    const float* d_tab = nullptr;  // (a rigid pass reads no table, shifts or width)
+    const uint32_t* d_shift = nullptr;
+    uint32_t width = 0;
+    if (motion)
+    {
+      // the table on the device: a device table where it lies, a host table in slot 0 of the synchronous workspace's pose block
+      // (copied on the stream, in front of the kernel; the call waits for both, so the caller's table is free when it returns)
+      d_tab = scan->memspace == VOFOD_MEM_DEVICE ? scan->col_tfs : d_staged_poses;
+      if (!d_tab)
+      {
+        const size_t tab = static_cast<size_t>(h->sp.sensor_hrays) * 12;
+        if (!h->ws.d_poses)
+          HIPCHK(h->ws.d_poses.alloc(static_cast<size_t>(h->ws.F) * tab));
+        HIPCHK(hipMemcpyAsync(h->ws.d_poses, scan->col_tfs, tab * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        d_tab = h->ws.d_poses;
+      }
+      d_shift = h->d_col_shift.p;
+      width = static_cast<uint32_t>(scan->width);
+    }
+    const bool aligned16 = reinterpret_cast<uintptr_t>(d_tab) % 16 == 0;
+    // one kernel template (kernels_raycast.h), selected by (motion, aligned16, exact), under the profiler name of the pass
+    auto cast = [&](const char* label, auto acc) {
+      using Acc = decltype(acc);
+      auto kern = !motion ? vr::k_raycast_t<false, true, Acc> : aligned16 ? vr::k_raycast_t<true, true, Acc> : vr::k_raycast_t<true, false, Acc>;
+      KLAUNCH_AS(h, label, kern, dim3((n + 255) / 256), dim3(256), rp, h->mg, acc, d_int, d_rng, stride, h->d_lut_dirs.p, h->d_lut_offs.p, h->d_mask.p, d_tab, d_shift, width,
+                 reinterpret_cast<typename Acc::T*>(h->d_ray.p), reinterpret_cast<uint32_t*>(h->d_counter + 1));
+    };
+    if (exact)
+      cast("k_raycast_exact", vr::AccUnits{xs});
+    else
+      cast(motion ? "k_raycast_motion" : "k_raycast", vr::AccFloat{});
+  }
   HIPCHK(hipStreamSynchronize(h->stream));
   return ret;
 }
@@ -245,11 +239,14 @@ int raycast_finish_locked(vofod_handle* h)
     const uint32_t bits = static_cast<uint32_t>(h->h_counter[2]);
     std::memcpy(&sp.max_val, &bits, 4);
   }
+  auto sweep = [&](const char* label, auto acc, float inv_scale) {
+    using Acc = decltype(acc);
+    KLAUNCH_AS(h, label, vr::k_ray_sweep_t<Acc>, dim3(256 * 8), dim3(256), sp, inv_scale, h->mg.n, h->d_map.p, h->d_flags.p, reinterpret_cast<typename Acc::T*>(h->d_ray.p));
+  };
   if (exact)
-    KLAUNCH_AS(h, "k_ray_sweep_exact", vr::k_ray_sweep_exact, dim3(256 * 8), dim3(256), sp, std::ldexp(1.0f, -h->ray_log2_units), h->mg.n, h->d_map.p, h->d_flags.p,
-               reinterpret_cast<uint32_t*>(h->d_ray.p));
+    sweep("k_ray_sweep_exact", vr::AccUnits{}, std::ldexp(1.0f, -h->ray_log2_units));
   else
-    KLAUNCH(h, vr::k_ray_sweep, dim3(256 * 8), dim3(256), sp, h->mg.n, h->d_map, h->d_flags, h->d_ray);
+    sweep("k_ray_sweep", vr::AccFloat{}, 0.0f);  // (the float pass reads no scale)
   HIPCHK(hipStreamSynchronize(h->stream));
   h->ray_dirty = false;
   h->mapbits_valid = false;

@@ -2,8 +2,37 @@
 //
 // raycast_cloud (vofod_nodelet.cpp:1397-1605): one lane per LiDAR ray walks the voxel map with the
 // Amanatides-Woo DDA of VoxelMap::forEachRay (voxel_map.cpp:229-263) and adds the in-voxel path length
-// to the raycast map with hardware float atomics; a single fused streaming pass then applies the
+// to the raycast map with hardware atomics; a single fused streaming pass then applies the
 // exponential pull of un-flagged traversed voxels towards scores/ray and clears flags + raycast map.
+//
+// The role is ONE kernel template, k_raycast_t<MOTION, ALIGNED16, Acc>: one front, one walk, one run merge, and two things that
+// vary - where the beam comes from (MOTION) and what is added (Acc).  The driver launches five instantiations under three profiler
+// names: k_raycast (rigid, float), k_raycast_motion (float, two table alignments), k_raycast_exact (units; rigid and two alignments).
+//
+// Motion-compensated rays (include/vofod.h, MOTION COMPENSATION, vofod_set_raycast_motion; MOTION): a scan that carries a pose per
+// measurement column.  Pixel i = row * width + col was measured in column m = (col + shift_by_row[row]) mod width (the handle keeps
+// the shifts reduced to [0, width)), and with T = col_tfs[m], d = lut_dirs[3i..], o = lut_offs[3i..], every operation IEEE float32,
+// rounded once, nothing fused:
+//   d'[k] = ((T[k][0]*d[0]) + (T[k][1]*d[1])) + (T[k][2]*d[2])
+//   o'[k] = (((T[k][0]*o[0]) + (T[k][1]*o[1])) + (T[k][2]*o[2])) + T[k][3]
+// From there on the ray is the rigid one with d', o' in place of the LUT entries: dir = R d', start = (R o') + t in the association
+// of the kernel's front, the gates, the length, the in-limits test of the ray's own start, the DDA.  An identity table gives d' == d
+// and o' == o as values (a zero may change sign; the walk reads only the magnitude of a zero component and compares it).  The two
+// matrices are never multiplied together; no exclude-box rule (the reference casts the airframe's short rays too, length <= 0 stops
+// them).  New against the rigid front: row = idx / width (one 32-bit division), m with one compare for the wrap, the pose, the two
+// transforms.  Lanes of a wave are 64 consecutive columns of one ring: their 64 poses are 3 KB of consecutive memory except where m
+// wraps or the wave spans a row end.  ALIGNED16: the table is 16-byte aligned and a pose is three 16-byte loads, otherwise twelve
+// 4-byte loads (range_motion.h: rm_load_pose).
+//
+// Exact raycast accumulation (include/vofod.h, EXACT RAYCAST ACCUMULATION, vofod_set_raycast_exact; Acc = AccUnits): path lengths
+// summed as fixed-point units in uint32 instead of float atomics.  With S = log2(units per metre) and QMAX of the handle
+// (ray_exact_scale below), a piece dd - the float min(dist, length) - prev of the walk, unchanged - counts
+//   q = min(rint(dd * 2^S), QMAX)          (the product is exact, rint is to nearest even; q == 0 leaves no trace)
+// and U[v] = sum of q over the pieces laid into voxel v, in the raycast map's own buffer.  Integer addition is associative and
+// n_pixels * QMAX fits in 32 bits, so U does not depend on the order of the atomics nor on how the wave groups its lanes into runs:
+// two passes of one scan, and the passes of two handles, end with the same bits.  The float view of a voxel is r = float(U) * 2^-S
+// (the conversion rounds to nearest even, the scaling is exact); the sweep, the old rule's max_val and vofod_read_map read that r.
+// An all-zero map is the same map in both representations, so the driver's ray_dirty / fill_map bookkeeping is shared.
 //
 // updateSeparatedBGClusters (vofod_nodelet.cpp:1126-1277): thresholded voxels are enumerated in the
 // reference's x-outer/z-inner order through a transposed occupancy bitmap, voxelised with the counted
@@ -12,9 +41,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
+#include <cmath>
 
 #include "kernels_voxelize.h"
+#include "range_motion.h"
 
 namespace vr
 {
@@ -30,153 +60,219 @@ struct RayParams
 
 __device__ __forceinline__ int c2i(float x, float off, float inv) { return static_cast<int>(floorf(__fmul_rn(__fsub_rn(x, off), inv))); }
 
-#ifndef RAY_ACC
-#define RAY_ACC 0  // diagnostics only (results wrong): 1 = the walk without the accumulation, 2 = plain stores instead of atomics
-#endif
+constexpr int RX_MAX_LOG2 = 24;  // the cap of S: 2^-24 m is below anything a float piece of a metre resolves
 
-// One DDA walk per lane: the state of forEachRay (voxel_map.cpp:229-263) in a form without branches.
-//   tmax / tdelta as in the reference (the per-ray sequence tmax += tdelta is kept: same floats, same voxel sequence);
-//   rem[a]  = steps left on axis a before the walk would leave the map (cur[a] == last[a] of the reference <=> rem[a] == 0);
-//   lin     = linear index of the current voxel, moved by lstep[a] = step[a] * stride[a].
-struct RayWalk
+// S and QMAX of a handle (host, double): S is the largest integer in [0, 24] with n_pixels * (floor(2 * vs * 2^S) + 1) <= 2^32 - 1,
+// QMAX = floor(2 * vs * 2^S).  False when not even S = 0 fits (a voxel size beyond any sensor): the switch is refused then.
+inline bool ray_exact_scale(float voxel_size, int hrays, int vrays, int32_t& S, uint32_t& qmax)
 {
-  float tmax[3], tdelta[3], prev, length;
-  int rem[3], lstep[3];
-  uint32_t lin;
-  bool active;
+  const double vs = static_cast<double>(voxel_size);
+  const double n_pixels = static_cast<double>(hrays) * static_cast<double>(vrays);
+  for (int s = RX_MAX_LOG2; s >= 0; s--)
+  {
+    const double q = std::floor(2.0 * vs * std::ldexp(1.0, s));
+    if (n_pixels * (q + 1.0) <= 4294967295.0)
+    {
+      S = s;
+      qmax = static_cast<uint32_t>(q);
+      return true;
+    }
+  }
+  return false;
+}
+
+struct ExactScale
+{
+  float scale;    // 2^S
+  uint32_t qmax;  // QMAX
 };
 
-// What bounds it (round 5, profiles/r05_raycast_variants.txt, one OS1-128 scan at 0.25 m): the float atomics.  The same kernel
-// without the accumulation: 78.5 us; with plain stores to the same addresses: 83.7 us; with the atomics: 218-222 us.  Tried and
-// not kept: two / four rays per lane for ILP (218.0 / 241.1 us against 219.8), and dealing the rays to the XCDs by azimuth sector
+// the units of one piece: min(rint(dd * 2^S), QMAX); a NaN piece counts nothing
+__device__ __forceinline__ uint32_t rx_units(float dd, const ExactScale& xs)
+{
+  const float x = rintf(__fmul_rn(dd, xs.scale));
+  // (clamped into [0, 2^32 - 256] before the conversion: fmaxf returns the other operand for a NaN)
+  const float c = fminf(fmaxf(x, 0.0f), 4294967040.0f);
+  return min(static_cast<uint32_t>(c), xs.qmax);
+}
+
+// What a pass adds, and how the sweep reads it back.  T is the word of the raycast map; piece() is what a lane lays for a step
+// of length dd (zero: no trace), add() joins two pieces of one run, commit() is the atomic of a run's last lane; touched() and
+// metres() are the sweep's view of a word.
+struct AccFloat  // in-voxel path lengths as floats: the sum depends on the order of the atomics
+{
+  using T = float;
+  __device__ __forceinline__ T piece(float dd) const { return dd; }
+  __device__ static __forceinline__ T add(T a, T b) { return __fadd_rn(a, b); }
+  __device__ static __forceinline__ void commit(T* cell, T run) { unsafeAtomicAdd(cell, run); }
+  __device__ static __forceinline__ bool touched(T r) { return r > 0.0f; }
+  __device__ static __forceinline__ float metres(T r, float) { return r; }
+};
+struct AccUnits  // fixed-point units, quantised per lane BEFORE the run merge: 64 lanes * QMAX fits, nobody reads the atomic's result
+{
+  using T = uint32_t;
+  ExactScale xs;
+  __device__ __forceinline__ T piece(float dd) const { return rx_units(dd, xs); }
+  __device__ static __forceinline__ T add(T a, T b) { return a + b; }
+  __device__ static __forceinline__ void commit(T* cell, T run) { (void)__hip_atomic_fetch_add(cell, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __device__ static __forceinline__ bool touched(T u) { return u != 0u; }
+  __device__ static __forceinline__ float metres(T u, float inv_scale) { return __fmul_rn(__uint2float_rn(u), inv_scale); }  // the float view
+};
+
+// d' and o' of the definition above
+__device__ __forceinline__ void ray_pose_apply(const vrm::Pose& T, const float d[3], const float o[3], float dm[3], float om[3])
+{
+  const float4 rows[3] = {T.r0, T.r1, T.r2};
+#pragma unroll
+  for (int k = 0; k < 3; k++)
+  {
+    const float4 t = rows[k];
+    dm[k] = __fadd_rn(__fadd_rn(__fmul_rn(t.x, d[0]), __fmul_rn(t.y, d[1])), __fmul_rn(t.z, d[2]));
+    om[k] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(t.x, o[0]), __fmul_rn(t.y, o[1])), __fmul_rn(t.z, o[2])), t.w);
+  }
+}
+
+// one axis of forEachRay's set-up (voxel_map.cpp:229-263):
+//   tmax / tdelta as in the reference (the per-ray sequence tmax += tdelta is kept: same floats, same voxel sequence);
+//   rem   = steps left on the axis before the walk would leave the map (cur == last of the reference <=> rem == 0);
+//   lstep = step * stride: what a step on the axis adds to the linear index of the current voxel.
+__device__ __forceinline__ void ray_axis(float dir, float start, int cur, int lim, int lstride, float vs, float off, float half, float& tmax, float& tdelta, int& rem, int& lstep)
+{
+  const float absdir = fabsf(dir);
+  const int step = (dir > 0.0f) - (dir < 0.0f);
+  tdelta = __fmul_rn(__fdiv_rn(1.0f, absdir), vs);
+  const float ctr = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(cur), 0.5f), vs), off);
+  const float ctr_offset = __fsub_rn(ctr, start);
+  tmax = __fdiv_rn(__fadd_rn(half, __fmul_rn(static_cast<float>(step), ctr_offset)), absdir);
+  rem = step > 0 ? lim - 1 - cur : cur;  // (last = step > 0 ? lim - 1 : 0, :246)
+  lstep = step * lstride;
+}
+
+// one step of the segmented inclusive sum: lanes whose flag is clear add the value CTRL brings, flags are or-ed
+template <class Acc, int CTRL, int MASK>
+__device__ __forceinline__ void ray_segstep(typename Acc::T& run, uint32_t& f)
+{
+  const auto t = __builtin_bit_cast(typename Acc::T, dpp_mov0<CTRL, MASK>(__builtin_bit_cast(uint32_t, run)));
+  const uint32_t ft = dpp_mov0<CTRL, MASK>(f);
+  run = f ? run : Acc::add(run, t);
+  f |= ft;
+}
+
+// Neighbouring lanes are neighbouring azimuth columns of one ring: their walks visit almost the same voxels in almost the same
+// order, so per DDA step the wave merges runs of lanes that sit in the same voxel and issues one atomic per run instead of one per
+// lane: a segmented inclusive sum with DPP moves (row_shr 1 / 2 / 4 / 8, row_bcast 15 / 31: vector ALU only, no LDS crossbar).  The
+// last lane of a run holds its total and issues the atomic.  key: the lane's voxel, 0xffffffff where it lays nothing.  Called by
+// every lane of the wave; returns whether this lane added.
+template <class Acc>
+__device__ __forceinline__ bool ray_merge_runs(uint32_t key, typename Acc::T piece, int lane, typename Acc::T* __restrict__ cells)
+{
+  const uint32_t kprev = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(~key), static_cast<int>(key), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
+  const bool head = lane == 0 || kprev != key;
+  uint32_t f = head ? 1u : 0u;
+  typename Acc::T run = piece;
+  ray_segstep<Acc, 0x111, 0xf>(run, f);
+  ray_segstep<Acc, 0x112, 0xf>(run, f);
+  ray_segstep<Acc, 0x114, 0xf>(run, f);
+  ray_segstep<Acc, 0x118, 0xf>(run, f);
+  ray_segstep<Acc, 0x142, 0xa>(run, f);
+  ray_segstep<Acc, 0x143, 0xc>(run, f);
+  const unsigned long long H = __ballot(head);
+  const bool tail = lane == 63 || ((H >> (lane + 1)) & 1ull);
+  if (tail && key != 0xffffffffu)  // (every lane of such a run laid a non-zero piece)
+  {
+    Acc::commit(&cells[key], run);
+    return true;
+  }
+  return false;
+}
+
+// What bounds the float pass (round 5, profiles/r05_raycast_variants.txt, one OS1-128 scan at 0.25 m): the float atomics.  The same
+// kernel without the accumulation: 78.5 us; with plain stores to the same addresses: 83.7 us; with the atomics: 218-222 us.  Tried
+// and not kept: two / four rays per lane for ILP (218.0 / 241.1 us against 219.8), and dealing the rays to the XCDs by azimuth sector
 // so that all rays through one wedge of the map are walked on one XCD and its L2 keeps the wedge's lines (221.7 us, 1 164 us at
 // OS2-128 x 2048 / 0.1 m against 1 168) - neither where the rays sit nor which L2 they go through changes what ~4 M single-float
-// read-modify-writes per scan cost.  The run merging below stays: without it there would be several times as many.
-__global__ __launch_bounds__(256) void k_raycast(const RayParams rp, const MapGeom mg, const char* __restrict__ intensity, const char* __restrict__ range, uint64_t stride,
-                                                 const float* __restrict__ lut_dirs, const float* __restrict__ lut_offs, const uint8_t* __restrict__ mask,
-                                                 float* __restrict__ ray, uint32_t* __restrict__ any_hit)
+// read-modify-writes per scan cost.  The run merging stays: without it there would be several times as many.
+//
+// MOTION: poses, shift and width are read; otherwise they are not (nullptr, 0) and the driver instantiates <false, true, .> only.
+// One ray per lane; every lane of every wave stays in the loop (the DPP merge and its ballots need the full wave: a lane beyond n or
+// behind a gate is carried as an inactive ray, never returned early).  No LDS and no scratch: the walk state lives in scalar locals
+// of the kernel and the step is written out in its body, not in a function on a struct of the state - behind a reference the
+// compiler folds `s2 ? rem2 : (s1 ? rem1 : rem0)` into one load through a selected ADDRESS, cannot split the struct into registers
+// any more and parks it in LDS (64 B per lane, read and written every step).
+template <bool MOTION, bool ALIGNED16, class Acc>
+__global__ __launch_bounds__(256) void k_raycast_t(const RayParams rp, const MapGeom mg, const Acc acc, const char* __restrict__ intensity, const char* __restrict__ range,
+                                                   uint64_t stride, const float* __restrict__ lut_dirs, const float* __restrict__ lut_offs, const uint8_t* __restrict__ mask,
+                                                   const float* __restrict__ poses, const uint32_t* __restrict__ shift, uint32_t width, typename Acc::T* __restrict__ cells,
+                                                   uint32_t* __restrict__ any_hit)
 {
-  constexpr int RPL = 1;
   const int lane = threadIdx.x & 63;
-  RayWalk w[RPL];
-#pragma unroll
-  for (int k = 0; k < RPL; k++)
+  const uint32_t idx_raw = blockIdx.x * blockDim.x + threadIdx.x;
+  bool alive = idx_raw < rp.n;
+  const uint32_t idx = alive ? idx_raw : 0u;  // (a lane beyond n reads pixel 0: row 0, a column and a pose inside the tables)
+  const float inten = *reinterpret_cast<const float*>(intensity + static_cast<uint64_t>(idx) * stride);
+  const uint32_t rng = *reinterpret_cast<const uint32_t*>(range + static_cast<uint64_t>(idx) * stride);
+  if (inten < rp.min_intensity || (!mask[idx] && rng == 0))  // vofod_nodelet.cpp:1449
+    alive = false;
+  float dm[3] = {lut_dirs[3 * idx], lut_dirs[3 * idx + 1], lut_dirs[3 * idx + 2]};
+  float om[3] = {lut_offs[3 * idx], lut_offs[3 * idx + 1], lut_offs[3 * idx + 2]};
+  if constexpr (MOTION)
   {
-    const uint32_t idx_raw = blockIdx.x * blockDim.x + threadIdx.x;
-    bool alive = idx_raw < rp.n;
-    const uint32_t idx = alive ? idx_raw : 0u;
-    const float inten = *reinterpret_cast<const float*>(intensity + static_cast<uint64_t>(idx) * stride);
-    const uint32_t rng = *reinterpret_cast<const uint32_t*>(range + static_cast<uint64_t>(idx) * stride);
-    if (inten < rp.min_intensity || (!mask[idx] && rng == 0))  // vofod_nodelet.cpp:1449
-      alive = false;
-    float dir[3], start[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-    {
-      const float* R = &rp.R[3 * r];
-      dir[r] = __fadd_rn(__fadd_rn(__fmul_rn(R[0], lut_dirs[3 * idx]), __fmul_rn(R[1], lut_dirs[3 * idx + 1])), __fmul_rn(R[2], lut_dirs[3 * idx + 2]));
-      start[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[0], lut_offs[3 * idx]), __fmul_rn(R[1], lut_offs[3 * idx + 1])), __fmul_rn(R[2], lut_offs[3 * idx + 2])), rp.origin[r]);
-    }
-    const float ray_dist = __fmul_rn(0.001f, static_cast<float>(rng));                                             // :1455-1456
-    w[k].length = ray_dist == 0.0f ? rp.max_dist : fminf(__fsub_rn(ray_dist, rp.voxel_size), rp.max_dist);          // :1457
-    const int cur[3] = {c2i(start[0], mg.off[0], mg.vs_inv), c2i(start[1], mg.off[1], mg.vs_inv), c2i(start[2], mg.off[2], mg.vs_inv)};
-    const int lim[3] = {mg.sx, mg.sy, mg.sz};
-    if (cur[0] < 0 || cur[0] >= lim[0] || cur[1] < 0 || cur[1] >= lim[1] || cur[2] < 0 || cur[2] >= lim[2])  // :1482
-      alive = false;
-    // forEachRay voxel_map.cpp:229-263
-    const float half = mg.vs / 2.0f;
-    const int lstride[3] = {1, mg.sx, mg.sx * mg.sy};
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-    {
-      const float absdir = fabsf(dir[a]);
-      const int step = (dir[a] > 0.0f) - (dir[a] < 0.0f);
-      w[k].tdelta[a] = __fmul_rn(__fdiv_rn(1.0f, absdir), mg.vs);
-      const float ctr = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(cur[a]), 0.5f), mg.vs), mg.off[a]);
-      const float ctr_offset = __fsub_rn(ctr, start[a]);
-      w[k].tmax[a] = __fdiv_rn(__fadd_rn(half, __fmul_rn(static_cast<float>(step), ctr_offset)), absdir);
-      w[k].rem[a] = step > 0 ? lim[a] - 1 - cur[a] : cur[a];  // (last[a] = step > 0 ? lim - 1 : 0, :246)
-      w[k].lstep[a] = step * lstride[a];
-    }
-    w[k].lin = alive ? static_cast<uint32_t>((static_cast<uint64_t>(cur[2]) * mg.sy + cur[1]) * mg.sx + cur[0]) : 0u;
-    w[k].prev = 0.0f;
-    w[k].active = alive && 0.0f < w[k].length;
+    // the pose of the pixel's measurement column, applied to the beam's direction and offset
+    const uint32_t row = idx / width;
+    const uint32_t m = vrm::rm_column(row, idx - row * width, width, shift);
+    const vrm::Pose T = vrm::rm_load_pose<ALIGNED16>(poses, m);
+    const float d[3] = {dm[0], dm[1], dm[2]}, o[3] = {om[0], om[1], om[2]};
+    ray_pose_apply(T, d, o, dm, om);
   }
-  // Neighbouring lanes are neighbouring azimuth columns of one ring: their walks visit almost the same voxels in
-  // almost the same order, so per DDA step the wave merges runs of lanes that sit in the same voxel (segmented
-  // sum) and issues one float atomic per run instead of one per lane.  The loop is kept wave-uniform.
-  bool any = false;
-  while (true)
+  // the call's tf
+  float dir[3], start[3];
+#pragma unroll
+  for (int r = 0; r < 3; r++)
   {
-    bool go = false;
-#pragma unroll
-    for (int k = 0; k < RPL; k++)
-      go |= w[k].active;
-    if (!__ballot(go))
-      break;
-#pragma unroll
-    for (int k = 0; k < RPL; k++)
-    {
-      RayWalk& r = w[k];
-      // the axis of the smallest tmax, first minimum on ties (Eigen's minCoeff, voxel_map.cpp:252)
-      const bool s1 = r.tmax[1] < r.tmax[0];
-      const float m01 = s1 ? r.tmax[1] : r.tmax[0];
-      const bool s2 = r.tmax[2] < m01;
-      const float dist = s2 ? r.tmax[2] : m01;
-      float dd = __fsub_rn(fminf(dist, r.length), r.prev);
-      dd = r.active ? dd : 0.0f;
-      const uint32_t key = dd != 0.0f ? r.lin : 0xffffffffu;
-      const int remi = s2 ? r.rem[2] : (s1 ? r.rem[1] : r.rem[0]);
-      const bool adv = r.active & (remi != 0);
-      const bool a2 = adv & s2, a1 = adv & s1 & !s2, a0 = adv & !s1 & !s2;
-      r.tmax[0] = a0 ? __fadd_rn(r.tmax[0], r.tdelta[0]) : r.tmax[0];
-      r.tmax[1] = a1 ? __fadd_rn(r.tmax[1], r.tdelta[1]) : r.tmax[1];
-      r.tmax[2] = a2 ? __fadd_rn(r.tmax[2], r.tdelta[2]) : r.tmax[2];
-      r.rem[0] -= a0 ? 1 : 0;
-      r.rem[1] -= a1 ? 1 : 0;
-      r.rem[2] -= a2 ? 1 : 0;
-      r.lin += static_cast<uint32_t>(a0 ? r.lstep[0] : (a1 ? r.lstep[1] : (a2 ? r.lstep[2] : 0)));
-      r.prev = r.active ? dist : r.prev;
-      r.active = adv & (dist < r.length);
-      // Runs of lanes in one voxel: segmented inclusive sum with DPP moves (row_shr 1 / 2 / 4 / 8, row_bcast 15 / 31: vector ALU
-      // only, no LDS crossbar).  The last lane of a run holds its total and issues the atomic.
-      const uint32_t kprev = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(static_cast<int>(~key), static_cast<int>(key), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-      const bool head = lane == 0 || kprev != key;
-      uint32_t f = head ? 1u : 0u;
-      float run = dd;
-      auto segstep = [&](auto ctrl_tag, auto mask_tag) {
-        constexpr int CTRL = decltype(ctrl_tag)::value, MASK = decltype(mask_tag)::value;
-        const float t = __uint_as_float(dpp_mov0<CTRL, MASK>(__float_as_uint(run)));
-        const uint32_t ft = dpp_mov0<CTRL, MASK>(f);
-        run = f ? run : __fadd_rn(run, t);
-        f |= ft;
-      };
-      segstep(std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});
-      segstep(std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});
-      segstep(std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});
-      segstep(std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});
-      segstep(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});
-      segstep(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});
-      const unsigned long long H = __ballot(head);
-      const bool tail = lane == 63 || ((H >> (lane + 1)) & 1ull);
-#if RAY_ACC == 1
-      if (tail && key != 0xffffffffu && run == 12345.678f)
-#else
-      if (tail && key != 0xffffffffu)
-#endif
-      {
-#if RAY_ACC == 2
-        ray[key] = run;
-#elif RAY_ACC == 3
-        atomicAdd(reinterpret_cast<unsigned int*>(ray) + key, __float_as_uint(run));  // (timing of an integer atomic on the same addresses)
-#elif RAY_ACC == 4
-        atomicAdd(reinterpret_cast<unsigned long long*>(ray) + (key >> 1), static_cast<unsigned long long>(__float_as_uint(run)));
-#else
-        unsafeAtomicAdd(&ray[key], run);
-#endif
-        any = true;
-      }
-    }
+    const float* R = &rp.R[3 * r];
+    dir[r] = __fadd_rn(__fadd_rn(__fmul_rn(R[0], dm[0]), __fmul_rn(R[1], dm[1])), __fmul_rn(R[2], dm[2]));
+    start[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[0], om[0]), __fmul_rn(R[1], om[1])), __fmul_rn(R[2], om[2])), rp.origin[r]);
+  }
+  // the walk's set-up: length, first voxel, in-limits test, then forEachRay's state one axis at a time
+  const float ray_dist = __fmul_rn(0.001f, static_cast<float>(rng));                                             // :1455-1456
+  const float length = ray_dist == 0.0f ? rp.max_dist : fminf(__fsub_rn(ray_dist, rp.voxel_size), rp.max_dist);  // :1457
+  const int c0 = c2i(start[0], mg.off[0], mg.vs_inv), c1 = c2i(start[1], mg.off[1], mg.vs_inv), c2 = c2i(start[2], mg.off[2], mg.vs_inv);
+  if (c0 < 0 || c0 >= mg.sx || c1 < 0 || c1 >= mg.sy || c2 < 0 || c2 >= mg.sz)  // :1482
+    alive = false;
+  const float half = mg.vs / 2.0f;
+  float tmax0, tmax1, tmax2, tdelta0, tdelta1, tdelta2;
+  int rem0, rem1, rem2, lstep0, lstep1, lstep2;
+  ray_axis(dir[0], start[0], c0, mg.sx, 1, mg.vs, mg.off[0], half, tmax0, tdelta0, rem0, lstep0);
+  ray_axis(dir[1], start[1], c1, mg.sy, mg.sx, mg.vs, mg.off[1], half, tmax1, tdelta1, rem1, lstep1);
+  ray_axis(dir[2], start[2], c2, mg.sz, mg.sx * mg.sy, mg.vs, mg.off[2], half, tmax2, tdelta2, rem2, lstep2);
+  uint32_t lin = alive ? static_cast<uint32_t>((static_cast<uint64_t>(c2) * mg.sy + c1) * mg.sx + c0) : 0u;
+  float prev = 0.0f;
+  bool active = alive && 0.0f < length;
+  // the loop is kept wave-uniform
+  bool any = false;
+  while (__ballot(active))
+  {
+    // the axis of the smallest tmax, first minimum on ties (Eigen's minCoeff, voxel_map.cpp:252)
+    const bool s1 = tmax1 < tmax0;
+    const float m01 = s1 ? tmax1 : tmax0;
+    const bool s2 = tmax2 < m01;
+    const float dist = s2 ? tmax2 : m01;
+    const float dd = __fsub_rn(fminf(dist, length), prev);
+    const typename Acc::T piece = active ? acc.piece(dd) : typename Acc::T(0);
+    const uint32_t key = piece != typename Acc::T(0) ? lin : 0xffffffffu;
+    const int remi = s2 ? rem2 : (s1 ? rem1 : rem0);
+    const bool adv = active & (remi != 0);
+    const bool a2 = adv & s2, a1 = adv & s1 & !s2, a0 = adv & !s1 & !s2;
+    tmax0 = a0 ? __fadd_rn(tmax0, tdelta0) : tmax0;
+    tmax1 = a1 ? __fadd_rn(tmax1, tdelta1) : tmax1;
+    tmax2 = a2 ? __fadd_rn(tmax2, tdelta2) : tmax2;
+    rem0 -= a0 ? 1 : 0;
+    rem1 -= a1 ? 1 : 0;
+    rem2 -= a2 ? 1 : 0;
+    lin += static_cast<uint32_t>(a0 ? lstep0 : (a1 ? lstep1 : (a2 ? lstep2 : 0)));
+    prev = active ? dist : prev;
+    active = adv & (dist < length);
+    any |= ray_merge_runs<Acc>(key, piece, lane, cells);
   }
   if (any)
     *any_hit = 1u;
@@ -199,6 +295,19 @@ __global__ __launch_bounds__(256) void k_max_nonneg(const float* __restrict__ v,
     atomicMax(out, m);
 }
 
+// integer max of U, for the old update rule (:1542): the host converts it to max_val by the rule of the float view
+__global__ __launch_bounds__(256) void k_max_units(const uint32_t* __restrict__ u, uint64_t n, uint32_t* out)
+{
+  uint32_t m = 0;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<uint64_t>(gridDim.x) * blockDim.x)
+    m = max(m, u[i]);
+#pragma unroll
+  for (int s = 32; s > 0; s >>= 1)
+    m = max(m, __shfl_xor(m, s));
+  if ((threadIdx.x & 63) == 0 && m)
+    atomicMax(out, m);
+}
+
 struct SweepParams
 {
   float its_diff;
@@ -210,15 +319,19 @@ struct SweepParams
 };
 
 // K15: fused update sweep (:1557-1602).  Reads flags + raycast (+ map where a ray passed), writes map,
-// clears flags and the raycast accumulator.  Stores are issued only where a value actually changes.
-__global__ __launch_bounds__(256) void k_ray_sweep(const SweepParams sp, uint64_t n, float* __restrict__ map, float* __restrict__ flags, float* __restrict__ ray)
+// clears flags and the raycast accumulator (to zero bits).  Stores are issued only where a value actually changes.
+// Launched as k_ray_sweep (AccFloat: r is the word itself, inv_scale is not read) and k_ray_sweep_exact (AccUnits: r = float(U) * 2^-S).
+template <class Acc>
+__global__ __launch_bounds__(256) void k_ray_sweep_t(const SweepParams sp, float inv_scale, uint64_t n, float* __restrict__ map, float* __restrict__ flags,
+                                                     typename Acc::T* __restrict__ cells)
 {
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<uint64_t>(gridDim.x) * blockDim.x)
   {
     const float flag = flags[i];
-    const float r = ray[i];
-    if (flag == 0.0f && r > 0.0f)
+    const typename Acc::T c = cells[i];
+    if (flag == 0.0f && Acc::touched(c))
     {
+      const float r = Acc::metres(c, inv_scale);
       float w1;
       if (sp.new_rule)
       {
@@ -236,8 +349,8 @@ __global__ __launch_bounds__(256) void k_ray_sweep(const SweepParams sp, uint64_
     }
     if (flag != 0.0f)
       flags[i] = 0.0f;
-    if (r != 0.0f)
-      ray[i] = 0.0f;
+    if (c != typename Acc::T(0))
+      cells[i] = typename Acc::T(0);
   }
 }
 

@@ -34,8 +34,6 @@
 #include "mapsync.h"
 #include "range_decode.h"
 #include "range_motion.h"
-#include "raycast_motion.h"
-#include "raycast_exact.h"
 #include "detection_points.h"
 #include "map_shift.h"
 
@@ -600,7 +598,7 @@ struct vofod_handle
   DevBuf<uint8_t> d_mask;
   DevBuf<uint32_t> d_col_shift;  // vofod_set_column_shift: one shift per row, reduced to [0, width); zeros until set
   bool raycast_motion = false;   // vofod_set_raycast_motion: the raycast role casts a scan with col_tfs ray by ray from the columns' poses (k_raycast_motion)
-  bool raycast_exact = false;    // vofod_set_raycast_exact: the next raycast pass accumulates fixed-point units (k_raycast_exact, raycast_exact.h)
+  bool raycast_exact = false;    // vofod_set_raycast_exact: the next raycast pass accumulates fixed-point units (k_raycast_exact)
   bool ray_pass_exact = false;   // the pass between begin and finish holds units in d_ray (the representation belongs to the pass: begin records it)
   int32_t ray_log2_units = -1;   // S and QMAX of EXACT RAYCAST ACCUMULATION, fixed at create (-1: no S fits, the switch is refused)
   uint32_t ray_qmax = 0;
