@@ -1,5 +1,5 @@
 """Motion-compensated range images on the GPU (include/vofod.h, MOTION COMPENSATION): the HIP detector is handed the sensor's range
-column and a pose per measurement column and rebuilds the compensated points itself (k_range_decode_motion, range_motion.h); the
+column and a pose per measurement column and rebuilds the compensated points itself (k_range_decode_motion, range_decode.h); the
 CPU oracle, which has neither input, is handed the points of the numpy statement (tests/range_motion_cases.py).
 
 (a) vofod_range_to_points with col_tfs against the statement, bit for bit;  (b) batches through the frame kernel, three views, mixed
@@ -231,13 +231,15 @@ def test_batches_of_compensated_range_images(pair16, n):
 
 def test_mixed_batches(pair16):
     """compensated range images, plain ones and point scans in one batch: each frame's result is its own, k_range_decode_motion runs
-    once, k_range_decode once only when plain range images are present"""
+    once, k_range_decode once only when plain range images are present.  full_*: max_batch frames, alternating - the two kinds share
+    one job list of max_batch entries (the compensated images first), and here every entry is taken"""
     p = pair16
-    n = 9
-    tfs = p.tfs[:n]
-    kinds = {"all_three": ["motion", "plain", "points"], "motion_and_points": ["motion", "points"], "plain_and_points": ["plain", "points"], "motion_and_plain": ["plain", "motion"]}
-    want_launches = {"all_three": (1, 1), "motion_and_points": (1, 0), "plain_and_points": (0, 1), "motion_and_plain": (1, 1)}
+    kinds = {"all_three": ["motion", "plain", "points"], "motion_and_points": ["motion", "points"], "plain_and_points": ["plain", "points"], "motion_and_plain": ["plain", "motion"],
+             "full_motion_first": ["motion", "plain"], "full_plain_first": ["plain", "motion"]}
+    want_launches = {"all_three": (1, 1), "motion_and_points": (1, 0), "plain_and_points": (0, 1), "motion_and_plain": (1, 1), "full_motion_first": (1, 1), "full_plain_first": (1, 1)}
     for name, cyc in kinds.items():
+        n = N_BATCH if name.startswith("full_") else 9
+        tfs = p.tfs[:n]
         ks = [cyc[f % len(cyc)] for f in range(n)]
         scans_ref = [ref_scan(p, f, compensated=ks[f] == "motion") for f in range(n)]
         scans_dev = [dev_scan(p, f, ks[f]) for f in range(n)]

@@ -162,11 +162,9 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
       d_tab = scan->memspace == VOFOD_MEM_DEVICE ? scan->col_tfs : d_staged_poses;
       if (!d_tab)
       {
-        const size_t tab = static_cast<size_t>(h->sp.sensor_hrays) * 12;
-        if (!h->ws.d_poses)
-          HIPCHK(h->ws.d_poses.alloc(static_cast<size_t>(h->ws.F) * tab));
-        HIPCHK(hipMemcpyAsync(h->ws.d_poses, scan->col_tfs, tab * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        d_tab = h->ws.d_poses;
+        float* slot = nullptr;
+        VCHK(pose_slot(h, h->ws, 0, scan->col_tfs, h->stream, slot));
+        d_tab = slot;
       }
       d_shift = h->d_col_shift.p;
       width = static_cast<uint32_t>(scan->width);
@@ -1408,8 +1406,8 @@ int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, flo
     return VOFOD_ERR_SIZE_MISMATCH;
   VCHK(check_col_tfs(h, *scan));
   VCHK(busy_check(h, true, false));
-  // one frame through the batch path's staging and kernel (k_range_decode, or k_range_decode_motion for a scan with col_tfs): frame
-  // slot 0 of the synchronous workspace
+  // one frame through the batch path's staging and kernel (range_decode.h: one job, launched as k_range_decode, or as
+  // k_range_decode_motion for a scan with col_tfs): frame slot 0 of the synchronous workspace
   Workspace& ws = h->ws;
   const size_t npts = static_cast<size_t>(scan->width) * scan->height;
   const float tf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};

@@ -178,9 +178,22 @@ inline int check_col_tfs(vofod_handle* h, const vofod_scan& s)
   return VOFOD_OK;
 }
 
-// Pose tables of the batch's motion jobs (in frame order, as the jobs are): device-resident tables are read where they lie,
-// host-resident ones go to the workspace's pose block - table j of the list into slot j - with ONE 2-D copy when they lie at a
-// constant pitch (one numpy block per batch), otherwise one copy each.  On the stream of the staging copies, in front of the event
+// Slot k of the workspace's pose block (F tables of width * 12 floats, allocated on the first use); a host table `src` is copied
+// there on `st` (nullptr: the caller copies).
+int pose_slot(vofod_handle* h, Workspace& ws, size_t k, const float* src, hipStream_t st, float*& slot)
+{
+  const size_t tab = static_cast<size_t>(h->sp.sensor_hrays) * 12;  // floats per table
+  if (!ws.d_poses)
+    HIPCHK(ws.d_poses.alloc(static_cast<size_t>(ws.F) * tab));
+  slot = ws.d_poses + k * tab;
+  if (src)
+    HIPCHK(hipMemcpyAsync(slot, src, tab * sizeof(float), hipMemcpyHostToDevice, st));
+  return VOFOD_OK;
+}
+
+// Pose tables of the batch's motion jobs (the first n_mjobs of the job list, in frame order): device-resident tables are read where
+// they lie, host-resident ones go to the workspace's pose block - table j of the list into slot j - with ONE 2-D copy when they lie
+// at a constant pitch (one numpy block per batch), otherwise one copy each.  On the stream of the staging copies, in front of the event
 // vofod_batch_submit waits for: the caller may overwrite its tables when submit returns.
 int stage_pose_tables(vofod_handle* h, Workspace& ws, const vofod_scan* scans, uint32_t n)
 {
@@ -199,29 +212,27 @@ int stage_pose_tables(vofod_handle* h, Workspace& ws, const vofod_scan* scans, u
     }
     j++;
   }
-  if (!host.empty())
+  if (host.empty())
+    return VOFOD_OK;
+  const ptrdiff_t pitch = host.size() >= 2 ? reinterpret_cast<const char*>(host[1]) - reinterpret_cast<const char*>(host[0]) : 0;
+  bool constant = pitch >= static_cast<ptrdiff_t>(tab * sizeof(float));
+  for (size_t k = 2; k < host.size() && constant; k++)
+    constant = reinterpret_cast<const char*>(host[k]) == reinterpret_cast<const char*>(host[0]) + static_cast<ptrdiff_t>(k) * pitch;
+  for (size_t k = 0; k < host.size(); k++)
   {
-    if (!ws.d_poses)
-      HIPCHK(ws.d_poses.alloc(static_cast<size_t>(ws.F) * tab));
-    for (uint32_t k = 0; k < host.size(); k++)
-      ws.h_mjobs.p[job_of[k]].poses = ws.d_poses + static_cast<size_t>(k) * tab;
-    const ptrdiff_t pitch = host.size() >= 2 ? reinterpret_cast<const char*>(host[1]) - reinterpret_cast<const char*>(host[0]) : 0;
-    bool constant = pitch >= static_cast<ptrdiff_t>(tab * sizeof(float));
-    for (size_t k = 2; k < host.size() && constant; k++)
-      constant = reinterpret_cast<const char*>(host[k]) == reinterpret_cast<const char*>(host[0]) + static_cast<ptrdiff_t>(k) * pitch;
-    if (constant)
-      HIPCHK(hipMemcpy2DAsync(ws.d_poses, tab * sizeof(float), host[0], static_cast<size_t>(pitch), tab * sizeof(float), host.size(), hipMemcpyHostToDevice, h->stream));
-    else
-      for (size_t k = 0; k < host.size(); k++)
-        HIPCHK(hipMemcpyAsync(ws.d_poses + k * tab, host[k], tab * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    float* slot = nullptr;
+    VCHK(pose_slot(h, ws, k, constant ? nullptr : host[k], h->stream, slot));
+    ws.h_rjobs.p[job_of[k]].poses = slot;
   }
-  HIPCHK(hipMemcpyAsync(ws.d_mjobs, ws.h_mjobs, sizeof(vrm::MotionJob) * ws.n_mjobs, hipMemcpyHostToDevice, h->stream));
+  if (constant)
+    HIPCHK(hipMemcpy2DAsync(ws.d_poses, tab * sizeof(float), host[0], static_cast<size_t>(pitch), tab * sizeof(float), host.size(), hipMemcpyHostToDevice, h->stream));
   return VOFOD_OK;
 }
 
-// the device copy of the pose table of the call's FIRST scan as stage_pose_tables left it in the workspace's job list (the jobs are in
-// frame order: a first scan with a table owns job 0); nullptr when the scan has none.  A re-run keeps the list of its first launch.
-inline const float* staged_pose_table(const Workspace& ws, const vofod_scan& s) { return s.col_tfs && ws.n_mjobs ? ws.h_mjobs.p[0].poses : nullptr; }
+// the device copy of the pose table of the call's FIRST scan as stage_pose_tables left it in the workspace's job list (the motion jobs
+// lead the list in frame order: a first scan with a table owns job 0); nullptr when the scan has none.  A re-run keeps the list of its
+// first launch.
+inline const float* staged_pose_table(const Workspace& ws, const vofod_scan& s) { return s.col_tfs && ws.n_mjobs ? ws.h_rjobs.p[0].poses : nullptr; }
 
 // ---- stage inputs (filterAndTransform :621-684 reads them)
 // (the re-run of a batch that overflowed the LDS kernels keeps the frame arguments and the staged columns of its first
@@ -237,15 +248,10 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
   bool staged_2d = false;
   ws.det_valid = false;  // (the workspace is taken: what vofod_detection_points answered from is about to be overwritten)
   ws.n_rjobs = ws.n_mjobs = 0;
+  // the range images of the batch, in frame order for now (a pose table: the caller's, for now)
+  vrd::RangeJob* const jobs = ws.h_rjobs.p;
+  uint32_t n_jobs = 0;
   auto slot = [&](uint32_t f) { return ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5; };
-  // a range image goes to one of the two job lists: with a pose per column to k_range_decode_motion's (its table: the caller's, for
-  // now), without to k_range_decode's
-  auto add_job = [&](const vofod_scan& s, const vrd::RangeJob& job) {
-    if (s.col_tfs)
-      ws.h_mjobs.p[ws.n_mjobs++] = vrm::MotionJob{job.src, job.dst, job.stride, s.col_tfs};
-    else
-      ws.h_rjobs.p[ws.n_rjobs++] = job;
-  };
   // the frame's arguments point at the packed x | y | z columns of its staging slot (copied there, or decoded there by k_range_decode)
   auto slot_args = [&](uint32_t f) {
     float* base = slot(f);
@@ -289,7 +295,7 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
       for (uint32_t f = 0; f < n; f++)
       {
         VCHK(slot_args(f));
-        add_job(scans[f], vrd::RangeJob{reinterpret_cast<const char*>(slot(f) + 4 * static_cast<size_t>(ws.pt_cap)), slot(f), 4, 0});
+        jobs[n_jobs++] = vrd::RangeJob{reinterpret_cast<const char*>(slot(f) + 4 * static_cast<size_t>(ws.pt_cap)), slot(f), 4, scans[f].col_tfs};
       }
       staged_2d = true;
     }
@@ -305,7 +311,7 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
       continue;
     }
     // a range image: device-resident ranges are read where they lie, a host column goes to column 4 of the slot (gathered when strided)
-    vrd::RangeJob job{static_cast<const char*>(s.range), slot(f), s.stride_bytes, 0};
+    vrd::RangeJob job{static_cast<const char*>(s.range), slot(f), s.stride_bytes, s.col_tfs};
     if (s.memspace != VOFOD_MEM_DEVICE)
     {
       VCHK(stage_host_column(h, slot(f) + 4 * static_cast<size_t>(ws.pt_cap), s.range, s.stride_bytes, npts));
@@ -318,71 +324,59 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
       return VOFOD_ERR_INVALID_ARG;
     }
     VCHK(slot_args(f));
-    add_job(s, job);
+    jobs[n_jobs++] = job;
   }
-  if (ws.n_rjobs)
-    HIPCHK(hipMemcpyAsync(ws.d_rjobs, ws.h_rjobs, sizeof(vrd::RangeJob) * ws.n_rjobs, hipMemcpyHostToDevice, h->stream));
+  // the jobs with a pose per column first (k_range_decode_motion's span), those without behind them (k_range_decode's), each kind
+  // still in frame order; the whole list goes up with one copy
+  ws.n_mjobs = static_cast<uint32_t>(std::stable_partition(jobs, jobs + n_jobs, [](const vrd::RangeJob& job) { return job.poses != nullptr; }) - jobs);
+  ws.n_rjobs = n_jobs - ws.n_mjobs;
   if (ws.n_mjobs)
     VCHK(stage_pose_tables(h, ws, scans, n));
+  if (n_jobs)
+    HIPCHK(hipMemcpyAsync(ws.d_rjobs, jobs, sizeof(vrd::RangeJob) * n_jobs, hipMemcpyHostToDevice, h->stream));
   return VOFOD_OK;
 }
 
-// k_range_decode_motion over the second job list (range images with a pose per column): one launch per batch that has such a frame
-int decode_ranges_motion(vofod_handle* h, Workspace& ws, size_t npts)
+// one launch of the decode template over jobs [first, first + n_jobs) of the list stage_inputs left in the workspace (none: no launch)
+int decode_span(vofod_handle* h, Workspace& ws, size_t npts, bool motion, uint32_t first, uint32_t n_jobs)
 {
-  if (!ws.n_mjobs)
+  if (!n_jobs)
     return VOFOD_OK;
   bool vec = npts % 4 == 0 && ws.pt_cap % 4 == 0, pose16 = true;
-  for (uint32_t j = 0; j < ws.n_mjobs; j++)
+  for (uint32_t j = first; j < first + n_jobs; j++)
   {
-    const vrm::MotionJob& job = ws.h_mjobs.p[j];
+    const vrd::RangeJob& job = ws.h_rjobs.p[j];
     vec = vec && job.stride == 4 && reinterpret_cast<uintptr_t>(job.src) % 16 == 0;
-    pose16 = pose16 && reinterpret_cast<uintptr_t>(job.poses) % 16 == 0;
+    pose16 = pose16 && reinterpret_cast<uintptr_t>(job.poses) % 16 == 0;  // (a plain job has none: stays true, and is not used)
   }
-  vrm::MotionBox box;
-  for (int a = 0; a < 3; a++)  // the bounds of the first crop: the expressions of fill_grid_params
+  vrd::MotionArgs ma{};  // (a plain span reads none of it)
+  if (motion)
   {
-    box.hi[a] = h->exclude_center[a] + h->sp.exclude_size[a] / 2;
-    box.lo[a] = h->exclude_center[a] - h->sp.exclude_size[a] / 2;
+    ma.shift = h->d_col_shift.p;
+    ma.width = static_cast<uint32_t>(h->sp.sensor_hrays);
+    exclude_box(h, ma.lo, ma.hi);
   }
-  const uint32_t chunk = std::min(std::max(ws.n_mjobs / 16u, 1u), vrm::RM_CHUNK_MAX);
-  const uint32_t n_px = static_cast<uint32_t>(npts), threads = vec ? n_px / 4u : n_px, width = static_cast<uint32_t>(h->sp.sensor_hrays);
-  const dim3 grid((threads + vrm::RM_THREADS - 1) / vrm::RM_THREADS, (ws.n_mjobs + chunk - 1) / chunk);
-#define VOFOD_MOTION_LAUNCH(V, P)                                                                                                                                                   \
-  KLAUNCH_AS(h, "k_range_decode_motion", (vrm::k_range_decode_motion<V, P>), grid, dim3(vrm::RM_THREADS), ws.d_mjobs.p, ws.n_mjobs, chunk, n_px, width, ws.pt_cap, h->d_lut_dirs.p, \
-             h->d_lut_offs.p, h->d_col_shift.p, box)
-  if (vec && pose16)
-    VOFOD_MOTION_LAUNCH(true, true);
-  else if (vec)
-    VOFOD_MOTION_LAUNCH(true, false);
-  else if (pose16)
-    VOFOD_MOTION_LAUNCH(false, true);
-  else
-    VOFOD_MOTION_LAUNCH(false, false);
-#undef VOFOD_MOTION_LAUNCH
+  // few frames: one per thread keeps every CU busy; many: up to RD_CHUNK_MAX per thread share one read of the LUT
+  const uint32_t chunk = std::min(std::max(n_jobs / 16u, 1u), vrd::RD_CHUNK_MAX);
+  const uint32_t n_px = static_cast<uint32_t>(npts), threads = vec ? n_px / 4u : n_px;
+  const dim3 grid((threads + vrd::RD_THREADS - 1) / vrd::RD_THREADS, (n_jobs + chunk - 1) / chunk);
+  // one kernel template (range_decode.h), selected by (vec, motion, pose16), under the profiler name of the span
+  auto pick = [&](auto v) {
+    constexpr bool V = decltype(v)::value;
+    return !motion ? vrd::k_range_decode_t<V, false, true> : pose16 ? vrd::k_range_decode_t<V, true, true> : vrd::k_range_decode_t<V, true, false>;
+  };
+  auto kern = vec ? pick(std::true_type{}) : pick(std::false_type{});
+  KLAUNCH_AS(h, motion ? "k_range_decode_motion" : "k_range_decode", kern, grid, dim3(vrd::RD_THREADS), ws.d_rjobs.p + first, n_jobs, chunk, n_px, ws.pt_cap, h->d_lut_dirs.p, h->d_lut_offs.p, ma);
   HIPCHK(hipGetLastError());
   return VOFOD_OK;
 }
 
-// k_range_decode over the job list stage_inputs left in the workspace: one launch per batch, on the stream of the staging copies
+// the decode of the batch's range images, on the stream of the staging copies: one launch over the jobs with a pose per column, one
+// over those without
 int decode_ranges(vofod_handle* h, Workspace& ws, size_t npts)
 {
-  VCHK(decode_ranges_motion(h, ws, npts));
-  if (!ws.n_rjobs)
-    return VOFOD_OK;
-  bool vec = npts % 4 == 0 && ws.pt_cap % 4 == 0;
-  for (uint32_t j = 0; j < ws.n_rjobs && vec; j++)
-    vec = ws.h_rjobs.p[j].stride == 4 && reinterpret_cast<uintptr_t>(ws.h_rjobs.p[j].src) % 16 == 0;
-  // few frames: one per thread keeps every CU busy; many: up to RD_CHUNK_MAX per thread share one read of the LUT
-  const uint32_t chunk = std::min(std::max(ws.n_rjobs / 16u, 1u), vrd::RD_CHUNK_MAX);
-  const uint32_t n_px = static_cast<uint32_t>(npts), threads = vec ? n_px / 4u : n_px;
-  const dim3 grid((threads + vrd::RD_THREADS - 1) / vrd::RD_THREADS, (ws.n_rjobs + chunk - 1) / chunk);
-  if (vec)
-    KLAUNCH_AS(h, "k_range_decode", vrd::k_range_decode<true>, grid, dim3(vrd::RD_THREADS), ws.d_rjobs.p, ws.n_rjobs, chunk, n_px, ws.pt_cap, h->d_lut_dirs.p, h->d_lut_offs.p);
-  else
-    KLAUNCH_AS(h, "k_range_decode", vrd::k_range_decode<false>, grid, dim3(vrd::RD_THREADS), ws.d_rjobs.p, ws.n_rjobs, chunk, n_px, ws.pt_cap, h->d_lut_dirs.p, h->d_lut_offs.p);
-  HIPCHK(hipGetLastError());
-  return VOFOD_OK;
+  VCHK(decode_span(h, ws, npts, true, 0, ws.n_mjobs));
+  return decode_span(h, ws, npts, false, ws.n_mjobs, ws.n_rjobs);
 }
 
 // an error return of the launch half must not leave copies from the caller's buffers in flight

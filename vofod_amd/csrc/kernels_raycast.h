@@ -22,7 +22,7 @@
 // them).  New against the rigid front: row = idx / width (one 32-bit division), m with one compare for the wrap, the pose, the two
 // transforms.  Lanes of a wave are 64 consecutive columns of one ring: their 64 poses are 3 KB of consecutive memory except where m
 // wraps or the wave spans a row end.  ALIGNED16: the table is 16-byte aligned and a pose is three 16-byte loads, otherwise twelve
-// 4-byte loads (range_motion.h: rm_load_pose).
+// 4-byte loads (column_pose.h: load_pose).
 //
 // Exact raycast accumulation (include/vofod.h, EXACT RAYCAST ACCUMULATION, vofod_set_raycast_exact; Acc = AccUnits): path lengths
 // summed as fixed-point units in uint32 instead of float atomics.  With S = log2(units per metre) and QMAX of the handle
@@ -43,8 +43,8 @@
 
 #include <cmath>
 
+#include "column_pose.h"
 #include "kernels_voxelize.h"
-#include "range_motion.h"
 
 namespace vr
 {
@@ -120,7 +120,7 @@ struct AccUnits  // fixed-point units, quantised per lane BEFORE the run merge: 
 };
 
 // d' and o' of the definition above
-__device__ __forceinline__ void ray_pose_apply(const vrm::Pose& T, const float d[3], const float o[3], float dm[3], float om[3])
+__device__ __forceinline__ void ray_pose_apply(const Pose& T, const float d[3], const float o[3], float dm[3], float om[3])
 {
   const float4 rows[3] = {T.r0, T.r1, T.r2};
 #pragma unroll
@@ -219,8 +219,8 @@ __global__ __launch_bounds__(256) void k_raycast_t(const RayParams rp, const Map
   {
     // the pose of the pixel's measurement column, applied to the beam's direction and offset
     const uint32_t row = idx / width;
-    const uint32_t m = vrm::rm_column(row, idx - row * width, width, shift);
-    const vrm::Pose T = vrm::rm_load_pose<ALIGNED16>(poses, m);
+    const uint32_t m = measurement_column(row, idx - row * width, width, shift);
+    const Pose T = load_pose<ALIGNED16>(poses, m);
     const float d[3] = {dm[0], dm[1], dm[2]}, o[3] = {om[0], om[1], om[2]};
     ray_pose_apply(T, d, o, dm, om);
   }

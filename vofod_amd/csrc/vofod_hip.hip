@@ -15,6 +15,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -33,7 +34,6 @@
 #include "kernels_voxelize.h"
 #include "mapsync.h"
 #include "range_decode.h"
-#include "range_motion.h"
 #include "detection_points.h"
 #include "map_shift.h"
 
@@ -338,15 +338,12 @@ struct Workspace
   DevBuf<float> d_stage;  // F * pt_cap * 5 words: x, y, z, intensity, range of host-resident inputs
   DevBuf<char> d_stage_aos;  // host-resident array-of-structs clouds (the nodelet's 48-byte ouster_ros::Point) cross the link as they are:
   size_t aos_pitch = 0;      // F * aos_pitch bytes, allocated on first use; the kernels read x / y / z in place at the struct's stride
-  // range images of the batch (range_decode.h): their job list, written in pinned memory by stage_inputs and uploaded with the inputs
+  // range images of the batch (range_decode.h): their job list, written in pinned memory by stage_inputs and uploaded with the inputs -
+  // the n_mjobs jobs that carry a pose per column first, the n_rjobs without behind them (a frame is one or the other: F entries) -
+  // and the block host-resident pose tables are staged into: F * width * 12 floats, allocated on the first such scan of this workspace
   DevBuf<vrd::RangeJob> d_rjobs;
   PinBuf<vrd::RangeJob> h_rjobs;
-  uint32_t n_rjobs = 0;
-  // ... and those that carry a pose per column (range_motion.h): a job list of their own, and the block host-resident pose tables are
-  // staged into - F * width * 12 floats, allocated on the first such scan of this workspace
-  DevBuf<vrm::MotionJob> d_mjobs;
-  PinBuf<vrm::MotionJob> h_mjobs;
-  uint32_t n_mjobs = 0;
+  uint32_t n_mjobs = 0, n_rjobs = 0;
   DevBuf<float> d_poses;
   DevBuf<PackedFrame> d_packed;
   PinBuf<PackedFrame> h_packed;
@@ -475,8 +472,6 @@ private:
     HIP_TRY(d_stage.alloc(5 * static_cast<size_t>(F_) * pt_cap_));
     HIP_TRY(d_rjobs.alloc(F_));
     HIP_TRY(h_rjobs.alloc(F_));
-    HIP_TRY(d_mjobs.alloc(F_));
-    HIP_TRY(h_mjobs.alloc(F_));
     HIP_TRY(d_packed.alloc(F_));
     HIP_TRY(d_lite.alloc(F_));
     HIP_TRY(d_tailc.alloc(vtd::TP_MAXC * static_cast<size_t>(F_)));
@@ -907,6 +902,16 @@ int build_close_rows(float max_dist, float vs_inv, std::vector<CloseRow>& rows)
   return VOFOD_OK;
 }
 
+// the closed exclude box of the first crop, sensor frame (vofod_nodelet.cpp:626-629)
+void exclude_box(const vofod_handle* h, float lo[3], float hi[3])
+{
+  for (int a = 0; a < 3; a++)
+  {
+    hi[a] = h->exclude_center[a] + h->sp.exclude_size[a] / 2;
+    lo[a] = h->exclude_center[a] - h->sp.exclude_size[a] / 2;
+  }
+}
+
 void fill_grid_params(vofod_handle* h, GridParams& g, const float leaf[3], bool align, const float align_center[3], const Workspace& ws)
 {
   std::memset(&g, 0, sizeof(g));
@@ -922,11 +927,10 @@ void fill_grid_params(vofod_handle* h, GridParams& g, const float leaf[3], bool 
         aco += leaf[a];
       g.aco[a] = aco;
     }
-    g.ex_max[a] = h->exclude_center[a] + h->sp.exclude_size[a] / 2;  // vofod_nodelet.cpp:626-629
-    g.ex_min[a] = h->exclude_center[a] - h->sp.exclude_size[a] / 2;
     g.op_max[a] = h->oparea_center[a] + h->sp.oparea_size[a] / 2;  // :645-648
     g.op_min[a] = h->oparea_center[a] - h->sp.oparea_size[a] / 2;
   }
+  exclude_box(h, g.ex_min, g.ex_max);
   g.align = align;
   g.words_cap = ws.words_cap;
   g.vox_cap = ws.vox_cap;
