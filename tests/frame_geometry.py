@@ -62,7 +62,7 @@ def ref_lattice(off, size, vs, cap=None):
 
 
 # the switches of tools/run_fallback_matrix.sh: under one of them a batch may take other kernels than the route a case names
-FALLBACK_SWITCHES = ("VOFOD_CLOSE_FIRST", "VOFOD_DEVICE_TAIL", "VOFOD_LITE", "VOFOD_SLABS", "VOFOD_SLAB_EMIT", "VOFOD_BRICK_LDS", "VOFOD_DILATE", "VOFOD_CCL", "VOFOD_EXPLORE")
+FALLBACK_SWITCHES = ("VOFOD_CLOSE_FIRST", "VOFOD_DEVICE_TAIL", "VOFOD_SLABS", "VOFOD_SLAB_EMIT", "VOFOD_BRICK_LDS", "VOFOD_DILATE", "VOFOD_CCL", "VOFOD_EXPLORE")
 
 # (the 0.2 m row has 128 cells along z where the table this one was drawn up from had 127: the lowest cell is floor(-1.25 / 0.2) = -7,
 # the alignment remainder 0.15 moves the offset to -1.55, and (23.75 + 1.55) / 0.2 = 126.5 gives 126 + 2.  fill_ref_lattice says 128;

@@ -93,11 +93,11 @@ def test_bench_workload_256_frames_os1_128(oracle, hip, fallback, monkeypatch):
     names = _profiled_kernels(dev.lib, dev)
     dev.lib.profile_enable(dev.h, 0)
     if not os.environ.get("VOFOD_TEST_HARNESS_SELFCHECK"):
-        expect = {"": "k_frame_lds_far", "VOFOD_CLOSE_FIRST=0": "k_frame_lds_full", "VOFOD_DEVICE_TAIL=0": "k_pack_lite", "VOFOD_LDS_MAX_BRICKS=4096": "k_brick_root"}[fallback]
+        expect = {"": "k_frame_lds_far", "VOFOD_CLOSE_FIRST=0": "k_frame_lds_full", "VOFOD_DEVICE_TAIL=0": "k_pack", "VOFOD_LDS_MAX_BRICKS=4096": "k_brick_root"}[fallback]
         assert expect in names, (fallback, names)
         if fallback == "":
             assert "k_tail_far" in names, names
-    # (the calls without debug output read back the lite slots - candidate clusters only; the debug call above the full tables)
+    # (production call and debug call above: the same detections, whichever tail built them)
     np.testing.assert_array_equal(want[0]["n_points"], db_full["n_points"])
     np.testing.assert_array_equal(want[0]["frame"], db_full["frame"])
     np.testing.assert_array_equal(want[0]["position"], db_full["position"])

@@ -118,8 +118,9 @@ def test_lean_equals_full_equals_oracle(case, monkeypatch):
 def test_stale_records_of_other_frames(case, monkeypatch):
     """One handle, in order: production batch A; the far-only debug view of OTHER frames C - the full emission: it leaves complete,
     plausible records in every slot; production batch B with other poses through the device tail, and again under
-    VOFOD_DEVICE_TAIL=0, where k_pack_lite reads the same records for the host tail.  A reader that touched a record B did not
-    write would now see C's.  Then C's view once more: bit-exact against the oracle's far view, weights included - a lean launch
+    VOFOD_DEVICE_TAIL=0, where k_pack reads the same records for the host tail - and more of them: the far clusters' table and
+    up to 768 candidate members with their voxel records, all of them in pure-far bricks, which B's lean launch writes.  A reader
+    that touched a record B did not write would now see C's.  Then C's view once more: bit-exact against the oracle's far view, weights included - a lean launch
     leaves nothing behind (extras list, parked bitmap) that a full launch trips over."""
     A, C_, B = case.batch(0, 4), case.batch(4, 8), case.batch(8, 12)
     oa, oc, ob = case.oracle("A4", *A), case.oracle("C4", *C_), case.oracle("B4", *B)
@@ -140,7 +141,7 @@ def test_stale_records_of_other_frames(case, monkeypatch):
         case.dev.lib.profile_enable(case.dev.h, 0)
     monkeypatch.delenv("VOFOD_DEVICE_TAIL")
     if ROUTE_CHECKED:
-        assert "k_frame_lds_far" in ran and "k_pack_lite" in ran and "k_tail_far" not in ran, ran
+        assert "k_frame_lds_far" in ran and "k_pack" in ran and "k_tail_far" not in ran, ran
     _assert_same(ob[:2], got)
     dc2, pc2, gc2 = case.dev.process_batch(*C_, debug=True, far_only=True)
     _assert_same(oc[:2], (dc2, pc2))

@@ -1,5 +1,6 @@
-"""The device classification tail (kernels_tail.h: k_tail_far, or k_tail_prep + k_explore + k_tail_finish) at its capacities and
-gate boundaries, on scenes placed by hand (tests/tail_edges.py) - the random scenes of the other files cross these limits by wide
+"""The classification tail at its capacities and gate boundaries: the device tail (kernels_tail.h: k_tail_far, or k_tail_prep +
+k_explore + k_tail_finish) and, on the gate scenes, the host tail (frames_collect.h) - the three callers of vt::classify_gates
+(host_tail.h), the one statement of boxes, gates and explore job.  The scenes are placed by hand (tests/tail_edges.py) - the random scenes of the other files cross these limits by wide
 margins or stay far below them, and none of them says which overflow branch a scan took.
 
 The recipe is the one of test_far_edge_window_that_starts_in_the_last_word_of_an_empty_bitmap_block: OS1-16, 0.25 m voxels, an apriori
@@ -12,6 +13,10 @@ Every scene runs through three device routes and is compared with the oracle by 
   batch   read-only batch of four frames, k_frame_lds_far + k_tail_far (process_batch, then batch_submit / batch_collect twice);
   full    the same under VOFOD_CLOSE_FIRST=0: k_frame_lds_full + k_tail_prep / k_explore / k_tail_finish;
   scan    single map-updating scans without debug output, k_far_final + k_tail_far; map and flags compared bit for bit afterwards.
+The gate scenes (cases 5 and 6) run through a fourth, with the same comparisons and statements:
+  host    the batch under VOFOD_DEVICE_TAIL=0: k_frame_lds_far, then k_pack (read-back of the full tables) and the host tail
+          (prep_frame_tail, k_explore for the fills); no kernel of the device tail runs.  The capacity cases are not run on it:
+          the host tail has none of the device's capacities.
 Ids, frames, point counts and per-frame counts are compared exactly (both sides make the same calls: their id counters stay in step).
 
 Statements of the scene itself, so that a misreading shared by product and oracle does not hide:
@@ -45,6 +50,7 @@ pytestmark = pytest.mark.gpu
 
 VS = te.VS
 ROUTES = ["batch", "full", "scan"]
+GATE_ROUTES = ROUTES + ["host"]
 
 
 def _selfcheck():
@@ -235,7 +241,8 @@ def _observed(ran):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the routes
-def _run_batch(bench, scene, full, checked, label):
+def _run_batch(bench, scene, route, checked, label):
+    full = route == "full"
     ref, dev = bench.ref, bench.dev
     scans, tfs = bench.scans, bench.tfs
     da, pa, gs = ref.process_batch(scans, tfs, debug=True)
@@ -247,7 +254,10 @@ def _run_batch(bench, scene, full, checked, label):
     _check_positions(bench, scene, db, pb)
     if checked:
         host_tail = None if scene.trips == "open" else scene.trips is not None
-        if full:
+        if route == "host":
+            assert "k_frame_lds_far" in ran and "k_frame_lds_full" not in ran, ran
+            assert ran.get("k_pack", 0) == 1 and [k for k in ran if k.startswith(("k_tail", "k_pack"))] == ["k_pack"], ran
+        elif full:
             assert "k_frame_lds_full" in ran and "k_frame_lds_far" not in ran and "k_tail_far" not in ran, ran
             assert ran.get("k_tail_finish", 0) == 1 and ran.get("k_explore", 0) >= 1, ran
             _assert_tail(ran, "k_tail_prep", host_tail)  # (k_explore is part of this chain: who ran the fills cannot be told here)
@@ -321,8 +331,10 @@ def _run(bench, scene, route, monkeypatch, label):
     checked = _route_checked()  # (before this test's own switch is set)
     if route == "full":
         monkeypatch.setenv("VOFOD_CLOSE_FIRST", "0")  # switches are read on every call
+    if route == "host":
+        monkeypatch.setenv("VOFOD_DEVICE_TAIL", "0")
     bench.load(scene)
-    counts = _run_scans(bench, scene, checked, label) if route == "scan" else _run_batch(bench, scene, route == "full", checked, label)
+    counts = _run_scans(bench, scene, checked, label) if route == "scan" else _run_batch(bench, scene, route, checked, label)
     bench.clean = True
     return counts
 
@@ -392,7 +404,7 @@ def test_fill_radius_at_the_limit(bench, monkeypatch, max_explore, R, open_, rou
             assert c["frontiers"] == len(te.diamond(*te.POCKET_FULL)), c["frontiers"]
 
 
-@pytest.mark.parametrize("route", ROUTES)
+@pytest.mark.parametrize("route", GATE_ROUTES)
 def test_gates_on_the_device(bench, monkeypatch, route):
     """case 5, the three gates at min_points = 2: obb_size > max_size on lines of 12 / 13 / 14 voxels along every axis (the 13-voxel
     line is exactly 3.0 m long: held to the oracle only) and on the diagonal lines; size >= min_points on single voxels and
@@ -402,19 +414,19 @@ def test_gates_on_the_device(bench, monkeypatch, route):
     assert c["candidates"] == 17 and 7 <= c["detections"] <= 10
 
 
-@pytest.mark.parametrize("route", ROUTES)
+@pytest.mark.parametrize("route", GATE_ROUTES)
 def test_min_points_4_on_the_device(bench, monkeypatch, route):
     """case 5, size >= min_points at min_points = 4: clusters of 2 and 3 voxels are dropped, clusters of 4 are detections"""
     c = _run(bench, te.scene_min_points_4(), route, monkeypatch, f"min_points 4 {route}")
     assert c["candidates"] == 6 and c["detections"] == 6
 
 
-@pytest.mark.parametrize("route", ROUTES)
+@pytest.mark.parametrize("route", GATE_ROUTES)
 def test_degenerate_lattice_shapes_on_the_device(bench, monkeypatch, route):
     """case 6: the shapes of test_obb_gates_on_degenerate_lattice_clusters (repeated eigenvalues everywhere: eigsolve3.h) through the
     device copy of vt::boxes_of_n, at map x above 62 m where float32 is coarse.  55 floating shapes cannot share a frame on the
     device routes (TP_MAXD = 16: the host tail would compute the boxes): 14 / 14 / 14 / 13 in the four frames of the batch, each
-    also a single scan."""
+    also a single scan.  Route host: the same four frames through the host's call of the same function."""
     scene = te.scene_degenerate()
     assert min(s.cells[:, 0].min() for f in scene.frames for s in f) >= 330 and sum(len(f) for f in scene.frames) == 55
     c = _run(bench, scene, route, monkeypatch, f"degenerate shapes {route}")

@@ -6,8 +6,8 @@
 # kernels and only changes what a kernel does (the lean emission's, README "Environment switches"): the route assertions of the
 # tests hold the list below to the switches that move a batch to other kernels
 set -o pipefail
-ALL=("" VOFOD_CLOSE_FIRST=0 VOFOD_DEVICE_TAIL=0 VOFOD_LITE=0 VOFOD_SLABS=0 VOFOD_SLAB_EMIT=0 VOFOD_BRICK_LDS=0 VOFOD_DILATE=0 VOFOD_CCL=voxel "VOFOD_DEVICE_TAIL=0 VOFOD_LITE=0" "VOFOD_CLOSE_FIRST=0 VOFOD_DEVICE_TAIL=0" VOFOD_EXPLORE=host)
-QUICK=(VOFOD_CLOSE_FIRST=0 VOFOD_DEVICE_TAIL=0 "VOFOD_DEVICE_TAIL=0 VOFOD_LITE=0" VOFOD_BRICK_LDS=0 VOFOD_CCL=voxel)
+ALL=("" VOFOD_CLOSE_FIRST=0 VOFOD_DEVICE_TAIL=0 VOFOD_SLABS=0 VOFOD_SLAB_EMIT=0 VOFOD_BRICK_LDS=0 VOFOD_DILATE=0 VOFOD_CCL=voxel "VOFOD_CLOSE_FIRST=0 VOFOD_DEVICE_TAIL=0" VOFOD_EXPLORE=host)
+QUICK=(VOFOD_CLOSE_FIRST=0 VOFOD_DEVICE_TAIL=0 VOFOD_BRICK_LDS=0 VOFOD_CCL=voxel)
 if [ "$1" = quick ]; then SW=("${QUICK[@]}"); else SW=("${ALL[@]}"); fi
 for x in $MATRIX_EXTRA; do SW+=("$x"); done
 TESTS=tests

@@ -19,9 +19,6 @@ int print_deferred_prof(vofod_handle* h, Workspace& ws, uint32_t n)
 // global-memory kernels.
 int adopt_status(vofod_handle* h, Workspace& ws, uint32_t n)
 {
-  if (ws.lite)
-    for (uint32_t f = 0; f < n; f++)
-      ws.h_packed[f].hdr = ws.h_lite[f].hdr;  // the host tail reads the frames through the packed slots
   if (ws.dtail)
     for (uint32_t f = 0; f < n; f++)
       ws.h_packed[f].hdr.status = ws.h_dets[f].status;
@@ -72,12 +69,51 @@ int check_close_first_overflow(vofod_handle* h, Workspace& ws, uint32_t n)
   return VOFOD_OK;
 }
 
-// ---- the tail ran on the device: extractDetections' record (:848-877) from the raw detections, frame by frame
+// What the three record builders below share: extractDetections' record (:848-877) for one detection after the other - ids,
+// the references vofod_detection_points answers from, the caller's array up to its capacity - and the ending of the call.
+struct RecordSink
+{
+  vofod_handle* h;
+  Workspace& ws;
+  const FrameCall& call;
+  vofod_detection* out;
+  size_t cap;
+  uint32_t* n_out_per_frame;
+  size_t total = 0, frame_begin = 0;
+  RecordSink(vofod_handle* h_, Workspace& ws_, const FrameCall& call_, vofod_detection* out_, size_t cap_, uint32_t* n_out_per_frame_)
+      : h(h_), ws(ws_), call(call_), out(out_), cap(cap_), n_out_per_frame(n_out_per_frame_)
+  {
+    ws.det_begin(call.submitted, call.g.vox_cap);
+  }
+  void add(uint32_t f, uint32_t root, const float center[3], uint32_t n_points, double conf_sum)
+  {
+    const vofod_detection det = vt::make_detection(h->last_detection_id++, call.tfs + 12 * f, center, n_points, conf_sum, f, h->sp, *call.dp);
+    ws.det_refs.push_back({det.id, f, root, n_points});
+    if (out && total < cap)
+      out[total] = det;
+    total++;
+  }
+  void frame_done(uint32_t f)
+  {
+    if (n_out_per_frame)
+      n_out_per_frame[f] = static_cast<uint32_t>(total - frame_begin);
+    frame_begin = total;
+  }
+  int close(int ret, size_t* n_out)
+  {
+    *n_out = total;
+    if (total > cap)
+      ret = VOFOD_ERR_CAPACITY;
+    ws.det_valid = ret == VOFOD_OK;
+    return ret;
+  }
+};
+
+// ---- the tail ran on the device: the raw detections, frame by frame
 int device_tail_records(vofod_handle* h, Workspace& ws, const FrameCall& call, vofod_detection* out, size_t cap, uint32_t* n_out_per_frame, size_t* n_out)
 {
   const uint32_t n = call.n;
   int ret = VOFOD_OK;
-  size_t total = 0;
   if (call.submitted && out)
   {
     // an output array too small for this batch: nothing is consumed - the ticket stays pending, ids are not handed
@@ -92,31 +128,19 @@ int device_tail_records(vofod_handle* h, Workspace& ws, const FrameCall& call, v
       return VOFOD_ERR_CAPACITY;
     }
   }
-  ws.det_begin(call.submitted, call.g.vox_cap);
+  RecordSink sink(h, ws, call, out, cap, n_out_per_frame);
   for (uint32_t f = 0; f < n; f++)
   {
     const vtd::FrameDets& D = ws.h_dets[f];
     if (D.status != VOFOD_OK)
       ret = D.status;
     for (uint32_t i = 0; i < D.n; i++)
-    {
-      const vtd::DetRaw& R = D.d[i];
-      const vofod_detection det = vt::make_detection(h->last_detection_id++, call.tfs + 12 * f, R.center, R.n_points, R.conf_sum, f, h->sp, *call.dp);
-      ws.det_refs.push_back({det.id, f, R.root, R.n_points});
-      if (out && total < cap)
-        out[total] = det;
-      total++;
-    }
-    if (n_out_per_frame)
-      n_out_per_frame[f] = D.n;
+      sink.add(f, D.d[i].root, D.d[i].center, D.d[i].n_points, D.d[i].conf_sum);
+    sink.frame_done(f);
   }
   if (trace_on())
-    std::fprintf(stderr, "[vofod trace] n=%u device tail: sync %.3f end %.3f ms, %zu detections\n", n, call.tr_sync1, ms_since(call.t0), total);
-  *n_out = total;
-  if (total > cap)
-    ret = VOFOD_ERR_CAPACITY;
-  ws.det_valid = ret == VOFOD_OK;
-  return ret;
+    std::fprintf(stderr, "[vofod trace] n=%u device tail: sync %.3f end %.3f ms, %zu detections\n", n, call.tr_sync1, ms_since(call.t0), sink.total);
+  return sink.close(ret, n_out);
 }
 
 // A map-updating scan whose flood fills have already written their frontiers to the map: the tail cannot be run again.
@@ -133,23 +157,12 @@ int device_tail_overflow_records(vofod_handle* h, Workspace& ws, const FrameCall
   std::vector<vc::ExploreResult> res(vtd::TP_MAXC);
   HIPCHK(hipMemcpy(tc.data(), ws.d_tailc, sizeof(vtd::TailCluster) * vtd::TP_MAXC, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(res.data(), h->explore.d_results, sizeof(vc::ExploreResult) * vtd::TP_MAXC, hipMemcpyDeviceToHost));  // (frame 0: result slots 0..TP_MAXC-1)
-  size_t total = 0;
-  ws.det_begin(call.submitted, call.g.vox_cap);
+  RecordSink sink(h, ws, call, out, cap, n_out_per_frame);
   for (int c = 0; c < vtd::TP_MAXC; c++)
-  {
-    if (tc[c].job < 0 || tc[c].job >= vtd::TP_MAXC || !res[tc[c].job].floating)
-      continue;
-    const vofod_detection det = vt::make_detection(h->last_detection_id++, call.tfs, tc[c].obb_center, tc[c].n_members, res[tc[c].job].conf_sum, 0, h->sp, *call.dp);
-    ws.det_refs.push_back({det.id, 0u, tc[c].root, tc[c].n_members});
-    if (out && total < cap)
-      out[total] = det;
-    total++;
-  }
-  if (n_out_per_frame)
-    n_out_per_frame[0] = static_cast<uint32_t>(total);
-  *n_out = total;
-  ws.det_valid = total <= cap;
-  return total > cap ? VOFOD_ERR_CAPACITY : VOFOD_OK;
+    if (tc[c].job >= 0 && tc[c].job < vtd::TP_MAXC && res[tc[c].job].floating)
+      sink.add(0u, tc[c].root, tc[c].obb_center, tc[c].n_members, res[tc[c].job].conf_sum);
+  sink.frame_done(0u);
+  return sink.close(VOFOD_OK, n_out);
 }
 
 // ---- host tail: classifyClusters :961 + extractDetections :963.
@@ -184,44 +197,15 @@ int fetch_big_tables(vofod_handle* h, Workspace& ws, const GridParams& g, uint32
   for (uint32_t f = 0; f < n; f++)
   {
     FrameTail& T = tails[f];
-    FrameHdr& hdr = ws.h_packed[f].hdr;
+    const FrameHdr& hdr = ws.h_packed[f].hdr;
     if (hdr.status != VOFOD_OK)
       ret = hdr.status;
-    if (ws.lite)
+    T.big_recs = hdr.C > SPEC_C;
+    T.big_members = hdr.n_cand > SPEC_M;
+    if (T.big_recs)
     {
-      // lite read-back: only the candidate clusters' records came back; the header's C becomes their number
-      const PackedLite& L = ws.h_lite[f];
-      PackedFrame& pf = ws.h_packed[f];
-      if (L.n_recs <= LITE_C)
-      {
-        std::memcpy(pf.table, L.recs, sizeof(ClusterRec) * L.n_recs);
-        static_assert(LITE_C <= SPEC_C && LITE_M <= SPEC_M, "the lite lists are unpacked into the packed slot");
-      }
-      else
-      {
-        // more candidate clusters than the lite slot holds: fetch the frame's whole table, keep the candidates
-        std::vector<ClusterRec> all(hdr.C);
-        HIPCHK(hipMemcpy(all.data(), ws.d_table + static_cast<size_t>(f) * ws.vox_cap, sizeof(ClusterRec) * hdr.C, hipMemcpyDeviceToHost));
-        for (const ClusterRec& r : all)
-          if (r.cand && !r.close)
-            T.recs_big.push_back(r);
-        T.big_recs = true;
-      }
-      hdr.C = L.n_recs;
-      if (L.n_members <= LITE_M)
-        std::memcpy(pf.members, L.members, sizeof(CandMemberX) * L.n_members);
-      else
-        T.big_members = true;
-    }
-    else
-    {
-      T.big_recs = hdr.C > SPEC_C;
-      T.big_members = hdr.n_cand > SPEC_M;
-      if (T.big_recs)
-      {
-        T.recs_big.resize(hdr.C);
-        HIPCHK(hipMemcpy(T.recs_big.data(), ws.d_table + static_cast<size_t>(f) * ws.vox_cap, sizeof(ClusterRec) * hdr.C, hipMemcpyDeviceToHost));
-      }
+      T.recs_big.resize(hdr.C);
+      HIPCHK(hipMemcpy(T.recs_big.data(), ws.d_table + static_cast<size_t>(f) * ws.vox_cap, sizeof(ClusterRec) * hdr.C, hipMemcpyDeviceToHost));
     }
     if (T.big_members)
     {
@@ -236,7 +220,7 @@ int fetch_big_tables(vofod_handle* h, Workspace& ws, const GridParams& g, uint32
 }
 
 // phase B (one frame, run in parallel over the frames): canonical order, member index, boxes and gates, the frame's explore jobs
-void prep_frame_tail(const vofod_handle* h, const PackedFrame& pf, uint32_t f, const float* tf, const vofod_dyn_params& dp, bool latches, FrameTail& T)
+void prep_frame_tail(const vofod_handle* h, const PackedFrame& pf, uint32_t f, const float* tf, const vt::TailParams& tp, FrameTail& T)
 {
   const FrameHdr& hdr = pf.hdr;
   const ClusterRec* recs = T.big_recs ? T.recs_big.data() : pf.table;
@@ -260,10 +244,8 @@ void prep_frame_tail(const vofod_handle* h, const PackedFrame& pf, uint32_t f, c
     T.by_root.build(tmp);
   }
   T.job_of.assign(hdr.C, -1);
-  const float tpos[3] = {tf[3], tf[7], tf[11]};
   std::vector<vc::ExploreJob>& jl = T.jobs;
   std::vector<int>& ml = T.members;
-  // classify_cluster :1648-1690: boxes and gates
   for (uint32_t ci = 0; ci < hdr.C; ci++)
   {
     HostCluster& c = T.cl[ci];
@@ -273,45 +255,31 @@ void prep_frame_tail(const vofod_handle* h, const PackedFrame& pf, uint32_t f, c
     if (!c.rec.cand)
       continue;  // fails min_points or cannot pass max_size (device-side gate)
     const vt::MemberSpan mem = T.by_root.of(c.rec.root);
-    c.boxes = vt::boxes_of(mem);
-    c.evaluated = true;
-    if (static_cast<int>(mem.size()) < dp.classification__min_points)
-      continue;
-    {
-      const float d[3] = {tpos[0] - c.boxes.obb_center[0], tpos[1] - c.boxes.obb_center[1], tpos[2] - c.boxes.obb_center[2]};
-      const double dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-      if (dist > dp.classification__max_distance)
-        continue;
-    }
-    {
-      const float d[3] = {c.boxes.obb_max[0] - c.boxes.obb_min[0], c.boxes.obb_max[1] - c.boxes.obb_min[1], c.boxes.obb_max[2] - c.boxes.obb_min[2]};
-      c.obb_size = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-      if (c.obb_size > dp.classification__max_size)
-        continue;
-    }
-    if (!latches)  // :1694, :1719-1722
-    {
+    auto get = [&](size_t i, float p[3]) {
+      for (int a = 0; a < 3; a++)
+        p[a] = mem[i].p[a];
+    };
+    // classify_cluster :1648-1696: boxes, gates, the explore job's radius and box
+    c.gates = vt::classify_gates(static_cast<uint32_t>(mem.size()), get, tf, tp, h->hg.off, h->hg.vs_inv, h->hg.s);
+    if (c.gates.passed && !c.gates.explore)  // without the latches :1694, :1719-1722
       c.cclass = VOFOD_CLASS_UNKNOWN;
+    if (!c.gates.explore)
       continue;
-    }
     vc::ExploreJob job{};
     job.frame = f;
     job.n_members = static_cast<uint32_t>(mem.size());
     job.member_off = static_cast<uint32_t>(ml.size() / 3);  // rebased when the frames are concatenated
-    job.R = static_cast<int>((c.obb_size + dp.classification__max_explore_distance) / h->sp.voxel_size);  // :1696
+    job.R = c.gates.R;
+    for (int a = 0; a < 3; a++)
+    {
+      job.box_lo[a] = c.gates.box_lo[a];
+      job.box_hi[a] = c.gates.box_hi[a];
+    }
     for (const vt::Member& m : mem)
     {
       int o[3];
       h->hg.coordToIdx(m.p, o);
       ml.insert(ml.end(), o, o + 3);
-    }
-    int mn[3], mx[3];  // getSubmapCopy(aabb, inflate 2) voxel_map.cpp:550-559
-    h->hg.coordToIdx(c.boxes.aabb_min, mn);
-    h->hg.coordToIdx(c.boxes.aabb_max, mx);
-    for (int a = 0; a < 3; a++)
-    {
-      job.box_lo[a] = std::clamp(mn[a] - 2, 0, h->hg.s[a] - 1);
-      job.box_hi[a] = std::clamp(mx[a] + 2, 0, h->hg.s[a] - 1);
     }
     if (job.R > vc::EX_MAX_R || job.R < 0)
       T.host_fallback = true;
@@ -371,25 +339,17 @@ int explore_on_device(vofod_handle* h, const FrameCall& call, ExploreWork& w, fl
   return VOFOD_OK;
 }
 
-// extractDetections :834-879 for one frame; returns the number of its detections
-uint32_t extract_detections(vofod_handle* h, Workspace& ws, const FrameTail& T, uint32_t f, const float* tf, const vofod_dyn_params& dp, const std::vector<vc::ExploreResult>& results, vofod_detection* out,
-                            size_t cap, size_t& total)
+// extractDetections :834-879 for one frame
+void extract_detections(RecordSink& sink, const FrameTail& T, uint32_t f, const std::vector<vc::ExploreResult>& results)
 {
-  uint32_t n_det_frame = 0;
   for (size_t ci = 0; ci < T.cl.size(); ci++)
   {
     const HostCluster& c = T.cl[ci];
     if (c.rec.close || c.cclass != VOFOD_CLASS_MAV)
       continue;
-    const vt::MemberSpan mem = T.by_root.of(c.rec.root);
-    const vofod_detection det = vt::make_detection(h->last_detection_id++, tf, c.boxes.obb_center, mem.size(), results[T.job_of[ci]].conf_sum, f, h->sp, dp);
-    ws.det_refs.push_back({det.id, f, c.rec.root, static_cast<uint32_t>(mem.size())});
-    if (out && total < cap)
-      out[total] = det;
-    total++;
-    n_det_frame++;
+    sink.add(f, c.rec.root, c.gates.obb_center, static_cast<uint32_t>(T.by_root.of(c.rec.root).size()), results[T.job_of[ci]].conf_sum);
   }
-  return n_det_frame;
+  sink.frame_done(f);
 }
 
 // the debug view of one frame (vofod_scan_debug): counts, weighted cloud, labels, cluster list
@@ -453,9 +413,9 @@ int fill_debug_view(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_
         {
           ci.aabb_min[a] = (static_cast<float>(hc.rec.imin[a]) + 0.5f) * g.leaf[a] + hdr.offset[a];
           ci.aabb_max[a] = (static_cast<float>(hc.rec.imax[a]) + 0.5f) * g.leaf[a] + hdr.offset[a];
-          ci.obb_center[a] = hc.evaluated ? hc.boxes.obb_center[a] : NAN;
+          ci.obb_center[a] = hc.gates.evaluated ? hc.gates.obb_center[a] : NAN;
         }
-        ci.obb_size = hc.obb_size;
+        ci.obb_size = hc.gates.obb_size;
       }
   }
   return VOFOD_OK;
@@ -471,12 +431,12 @@ int host_tail(vofod_handle* h, Workspace& ws, const FrameCall& call, const doubl
   const auto t_tail = clk::now();
   const float thr_new = static_cast<float>(dp.voxel_map__thresholds__new_obstacles);
   const float thr_frontiers = static_cast<float>(dp.voxel_map__thresholds__frontiers);
-  const bool latches = h->background_pts_sufficient && h->sure_background_sufficient;
+  const vt::TailParams tp = tail_params(h, dp);
   int ret = VOFOD_OK;
   std::vector<FrameTail> tails(n);
   ExploreWork w;
   VCHK(fetch_big_tables(h, ws, call.g, n, tails, ret));
-  h->pool->parallel_for(n, [&](uint32_t f) { prep_frame_tail(h, ws.h_packed[f], f, call.tfs + 12 * f, dp, latches, tails[f]); });
+  h->pool->parallel_for(n, [&](uint32_t f) { prep_frame_tail(h, ws.h_packed[f], f, call.tfs + 12 * f, tp, tails[f]); });
   concat_jobs(tails, w);
   const double tr_prep = ms_since(call.t0);
 
@@ -487,8 +447,7 @@ int host_tail(vofod_handle* h, Workspace& ws, const FrameCall& call, const doubl
     VCHK(explore_on_device(h, call, w, thr_new, no_update));
   const double tr_explore = ms_since(call.t0);
 
-  size_t total = 0;
-  ws.det_begin(call.submitted, call.g.vox_cap);
+  RecordSink sink(h, ws, call, out, cap, n_out_per_frame);
   for (uint32_t f = 0; f < n; f++)
   {
     FrameTail& T = tails[f];
@@ -500,9 +459,7 @@ int host_tail(vofod_handle* h, Workspace& ws, const FrameCall& call, const doubl
     for (size_t ci = 0; ci < T.cl.size(); ci++)
       if (const int ji = T.job_of[ci]; ji >= 0)
         T.cl[ci].cclass = w.results[ji].floating ? VOFOD_CLASS_MAV : VOFOD_CLASS_UNKNOWN;
-    const uint32_t n_det_frame = extract_detections(h, ws, T, f, call.tfs + 12 * f, dp, w.results, out, cap, total);
-    if (n_out_per_frame)
-      n_out_per_frame[f] = n_det_frame;
+    extract_detections(sink, T, f, w.results);
     if (dbg)
     {
       vofod_scan_debug& d = dbg[f];
@@ -521,16 +478,12 @@ int host_tail(vofod_handle* h, Workspace& ws, const FrameCall& call, const doubl
       sumC += ws.h_packed[f].hdr.C;
       sumCand += ws.h_packed[f].hdr.n_cand;
       for (const auto& c : tails[f].cl)
-        sumEval += c.evaluated;
+        sumEval += c.gates.evaluated;
     }
     std::fprintf(stderr, "[vofod trace] n=%u launch %.3f sync1 %.3f prep %.3f explore %.3f end %.3f ms jobs %zu C %zu cand_members %zu evaluated %zu\n", n, call.tr_launch, call.tr_sync1, tr_prep,
                  tr_explore, ms_since(call.t0), w.jobs.size(), sumC, sumCand, sumEval);
   }
-  *n_out = total;
-  if (total > cap)
-    ret = VOFOD_ERR_CAPACITY;
-  ws.det_valid = ret == VOFOD_OK;
-  return ret;
+  return sink.close(ret, n_out);
 }
 
 // The collect half: `call` comes from launch_frames of the same synchronous call, or from ticket_call.

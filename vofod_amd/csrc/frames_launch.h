@@ -37,7 +37,7 @@ struct LaunchRoute
   hipStream_t chain = nullptr;    // submitted: the stream of the chain (the ticket's own, or the streaming stage's); nullptr: the handle's
   int own_tail = -1;              // submitted small batch: the ticket whose stream and flood-fill buffers the device tail takes
   bool single_update = false;     // one map-updating scan, synchronous: the reference's own mode
-  bool dtail = false, lite = false;  // device tail / lite read-back (neither: the full tables come back)
+  bool dtail = false;             // the classification tail runs on the device (otherwise the full tables come back for the host tail)
 };
 
 // h->stream names the stream every KLAUNCH goes to.  A scope that sends the launches elsewhere (or moves h->stream itself
@@ -106,6 +106,19 @@ vc::ExploreParams explore_params(const vofod_dyn_params& dp, float thr_new, bool
   ep.no_update = no_update ? 1 : 0;
   ep.stack_cap = vc::EX_CELLS;
   return ep;
+}
+
+// the gates' parameters (classify_cluster :1648-1696) as the device tail and the host tail take them
+vt::TailParams tail_params(const vofod_handle* h, const vofod_dyn_params& dp)
+{
+  vt::TailParams tp{};
+  tp.min_points = dp.classification__min_points;
+  tp.max_distance = dp.classification__max_distance;
+  tp.max_size = dp.classification__max_size;
+  tp.max_explore = dp.classification__max_explore_distance;
+  tp.voxel_size = h->sp.voxel_size;
+  tp.latches = (h->background_pts_sufficient && h->sure_background_sufficient) ? 1 : 0;
+  return tp;
 }
 
 // read-back of the full tables: header, speculative cluster records and candidate members of every frame
@@ -543,13 +556,7 @@ int launch_device_tail(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, co
   }
   else
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_explore, 0));  // (a synchronous call: wait for the tails of batches in flight)
-  vtd::TailParams tp{};
-  tp.min_points = dp.classification__min_points;
-  tp.max_distance = dp.classification__max_distance;
-  tp.max_size = dp.classification__max_size;
-  tp.max_explore = dp.classification__max_explore_distance;
-  tp.voxel_size = h->sp.voxel_size;
-  tp.latches = (h->background_pts_sufficient && h->sure_background_sufficient) ? 1 : 0;
+  const vt::TailParams tp = tail_params(h, dp);
   const vc::ExploreParams ep = explore_params(dp, static_cast<float>(dp.voxel_map__thresholds__new_obstacles), rt.no_update);
   // the records (135 KB) go straight into the pinned host slots from the last tail kernel: no copy command on any stream (see k_tail_finish)
   static const bool diag_no_tail = std::getenv("VOFOD_DIAG_NO_TAIL") != nullptr;  // (diagnostics: timing of the pipeline without the tail kernel - results are wrong)
@@ -574,21 +581,8 @@ int launch_device_tail(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, co
   return VOFOD_OK;
 }
 
-// Read-back of a batch nobody debugs whose tail runs on the host: the lite slots, on the copy stream when nobody waits in this call
-int read_back_lite(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t n, bool submitted)
-{
-  KLAUNCH(h, k_pack_lite, dim3(n), dim3(256), g, ws.d_hdrs, ws.d_table, ws.d_cand, ws.va, ws.d_lite);
-  if (submitted)
-  {
-    HIPCHK(hipEventRecord(ws.ev_packed, h->stream));
-    HIPCHK(hipStreamWaitEvent(ws.copy_stream, ws.ev_packed, 0));
-  }
-  HIPCHK(hipMemcpyAsync(ws.h_lite, ws.d_lite, sizeof(PackedLite) * n, hipMemcpyDeviceToHost, submitted ? ws.copy_stream : h->stream));
-  return VOFOD_OK;
-}
-
 // The launch half.  `call` is filled for the collect half of a synchronous call; a submitted batch leaves what its collect
-// half needs in the workspace (pending, job_n, job_g, job_tfs, job_scans, job_dp, dtail, lite, ev_done).
+// half needs in the workspace (pending, job_n, job_g, job_tfs, job_scans, job_dp, dtail, ev_done).
 int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
 {
   const vofod_static_params& sp = h->sp;
@@ -634,7 +628,6 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   rt.single_update = !no_update && n == 1 && !submitted;
   const bool dtail_on = !switch_off("VOFOD_DEVICE_TAIL");
   rt.dtail = dtail_on && !dbg && ((n >= 4 && no_update) || rt.single_update);
-  rt.lite = !rt.dtail && !switch_off("VOFOD_LITE") && !dbg && n >= 4 && no_update;
   if (submitted)
     VCHK(route_submitted(h, ws, n, rt));
   StreamScope chain_scope(h, rt.chain);
@@ -713,14 +706,11 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
 
   // ---- the tail on the device, or the read-back of what the host tail needs
   ws.dtail = rt.dtail;
-  ws.lite = rt.lite;
   call.tail_stream_used = h->stream;
   if (rt.dtail && rt.single_update && (call.flags & VOFOD_SCAN_AUTO_RAYCAST))
     VCHK(raycast_ahead_of_tail(h, ws, call));
   if (rt.dtail)
     VCHK(launch_device_tail(h, ws, lf, rt, call));
-  else if (rt.lite)
-    VCHK(read_back_lite(h, ws, g, n, submitted));
   else
     VCHK(read_back_full(h, ws, g, n));
   if (dbg)
@@ -732,7 +722,7 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   h2d_guard.armed = false;
   if (host_copies)
     HIPCHK(hipEventSynchronize(ws.ev_h2d));  // (the whole chain is enqueued by now: the device works while the host waits for the link)
-  HIPCHK(hipEventRecord(ws.ev_done, rt.dtail ? call.tail_stream_used : rt.lite ? ws.copy_stream : h->stream));
+  HIPCHK(hipEventRecord(ws.ev_done, rt.dtail ? call.tail_stream_used : h->stream));
   ws.pending = true;
   ws.job_n = n;
   ws.job_g = g;

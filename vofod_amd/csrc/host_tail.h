@@ -22,6 +22,12 @@
 namespace vt
 {
 
+// VoxelMap::coordToIdx (voxel_map.cpp:592-599) for one axis: the map cell of a coordinate.  Host and device run this very function.
+VT_HD inline int map_cell(float p, float off, float vs_inv)
+{
+  return static_cast<int>(floorf((p - off) * vs_inv));
+}
+
 // VoxelMap geometry (voxel_map.cpp:592-613) on the host, same float expressions as the kernels.
 struct Geom
 {
@@ -31,7 +37,7 @@ struct Geom
   void coordToIdx(const float p[3], int o[3]) const
   {
     for (int a = 0; a < 3; a++)
-      o[a] = static_cast<int>(std::floor((p[a] - off[a]) * vs_inv));
+      o[a] = map_cell(p[a], off[a], vs_inv);
   }
   void idxToCoord(const int i[3], float c[3]) const
   {
@@ -105,7 +111,7 @@ struct Boxes
 
 // [3P] pcl::MomentOfInertiaEstimation: mean, covariance/n^2, principal axes (major >= middle >= minor,
 // right-handed), AABB and OBB (centre = mean + R*shift).  Members in ascending index order; `get(i, p)` fetches the centre
-// of member i.  Host (classification tail, fallback) and device (k_tail_prep) run this very function.
+// of member i.  Host (classification tail, fallback) and device (k_tail_far, k_tail_prep) run this very function.
 template <class Get>
 VT_HD inline Boxes boxes_of_n(size_t n, Get get)
 {
@@ -209,13 +215,73 @@ VT_HD inline Boxes boxes_of_n(size_t n, Get get)
   return b;
 }
 
-inline Boxes boxes_of(const MemberSpan& m)
+// The parameters of classify_cluster's gates (vofod_nodelet.cpp:1648-1696), as the kernels take them.
+struct TailParams
 {
-  return boxes_of_n(m.size(), [&](size_t i, float p[3]) {
-    p[0] = m[i].p[0];
-    p[1] = m[i].p[1];
-    p[2] = m[i].p[2];
-  });
+  int32_t min_points;       // classification__min_points
+  double max_distance;      // classification__max_distance
+  double max_size;          // classification__max_size
+  double max_explore;       // classification__max_explore_distance
+  float voxel_size;
+  int32_t latches;          // background_pts_sufficient && sure_background_sufficient (:1694)
+};
+
+struct Gates
+{
+  float obb_center[3] = {0, 0, 0};
+  float obb_size = NAN;    // not computed: a gate in front of max_size failed
+  bool evaluated = false;  // the boxes were computed (the cluster has members)
+  bool passed = false;     // min_points, max_distance and max_size
+  bool explore = false;    // ... and the latches are set: the cluster reaches its flood fill; R and the box are valid
+  int R = 0;               // Manhattan radius of the flood fill in voxels (:1696)
+  int box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};  // getSubmapCopy(aabb, inflate 2) voxel_map.cpp:550-559, clamped to the map
+};
+
+// classify_cluster's front (vofod_nodelet.cpp:1648-1696): the boxes of a cluster of n members, the three gates in the
+// reference's order, and for a cluster that reaches its flood fill the explore job's radius and sub-map box.  `tf` is the sensor
+// pose (3 x 4: the position is tf[3], tf[7], tf[11]); off / vs_inv / size are the voxel map's geometry.  Host tail (prep_frame_tail) and
+// device tail (k_tail_far, k_tail_prep) run this very function: the results are compared bit for bit with the oracle, so the
+// float sums, their widening to double for the compare and the negated compares (a NaN passes) stay as they are.
+// (always_inline: the kernels' register budgets were set with this text written out in them - k_tail_far sits on 96 registers)
+template <class Get>
+VT_HD __attribute__((always_inline)) inline Gates classify_gates(uint32_t n, Get get, const float tf[12], const TailParams& tp, const float off[3], float vs_inv, const int size[3])
+{
+  Gates r;
+  if (n == 0)
+    return r;
+  const Boxes bx = boxes_of_n(n, get);
+  r.evaluated = true;
+  for (int q = 0; q < 3; q++)
+    r.obb_center[q] = bx.obb_center[q];
+  bool pass = static_cast<int>(n) >= tp.min_points;
+  if (pass)
+  {
+    const float d[3] = {tf[3] - bx.obb_center[0], tf[7] - bx.obb_center[1], tf[11] - bx.obb_center[2]};
+    const double dist = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    pass = !(dist > tp.max_distance);
+  }
+  float obb_size = 0.0f;
+  if (pass)
+  {
+    const float d[3] = {bx.obb_max[0] - bx.obb_min[0], bx.obb_max[1] - bx.obb_min[1], bx.obb_max[2] - bx.obb_min[2]};
+    obb_size = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    r.obb_size = obb_size;
+    pass = !(obb_size > tp.max_size);
+  }
+  r.passed = pass;
+  if (pass && tp.latches)  // without the latches the cluster stays "unknown" (:1694, :1719-1722): no detection
+  {
+    r.explore = true;
+    r.R = static_cast<int>((obb_size + tp.max_explore) / tp.voxel_size);  // :1696
+    for (int q = 0; q < 3; q++)
+    {
+      const int mn = map_cell(bx.aabb_min[q], off[q], vs_inv), mx = map_cell(bx.aabb_max[q], off[q], vs_inv);
+      const int lo = mn - 2 > 0 ? mn - 2 : 0, hi = mx + 2 > 0 ? mx + 2 : 0;
+      r.box_lo[q] = lo < size[q] - 1 ? lo : size[q] - 1;
+      r.box_hi[q] = hi < size[q] - 1 ? hi : size[q] - 1;
+    }
+  }
+  return r;
 }
 
 // VoxelMap::exploreToGround (voxel_map.cpp:402-488) as a flood fill over a read-back box.  The

@@ -1,18 +1,22 @@
-// Device-side classification tail of a read-only batch (gfx950): classify_cluster's boxes and gates
-// (vofod_nodelet.cpp:1648-1690) and the selection of the detections (extractDetections :834-879), so that a batch is one
-// stream-ordered chain - k_frame_lds -> k_tail_prep -> k_explore -> k_tail_finish - and the host only reads the few
-// detection records back.  Round 1 did this part on the host between two device round trips (the candidate tables came
-// back over PCIe, the boxes were computed by host threads, the explore jobs went up again): with the device chain down to
-// 0.65 ms per 256 frames the host tail (0.4-0.7 ms) had become the bottleneck.
-//   k_tail_prep    one workgroup per frame: candidate clusters (far, small) from the cluster table, their members sorted by
-//                  (cluster, voxel rank) with a bitonic sort in LDS, canonical cluster order (size descending, smallest member
-//                  ascending: SURVEY H3), then one lane per cluster: pcl::MomentOfInertiaEstimation boxes (vt::boxes_of_n:
-//                  the very function of the host tail), the three gates, the explore job (Manhattan radius, sub-map box,
-//                  members' map voxels) for clusters that reach the flood fill;
-//   k_explore      (kernels_classify.h) flood fills + uncertainty sums, one wave per frame, jobs in the reference's order;
-//   k_tail_finish  one wave per frame: the clusters found floating become raw detection records in cluster order.
-// A frame beyond a capacity here (members, clusters, jobs, detections, Manhattan radius) sets a flag: the host then runs
-// its own tail for that batch (the round-1 path, still used for debug output).
+// Device-side classification tail (gfx950): classify_cluster's boxes and gates (vofod_nodelet.cpp:1648-1696), the flood fills
+// and the selection of the detections (extractDetections :834-879), so that the host only reads the few detection records
+// back.  It takes every call nobody debugs that is a read-only batch of four frames or more, or one map-updating scan.
+// Two chains, chosen per batch by launch_device_tail:
+//   k_tail_far                               close-first frames (k_frame_lds_far, or k_far_final for a single scan): the
+//                                            candidate clusters head the cluster table in canonical order and their members
+//                                            follow cluster by cluster, so one wave per frame does the whole tail - boxes
+//                                            and gates, the frame's flood fills (vc::explore_frame), the records;
+//   k_tail_prep -> k_explore -> k_tail_finish  frames that went through the full clustering (no dilated map image, a cold map,
+//                                            VOFOD_CLOSE_FIRST=0): k_tail_prep finds the candidates in the table and sorts their
+//                                            members (bitonic sort in LDS) into the canonical order (size descending, smallest
+//                                            member ascending: SURVEY H3), then boxes, gates and explore jobs, one lane per cluster;
+//                                            k_explore (kernels_classify.h) runs the flood fills, k_tail_finish writes the records.
+// What the two share is stated once: boxes, gates and the explore job's radius and box are vt::classify_gates (host_tail.h: the
+// very function of the host tail), a lane's place among the wave's is rank_in_wave, the records and the slot's header are
+// write_records / put_header.
+// A frame beyond a capacity here (members, clusters, detections, Manhattan radius, flood-fill work list) sets a flag in its
+// record slot: the host tail (frames_collect.h) then redoes the batch from the full tables.  The host tail also serves what
+// never comes here: calls with debug output, batches of fewer than four frames, VOFOD_DEVICE_TAIL=0.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,15 +44,7 @@ constexpr int TP_MAXM = TAIL_MAXM;  // candidate members per frame
 constexpr int TP_MAXC = TAIL_MAXC;  // candidate clusters per frame (one lane each)
 constexpr int TP_MAXD = 16;    // detections per frame read back
 
-struct TailParams
-{
-  int32_t min_points;       // classification__min_points
-  double max_distance;      // classification__max_distance
-  double max_size;          // classification__max_size
-  double max_explore;       // classification__max_explore_distance
-  float voxel_size;
-  int32_t latches;          // background_pts_sufficient && sure_background_sufficient (:1694)
-};
+using vt::TailParams;
 
 struct TailCluster
 {
@@ -75,6 +71,98 @@ struct FrameDets
 };
 
 enum : uint32_t { TAIL_FB_MEMBERS = 1u, TAIL_FB_CLUSTERS = 2u, TAIL_FB_RADIUS = 4u, TAIL_FB_DETS = 8u, TAIL_FB_EXPLORE = 16u };
+
+// a lane's place among the lanes of the wave that raise `flag` (cluster order = lane order), and how many do
+__device__ __forceinline__ uint32_t rank_in_wave(bool flag, int lane, uint32_t& count)
+{
+  const unsigned long long m = __ballot(flag);
+  count = __popcll(m);
+  return __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// the header of a frame's record slot, twice: to the workspace (device memory, read by the capacity fall-back) and, where the
+// caller gave one, to the pinned host slot (one lane calls this)
+__device__ __forceinline__ void put_header(FrameDets& out, FrameDets* hout, uint32_t f, uint32_t n, uint32_t fb, int32_t status, uint32_t n_jobs)
+{
+  out.n = n;
+  out.fallback = fb;
+  out.status = status;
+  out.n_jobs = n_jobs;
+  if (hout)
+  {
+    hout[f].n = n;
+    hout[f].fallback = fb;
+    hout[f].status = status;
+    hout[f].n_jobs = n_jobs;
+  }
+}
+
+// The floating clusters (extractDetections :843-846) of a frame as raw detection records in cluster order, lane c = cluster c
+// of the canonical order.  Returns what the slot's header says of them: their number and the capacities they exceeded (the
+// caller's lane 0 passes both on to put_header).
+__device__ __forceinline__ void write_records(const TailCluster& tc, const vc::ExploreResult* __restrict__ results, int lane, FrameDets& out, FrameDets* hout, uint32_t f, uint32_t& n, uint32_t& fb)
+{
+  bool det = false, bad = false;
+  double conf = 0.0;
+  if (tc.job >= 0)
+  {
+    const vc::ExploreResult r = results[tc.job];
+    det = r.floating != 0u;
+    bad = r.overflow != 0u;
+    conf = r.conf_sum;
+  }
+  const uint32_t pos = rank_in_wave(det, lane, n);
+  const unsigned long long bm = __ballot(bad);
+  if (det && pos < TP_MAXD)
+  {
+    DetRaw d;
+    d.root = tc.root;
+    d.n_points = tc.n_members;
+    for (int q = 0; q < 3; q++)
+      d.center[q] = tc.obb_center[q];
+    d.pad = 0;
+    d.conf_sum = conf;
+    out.d[pos] = d;
+    if (hout)
+      hout[f].d[pos] = d;
+  }
+  fb = (n > TP_MAXD ? TAIL_FB_DETS : 0u) | (bm ? TAIL_FB_EXPLORE : 0u);
+}
+
+// One lane's cluster through vt::classify_gates; a cluster that reaches its flood fill fills in its explore job (all but the
+// result slot) and stores its members' map voxels.  `get(i, p)` fetches the centre of the cluster's member i, m_begin is its
+// first member's place among the frame's candidate members.
+template <class Get>
+__device__ __forceinline__ bool gate_cluster(uint32_t f, uint32_t m_begin, uint32_t m_count, Get get, const float* tf, const MapGeom& mg, const TailParams& tp, int* __restrict__ members_out, TailCluster& tc,
+                                             vc::ExploreJob& job, uint32_t& fallback)
+{
+  const int s3[3] = {mg.sx, mg.sy, mg.sz};
+  const vt::Gates gt = vt::classify_gates(m_count, get, tf, tp, mg.off, mg.vs_inv, s3);
+  for (int q = 0; q < 3; q++)
+    tc.obb_center[q] = gt.obb_center[q];
+  if (!gt.explore)
+    return false;
+  job.frame = f;
+  job.n_members = m_count;
+  job.member_off = f * TP_MAXM + m_begin;
+  job.R = gt.R;
+  if (job.R > vc::EX_MAX_R || job.R < 0)
+    fallback |= TAIL_FB_RADIUS;
+  for (int q = 0; q < 3; q++)
+  {
+    job.box_lo[q] = gt.box_lo[q];
+    job.box_hi[q] = gt.box_hi[q];
+  }
+  for (uint32_t i = 0; i < m_count; i++)
+  {
+    float p[3];
+    get(i, p);
+    int* o = members_out + 3 * static_cast<size_t>(job.member_off + i);
+    for (int q = 0; q < 3; q++)
+      o[q] = vt::map_cell(p[q], mg.off[q], mg.vs_inv);
+  }
+  return true;
+}
 
 __global__ __launch_bounds__(TP_THREADS) void k_tail_prep(const GridParams g, const FrameHdr* __restrict__ hdrs, const FrameArgs* __restrict__ args, const ClusterRec* __restrict__ table_all,
                                                          const CandMember* __restrict__ cand_all, VoxelArrays va_all, const MapGeom mg, const TailParams tp, vc::ExploreJob* __restrict__ jobs,
@@ -203,82 +291,30 @@ __global__ __launch_bounds__(TP_THREADS) void k_tail_prep(const GridParams g, co
       p[1] = q.y;
       p[2] = q.z;
     };
-    // classify_cluster :1648-1690: boxes and gates
-    bool pass = m_count > 0 && static_cast<int>(m_count) >= tp.min_points;
-    if (m_count > 0)
-    {
-      const vt::Boxes bx = vt::boxes_of_n(m_count, get);
-      for (int q = 0; q < 3; q++)
-        tc.obb_center[q] = bx.obb_center[q];
-      if (pass)
-      {
-        const float d[3] = {a.tf[3] - bx.obb_center[0], a.tf[7] - bx.obb_center[1], a.tf[11] - bx.obb_center[2]};
-        const double dist = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        pass = !(dist > tp.max_distance);
-      }
-      float obb_size = 0.0f;
-      if (pass)
-      {
-        const float d[3] = {bx.obb_max[0] - bx.obb_min[0], bx.obb_max[1] - bx.obb_min[1], bx.obb_max[2] - bx.obb_min[2]};
-        obb_size = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        pass = !(obb_size > tp.max_size);
-      }
-      if (pass && tp.latches)  // without the latches the cluster stays "unknown" (:1694, :1719-1722): no detection
-      {
-        wants_job = true;
-        job.frame = f;
-        job.n_members = m_count;
-        job.member_off = f * TP_MAXM + m_begin;
-        job.R = static_cast<int>((obb_size + tp.max_explore) / tp.voxel_size);  // :1696
-        if (job.R > vc::EX_MAX_R || job.R < 0)
-          fallback |= TAIL_FB_RADIUS;
-        const int s3[3] = {mg.sx, mg.sy, mg.sz};
-        for (int q = 0; q < 3; q++)  // getSubmapCopy(aabb, inflate 2) voxel_map.cpp:550-559
-        {
-          const int mn = static_cast<int>(floorf((bx.aabb_min[q] - mg.off[q]) * mg.vs_inv)), mx = static_cast<int>(floorf((bx.aabb_max[q] - mg.off[q]) * mg.vs_inv));
-          job.box_lo[q] = min(max(mn - 2, 0), s3[q] - 1);
-          job.box_hi[q] = min(max(mx + 2, 0), s3[q] - 1);
-        }
-        for (uint32_t i = 0; i < m_count; i++)
-        {
-          float p[3];
-          get(i, p);
-          int* o = members_out + 3 * static_cast<size_t>(job.member_off + i);
-          for (int q = 0; q < 3; q++)
-            o[q] = static_cast<int>(floorf((p[q] - mg.off[q]) * mg.vs_inv));
-        }
-      }
-    }
+    wants_job = gate_cluster(f, m_begin, m_count, get, a.tf, mg, tp, members_out, tc, job, fallback);
   }
   // jobs in cluster order
-  const unsigned long long jm = __ballot(wants_job);
-  const uint32_t n_jobs = __popcll(jm);
+  uint32_t n_jobs;
+  const uint32_t slot = f * TP_MAXC + rank_in_wave(wants_job, lane, n_jobs);
   if (wants_job)
   {
-    const uint32_t slot = f * TP_MAXC + __popcll(jm & ((1ull << lane) - 1ull));
     job.result_slot = slot;
     jobs[slot] = job;
     tc.job = static_cast<int32_t>(slot);
   }
-  const unsigned long long fb_any = __ballot(fallback != 0u);
   uint32_t fb_all = fallback;
 #pragma unroll
   for (int s = 32; s > 0; s >>= 1)
     fb_all |= __shfl_xor(fb_all, s);
-  (void)fb_any;
   if (live)
     tailc[f * TP_MAXC + lane] = tc;
   if (lane == 0)
   {
-    out.n = 0;
-    out.fallback = fb_all;
-    out.status = h.status;
-    out.n_jobs = fb_all ? 0u : n_jobs;
+    put_header(out, nullptr, f, 0u, fb_all, h.status, fb_all ? 0u : n_jobs);
     if (!fb_all)
       job_end[f] = f * TP_MAXC + n_jobs;
-    // clusters past nc are marked empty for k_tail_finish
   }
-  if (!live && lane < TP_MAXC)
+  if (!live && lane < TP_MAXC)  // clusters past nc are marked empty for k_tail_finish
   {
     TailCluster e{};
     e.job = -1;
@@ -388,60 +424,14 @@ __global__ TAIL_OCC_ATTR __launch_bounds__(64 * TAIL_WPB) void k_tail_far(const 
       p[1] = q.y;
       p[2] = q.z;
     };
-    // classify_cluster :1648-1690: boxes and gates
-    bool pass = m_count > 0 && static_cast<int>(m_count) >= tp.min_points;
-    if (m_count > 0)
-    {
-      const vt::Boxes bx = vt::boxes_of_n(m_count, get);
-      for (int q = 0; q < 3; q++)
-        tc.obb_center[q] = bx.obb_center[q];
-      if (pass)
-      {
-        const float d[3] = {a.tf[3] - bx.obb_center[0], a.tf[7] - bx.obb_center[1], a.tf[11] - bx.obb_center[2]};
-        const double dist = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        pass = !(dist > tp.max_distance);
-      }
-      float obb_size = 0.0f;
-      if (pass)
-      {
-        const float d[3] = {bx.obb_max[0] - bx.obb_min[0], bx.obb_max[1] - bx.obb_min[1], bx.obb_max[2] - bx.obb_min[2]};
-        obb_size = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        pass = !(obb_size > tp.max_size);
-      }
-      if (pass && tp.latches)  // without the latches the cluster stays "unknown" (:1694, :1719-1722): no detection
-      {
-        wants_job = true;
-        job.frame = f;
-        job.n_members = m_count;
-        job.member_off = f * TP_MAXM + m_begin;
-        job.R = static_cast<int>((obb_size + tp.max_explore) / tp.voxel_size);  // :1696
-        if (job.R > vc::EX_MAX_R || job.R < 0)
-          fallback |= TAIL_FB_RADIUS;
-        const int s3[3] = {mg.sx, mg.sy, mg.sz};
-        for (int q = 0; q < 3; q++)  // getSubmapCopy(aabb, inflate 2) voxel_map.cpp:550-559
-        {
-          const int mn = static_cast<int>(floorf((bx.aabb_min[q] - mg.off[q]) * mg.vs_inv)), mx = static_cast<int>(floorf((bx.aabb_max[q] - mg.off[q]) * mg.vs_inv));
-          job.box_lo[q] = min(max(mn - 2, 0), s3[q] - 1);
-          job.box_hi[q] = min(max(mx + 2, 0), s3[q] - 1);
-        }
-        for (uint32_t i = 0; i < m_count; i++)
-        {
-          float p[3];
-          get(i, p);
-          int* o = members_out + 3 * static_cast<size_t>(job.member_off + i);
-          for (int q = 0; q < 3; q++)
-            o[q] = static_cast<int>(floorf((p[q] - mg.off[q]) * mg.vs_inv));
-        }
-      }
-    }
+    wants_job = gate_cluster(f, m_begin, m_count, get, a.tf, mg, tp, members_out, tc, job, fallback);
   }
   // jobs in cluster order
-  const unsigned long long jm = __ballot(wants_job);
-  uint32_t n_jobs = __popcll(jm);
+  uint32_t n_jobs;
   const uint32_t jb = f * TP_MAXC;
+  const uint32_t slot = jb + rank_in_wave(wants_job, lane, n_jobs);
   if (wants_job)
   {
-    const uint32_t slot = jb + __popcll(jm & ((1ull << lane) - 1ull));
     job.result_slot = slot;
     jobs[slot] = job;
     tc.job = static_cast<int32_t>(slot);
@@ -462,19 +452,7 @@ __global__ TAIL_OCC_ATTR __launch_bounds__(64 * TAIL_WPB) void k_tail_far(const 
   if (fb_all)
   {
     if (lane == 0)
-    {
-      out.n = 0;
-      out.fallback = fb_all;
-      out.status = h.status;
-      out.n_jobs = 0;
-      if (hout)
-      {
-        hout[f].n = 0;
-        hout[f].fallback = fb_all;
-        hout[f].status = h.status;
-        hout[f].n_jobs = 0;
-      }
-    }
+      put_header(out, hout, f, 0u, fb_all, h.status, 0u);
     return;
   }
   __threadfence_block();
@@ -486,53 +464,11 @@ __global__ TAIL_OCC_ATTR __launch_bounds__(64 * TAIL_WPB) void k_tail_far(const 
   vc::wave_sync();
   if (prof)
     tp2 = wall_clock64();
-  // the floating clusters (extractDetections :843-846) in cluster order, as k_tail_finish
-  bool det = false, bad = false;
-  double conf = 0.0;
-  if (tc.job >= 0)
-  {
-    const vc::ExploreResult r = results[tc.job];
-    det = r.floating != 0u;
-    bad = r.overflow != 0u;
-    conf = r.conf_sum;
-  }
-  const unsigned long long dm = __ballot(det), bm = __ballot(bad);
-  const uint32_t n = __popcll(dm);
-  if (det)
-  {
-    const uint32_t pos = __popcll(dm & ((1ull << lane) - 1ull));
-    if (pos < TP_MAXD)
-    {
-      DetRaw d;
-      d.root = tc.root;
-      d.n_points = tc.n_members;
-      for (int q = 0; q < 3; q++)
-        d.center[q] = tc.obb_center[q];
-      d.pad = 0;
-      d.conf_sum = conf;
-      out.d[pos] = d;
-      if (hout)
-        hout[f].d[pos] = d;
-    }
-  }
+  uint32_t n, fb;
+  write_records(tc, results, lane, out, hout, f, n, fb);
   if (lane == 0)
   {
-    uint32_t fb = 0;
-    if (n > TP_MAXD)
-      fb |= TAIL_FB_DETS;
-    if (bm)
-      fb |= TAIL_FB_EXPLORE;
-    out.n = n;
-    out.fallback = fb;
-    out.status = h.status;
-    out.n_jobs = n_jobs;
-    if (hout)
-    {
-      hout[f].n = n;
-      hout[f].fallback = fb;
-      hout[f].status = h.status;
-      hout[f].n_jobs = n_jobs;
-    }
+    put_header(out, hout, f, n, fb, h.status, n_jobs);
     if (prof)
     {
       const unsigned long long te = wall_clock64();
@@ -556,61 +492,15 @@ __global__ __launch_bounds__(64) void k_tail_finish(const TailCluster* __restric
   const uint32_t fb_in = out.fallback;
   if (fb_in)
   {
-    if (hout && lane == 0)
-    {
-      hout[f].n = 0;
-      hout[f].fallback = fb_in;
-      hout[f].status = out.status;
-      hout[f].n_jobs = out.n_jobs;
-    }
+    if (lane == 0)
+      put_header(out, hout, f, 0u, fb_in, out.status, out.n_jobs);
     return;
   }
   const TailCluster tc = tailc[f * TP_MAXC + lane];
-  bool det = false, bad = false;
-  double conf = 0.0;
-  if (tc.job >= 0)
-  {
-    const vc::ExploreResult r = results[tc.job];
-    det = r.floating != 0u;
-    bad = r.overflow != 0u;
-    conf = r.conf_sum;
-  }
-  const unsigned long long dm = __ballot(det), bm = __ballot(bad);
-  const uint32_t n = __popcll(dm);
-  if (det)
-  {
-    const uint32_t pos = __popcll(dm & ((1ull << lane) - 1ull));
-    if (pos < TP_MAXD)
-    {
-      DetRaw d;
-      d.root = tc.root;
-      d.n_points = tc.n_members;
-      for (int q = 0; q < 3; q++)
-        d.center[q] = tc.obb_center[q];
-      d.pad = 0;
-      d.conf_sum = conf;
-      out.d[pos] = d;
-      if (hout)
-        hout[f].d[pos] = d;
-    }
-  }
+  uint32_t n, fb;
+  write_records(tc, results, lane, out, hout, f, n, fb);
   if (lane == 0)
-  {
-    uint32_t fb = 0;
-    if (n > TP_MAXD)
-      fb |= TAIL_FB_DETS;
-    if (bm)
-      fb |= TAIL_FB_EXPLORE;
-    out.n = n;
-    out.fallback = fb;
-    if (hout)
-    {
-      hout[f].n = n;
-      hout[f].fallback = fb;
-      hout[f].status = out.status;
-      hout[f].n_jobs = out.n_jobs;
-    }
-  }
+    put_header(out, hout, f, n, fb, out.status, out.n_jobs);
 }
 
 }  // namespace vtd

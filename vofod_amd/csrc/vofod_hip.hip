@@ -61,6 +61,21 @@ struct PackedFrame
 };
 static_assert(sizeof(FrameHdr) <= 128, "FrameHdr grew past its slot");
 
+// a candidate member with its voxel's centre and point count, as the host tail reads it
+__device__ __forceinline__ CandMemberX gather_member(const GridParams& g, uint32_t f, uint32_t t, const CandMember* cand_all, const VoxelArrays& va_all)
+{
+  const CandMember cm = cand_all[static_cast<size_t>(f) * g.vox_cap + t];
+  const float4 p = va_all.pts[static_cast<size_t>(f) * g.vox_cap + cm.v];
+  CandMemberX x;
+  x.root = cm.root;
+  x.v = cm.v;
+  x.x = p.x;
+  x.y = p.y;
+  x.z = p.z;
+  x.count = __float_as_uint(p.w);
+  return x;
+}
+
 __global__ void k_pack(const GridParams g, const FrameHdr* hdrs, const ClusterRec* table_all, const CandMember* cand_all, VoxelArrays va_all, PackedFrame* out)
 {
   uint32_t FRAME, BX, GX;
@@ -76,94 +91,14 @@ __global__ void k_pack(const GridParams g, const FrameHdr* hdrs, const ClusterRe
   if (t < min(h.C, SPEC_C))
     o.table[t] = table_all[static_cast<size_t>(f) * g.vox_cap + t];
   if (t < min(h.n_cand, SPEC_M))
-  {
-    const CandMember cm = cand_all[static_cast<size_t>(f) * g.vox_cap + t];
-    const float4 p = va_all.pts[static_cast<size_t>(f) * g.vox_cap + cm.v];
-    CandMemberX x;
-    x.root = cm.root;
-    x.v = cm.v;
-    x.x = p.x;
-    x.y = p.y;
-    x.z = p.z;
-    x.count = __float_as_uint(p.w);
-    o.members[t] = x;
-  }
-}
-
-// Read-back of a batch nobody debugs: only what the classification tail consumes - the header, the candidate clusters'
-// records (far, small enough: the others can neither be classified nor detected) and the candidate members.  6.9 KB per
-// frame instead of the 26 KB speculative slot, copied on a stream of its own so that the next batch's chain does not wait for PCIe.
-constexpr uint32_t LITE_C = 16;
-constexpr uint32_t LITE_M = 256;
-struct PackedLite
-{
-  FrameHdr hdr;
-  uint32_t pad[32 - sizeof(FrameHdr) / 4];
-  uint32_t n_recs, n_members, pad2[2];  // counts found on the device (beyond LITE_C / LITE_M: the host fetches the frame's full lists)
-  ClusterRec recs[LITE_C];
-  CandMemberX members[LITE_M];
-};
-
-__global__ __launch_bounds__(256) void k_pack_lite(const GridParams g, const FrameHdr* hdrs, const ClusterRec* table_all, const CandMember* cand_all, VoxelArrays va_all, PackedLite* out)
-{
-  __shared__ uint32_t s_cnt;
-  const uint32_t f = blockIdx.x;
-  const FrameHdr h = hdrs[f];
-  PackedLite& o = out[f];
-  if (threadIdx.x == 0)
-  {
-    o.hdr = h;
-    s_cnt = 0;
-  }
-  __syncthreads();
-  const ClusterRec* table = table_all + static_cast<size_t>(f) * g.vox_cap;
-  for (uint32_t c = threadIdx.x; c < h.C; c += blockDim.x)
-  {
-    const ClusterRec r = table[c];
-    if (r.cand && !r.close)
-    {
-      const uint32_t pos = atomicAdd(&s_cnt, 1u);
-      if (pos < LITE_C)
-        o.recs[pos] = r;
-    }
-  }
-  static_assert(LITE_M <= 256, "one member per thread");
-  if (threadIdx.x < min(h.n_cand, LITE_M))
-  {
-    const CandMember cm = cand_all[static_cast<size_t>(f) * g.vox_cap + threadIdx.x];
-    const float4 p = va_all.pts[static_cast<size_t>(f) * g.vox_cap + cm.v];
-    CandMemberX x;
-    x.root = cm.root;
-    x.v = cm.v;
-    x.x = p.x;
-    x.y = p.y;
-    x.z = p.z;
-    x.count = __float_as_uint(p.w);
-    o.members[threadIdx.x] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    o.n_recs = s_cnt;
-    o.n_members = h.n_cand;
-  }
+    o.members[t] = gather_member(g, f, t, cand_all, va_all);
 }
 
 __global__ void k_gather_members(const GridParams g, uint32_t frame, uint32_t n, const CandMember* cand_all, VoxelArrays va_all, CandMemberX* out)
 {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n)
-    return;
-  const CandMember cm = cand_all[static_cast<size_t>(frame) * g.vox_cap + t];
-  const float4 p = va_all.pts[static_cast<size_t>(frame) * g.vox_cap + cm.v];
-  CandMemberX x;
-  x.root = cm.root;
-  x.v = cm.v;
-  x.x = p.x;
-  x.y = p.y;
-  x.z = p.z;
-  x.count = __float_as_uint(p.w);
-  out[t] = x;
+  if (t < n)
+    out[t] = gather_member(g, frame, t, cand_all, va_all);
 }
 
 using clk = std::chrono::steady_clock;
@@ -347,9 +282,6 @@ struct Workspace
   DevBuf<float> d_poses;
   DevBuf<PackedFrame> d_packed;
   PinBuf<PackedFrame> h_packed;
-  DevBuf<PackedLite> d_lite;
-  PinBuf<PackedLite> h_lite;
-  bool lite = false;  // the batch in this workspace was read back through the lite slots (no debug output asked for)
   bool mapbits_patched = false;  // k_finalize_far kept the map's occupancy image and counters up to date with this scan's update
   bool prof_deferred = false;  // VOFOD_LDS_PROF=2: the frame kernel's stamps of this batch are printed when it is collected
   uint32_t prof_slot0 = 0;
@@ -411,7 +343,6 @@ struct Workspace
   DevEvent ev_packed;   // the read-back slots are complete on the chain's stream
   DevEvent ev_key;      // staged pipeline: the batch's streaming kernels (brick codes) are through
   DevEvent ev_h2d;      // the host-resident columns of a submitted batch have crossed the link (vofod_batch_submit returns behind it)
-  DevStream copy_stream;  // device-to-host copy of the slots: the chain's stream goes on with the next batch meanwhile
 
   // Grow to at least these capacities.  What was there is released first (two 6.4 GB workspaces must never coexist); a failure
   // leaves an empty workspace.
@@ -473,7 +404,6 @@ private:
     HIP_TRY(d_rjobs.alloc(F_));
     HIP_TRY(h_rjobs.alloc(F_));
     HIP_TRY(d_packed.alloc(F_));
-    HIP_TRY(d_lite.alloc(F_));
     HIP_TRY(d_tailc.alloc(vtd::TP_MAXC * static_cast<size_t>(F_)));
     HIP_TRY(d_dets.alloc(F_));
     HIP_TRY(d_job_be.alloc(2 * static_cast<size_t>(F_)));
@@ -485,7 +415,6 @@ private:
     HIP_TRY(alloc_view(fs_bbsave, fs.bbsave, FR_BB64 * static_cast<size_t>(F_)));
     HIP_TRY(alloc_view(fs_frag, fs.frag, static_cast<size_t>(F_) * std::max<uint32_t>(pt_cap_, 1)));
     HIP_TRY(h_packed.alloc(F_));
-    HIP_TRY(h_lite.alloc(F_));
     HIP_TRY(h_dets.alloc(F_, hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(h_dets, 0, sizeof(vtd::FrameDets) * F_);
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_dets_dev), h_dets, 0));
@@ -494,7 +423,6 @@ private:
     HIP_TRY(ev_packed.create(hipEventCreateWithFlags, hipEventDisableTiming));
     HIP_TRY(ev_h2d.create(hipEventCreateWithFlags, hipEventDisableTiming));
     HIP_TRY(ev_key.create(hipEventCreateWithFlags, hipEventDisableTiming));
-    HIP_TRY(copy_stream.create(hipStreamCreateWithFlags, hipStreamNonBlocking));
     // the memsets above run on the null stream, the kernels on non-blocking streams: wait for the fills to land
     HIP_TRY(hipDeviceSynchronize());
     F = F_;
@@ -523,9 +451,7 @@ struct HostCluster
 {
   ClusterRec rec;
   int cclass = VOFOD_CLASS_NONE;
-  bool evaluated = false;
-  vt::Boxes boxes{};
-  float obb_size = NAN;
+  vt::Gates gates;  // boxes and gates of a candidate cluster (not evaluated: obb_size NaN)
 };
 
 struct vofod_handle
@@ -628,7 +554,6 @@ struct vofod_handle
   DevBuf<CloseRow> d_crows;
   DevBuf<float> d_boxstage;
   DevBuf<uint64_t> d_idxstage;
-  std::vector<CandMemberX> h_members_big;
 
   bool background_pts_sufficient = false, sure_background_sufficient = false;
   int detection_its = 0;
@@ -1132,6 +1057,22 @@ RefLattice fill_ref_lattice(const GridParams& g)
   return rl;
 }
 
+// K3-K6 of the general voxeliser through the global occupancy bitmaps: bitmap (cleared first where `clear`) -> ranks -> weighted cloud
+int launch_bitmap_chain(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t n, uint32_t max_pts, bool clear, const BrickParams& bpv, int emit_bricks, uint32_t lean_bit, bool want_ptrank)
+{
+  const uint32_t gx = std::max(1u, std::min((max_pts + 255u) / 256u, 1024u));
+  if (clear)
+    HIPCHK(hipMemsetAsync(ws.d_bitmaps, 0, sizeof(unsigned long long) * ws.F * (static_cast<size_t>(ws.words_cap) + 2), h->stream));
+  ws.bitmap_clean = false;  // set again by whoever runs the clearing pass
+  KLAUNCH(h, k_setbits, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps);
+  KLAUNCH(h, k_scan_a, fgrid(g, ws.nblk_cap), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap);
+  KLAUNCH(h, k_scan_b, dim3(n), dim3(1024), g, ws.d_hdrs, ws.d_blocksums, ws.nblk_cap);
+  KLAUNCH(h, k_emit, fgrid(g, ws.nblk_cap * emit_split(n)), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap, ws.d_wprefix, ws.va, bpv, ws.ba, emit_bricks, lean_bit, emit_split(n));
+  KLAUNCH(h, k_count, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va, want_ptrank ? ws.d_ptrank : nullptr, ws.pt_cap);
+  HIPCHK(hipGetLastError());
+  return VOFOD_OK;
+}
+
 // kernel chain K1-K6 over frames [0,n): bbox -> lattice -> occupancy bitmap -> ranks -> weighted cloud
 int launch_voxelize(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams& g, uint32_t n, uint32_t max_pts, bool want_ptrank, bool two_phase, const BrickParams* bricks = nullptr,
                     bool lean_hint = false)
@@ -1145,7 +1086,6 @@ int launch_voxelize(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams&
   // lean emission: the LDS clustering kernel will follow and initialises the per-root slots itself (see plan_lds_ccl)
   lf.lean_emit = lean_hint && !bricks && !two_phase;
   HIPCHK(hipMemcpyAsync(ws.d_args, ws.h_args.data(), sizeof(FrameArgs) * n, hipMemcpyHostToDevice, h->stream));
-  const uint32_t gx = std::max(1u, std::min((max_pts + 255u) / 256u, 1024u));
   const uint32_t gb = std::max(1u, std::min((max_pts + 2047u) / 2048u, 1024u));  // 8 points per thread: few header atomics
   // Batches whose clustering will run inside LDS (plan_lds_ccl): the brick-first frame kernel (kernels_frame.h) reads the input
   // itself (round 5; rounds 2-4 had a streaming kernel in front, k_key1, which is gone), builds the voxel records and clusters them on the same LDS
@@ -1160,7 +1100,7 @@ int launch_voxelize(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams&
   if (!frame_plan)
     lf.lean_emit = false;  // the general emission kernels initialise every per-voxel slot; the global clustering kernels follow
   const uint32_t lean_bit = lf.lean_emit ? 0x80000000u : 0u;
-  KLAUNCH(h, k_init_hdr, dim3(n), dim3(64), ws.d_hdrs, static_cast<uint32_t*>(nullptr));
+  KLAUNCH(h, k_init_hdr, dim3(n), dim3(64), ws.d_hdrs);
   if (frame_plan)
   {
     bool packed = true;
@@ -1256,34 +1196,16 @@ int launch_voxelize(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams&
     HIPCHK(hipGetLastError());
     return VOFOD_OK;
   }
-  if (!ws.bitmap_clean)
-    HIPCHK(hipMemsetAsync(ws.d_bitmaps, 0, sizeof(unsigned long long) * ws.F * (static_cast<size_t>(ws.words_cap) + 2), h->stream));
-  ws.bitmap_clean = false;  // set again by whoever runs the clearing pass
-  KLAUNCH(h, k_setbits, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps);
-  KLAUNCH(h, k_scan_a, fgrid(g, ws.nblk_cap), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap);
-  KLAUNCH(h, k_scan_b, dim3(n), dim3(1024), g, ws.d_hdrs, ws.d_blocksums, ws.nblk_cap);
-  KLAUNCH(h, k_emit, fgrid(g, ws.nblk_cap * emit_split(n)), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap, ws.d_wprefix, ws.va, bpv, ws.ba, bricks ? 1 : 0, lean_bit, emit_split(n));
-  KLAUNCH(h, k_count, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va, want_ptrank ? ws.d_ptrank : nullptr, ws.pt_cap);
-  HIPCHK(hipGetLastError());
-  return VOFOD_OK;
+  return launch_bitmap_chain(h, ws, g, n, max_pts, !ws.bitmap_clean, bpv, bricks ? 1 : 0, lean_bit, want_ptrank);
 }
 
+// the second phase of a two-phase voxelisation (the caller has inspected the lattice k_bbox / k_grid found)
 int launch_voxelize_rest(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridParams& g, uint32_t n, uint32_t max_pts, bool want_ptrank)
 {
   BrickParams bpv{};
   bpv.bricks_cap = ws.bricks_cap;
-  const BrickParams* bricks = nullptr;
   lf.bricks_preset = false;  // (two-phase voxelisation never registers bricks in k_emit)
-  const uint32_t gx = std::max(1u, std::min((max_pts + 255u) / 256u, 1024u));
-  HIPCHK(hipMemsetAsync(ws.d_bitmaps, 0, sizeof(unsigned long long) * ws.F * (static_cast<size_t>(ws.words_cap) + 2), h->stream));
-  ws.bitmap_clean = false;
-  KLAUNCH(h, k_setbits, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps);
-  KLAUNCH(h, k_scan_a, fgrid(g, ws.nblk_cap), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap);
-  KLAUNCH(h, k_scan_b, dim3(n), dim3(1024), g, ws.d_hdrs, ws.d_blocksums, ws.nblk_cap);
-  KLAUNCH(h, k_emit, fgrid(g, ws.nblk_cap * emit_split(n)), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap, ws.d_wprefix, ws.va, bpv, ws.ba, bricks ? 1 : 0, 0u, emit_split(n));
-  KLAUNCH(h, k_count, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va, want_ptrank ? ws.d_ptrank : nullptr, ws.pt_cap);
-  HIPCHK(hipGetLastError());
-  return VOFOD_OK;
+  return launch_bitmap_chain(h, ws, g, n, max_pts, true, bpv, 0, 0u, want_ptrank);
 }
 
 // Stencil / brick tables of a clustering problem, cached per (leaf, tolerance, coordinate bound).
