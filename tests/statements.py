@@ -74,13 +74,37 @@ def close_image(m, thr, max_dist, vs):
     map's faces - pinned against the oracle's hasCloseTo by test_has_close_to_is_a_dilation_of_the_occupancy_image."""
     from scipy import ndimage
 
+    S, _ = close_stencil(max_dist, vs)
+    # close(c) = OR over o in S of occ(c + o): a dilation by the REFLECTED stencil (scipy's convention is occ(c - o))
+    return ndimage.binary_dilation(m > thr, structure=S[::-1, ::-1, ::-1])
+
+
+def close_stencil(max_dist, vs):
+    """hasCloseTo's stencil (voxel_map.cpp:376-400) as a boolean cube [oz, oy, ox] over the offsets -d .. d, d = ceil(max_dist / vs),
+    and d: {o in [-d, d)^3 : floor(sqrt(|o|^2)) <= max_dist / vs} - the half-open cube and the truncated integer norm of close_image"""
     mdi = np.float32(max_dist) * np.float32(np.float32(1.0) / np.float32(vs))
     dd = int(np.ceil(mdi))
     o = np.arange(-dd, dd + 1)
     oz, oy, ox = np.meshgrid(o, o, o, indexing="ij")
     S = (np.floor(np.sqrt((ox * ox + oy * oy + oz * oz).astype(np.float64))).astype(np.float32) <= mdi) & (ox < dd) & (oy < dd) & (oz < dd)
-    # close(c) = OR over o in S of occ(c + o): a dilation by the REFLECTED stencil (scipy's convention is occ(c - o))
-    return ndimage.binary_dilation(m > thr, structure=S[::-1, ::-1, ::-1])
+    return S, dd
+
+
+def close_at(m, thr, max_dist, vs, cells):
+    """hasCloseTo at the map cells `cells` [n, 3] (x, y, z) only: OR over the stencil's offsets of m[c + o] > thr, offsets that leave
+    the map skipped - close_image read at those cells, without dilating the whole map"""
+    S, dd = close_stencil(max_dist, vs)
+    oz, oy, ox = (a - dd for a in np.nonzero(S))
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1, 3)
+    sz, sy, sx = m.shape
+    out = np.zeros(len(cells), dtype=bool)
+    for k in range(0, len(cells), 2048):  # (2 197 offsets per cell: in slices)
+        c = cells[k : k + 2048]
+        x, y, z = c[:, 0, None] + ox[None, :], c[:, 1, None] + oy[None, :], c[:, 2, None] + oz[None, :]
+        ok = (x >= 0) & (x < sx) & (y >= 0) & (y < sy) & (z >= 0) & (z < sz)
+        occ = m[np.clip(z, 0, sz - 1), np.clip(y, 0, sy - 1), np.clip(x, 0, sx - 1)] > thr
+        out[k : k + 2048] = (occ & ok).any(axis=1)
+    return out
 
 
 def map_cells(pts, off, vs):

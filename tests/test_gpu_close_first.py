@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from vofod_amd import capi, synth
-from vofod_amd.detector import ScanData
 
+from close_first_edges import cells_scan as _cells_scan
 from helpers import assert_detections_equal, assert_scan_debug_equal, far_view, make_pair, sync_maps
 
 pytestmark = pytest.mark.gpu
@@ -95,17 +95,6 @@ def test_cold_map_everything_is_far(oracle, hip, sensor):
     for g in ga:
         assert int(g["clusters"]["is_close"].sum()) == 0
         assert len(g["clusters"]) >= 2
-
-
-def _cells_scan(pts_world, t, w=1024, h=16):
-    """a scan whose returns are the given world points, seen from a sensor at `t` (pose = pure translation)"""
-    n = w * h
-    p = np.asarray(pts_world, dtype=np.float64) - np.asarray(t, dtype=np.float64)
-    assert len(p) <= n
-    cols = [np.zeros(n, dtype=np.float32) for _ in range(3)]  # (0,0,0) = no return: dropped by the exclude box
-    for a in range(3):
-        cols[a][: len(p)] = p[:, a]
-    return ScanData(x=cols[0], y=cols[1], z=cols[2], width=w, height=h, stride_bytes=4)
 
 
 def test_far_blobs_at_exactly_the_tolerance_from_close_voxels(oracle, hip):

@@ -11,7 +11,7 @@ QUICK=(VOFOD_CLOSE_FIRST=0 VOFOD_DEVICE_TAIL=0 VOFOD_BRICK_LDS=0 VOFOD_CCL=voxel
 if [ "$1" = quick ]; then SW=("${QUICK[@]}"); else SW=("${ALL[@]}"); fi
 for x in $MATRIX_EXTRA; do SW+=("$x"); done
 TESTS=tests
-if [ "$1" = core ]; then TESTS="tests/test_gpu_parity.py tests/test_gpu_kat.py tests/test_gpu_close_first.py tests/test_gpu_tail_edges.py tests/test_gpu_lean_emit.py tests/test_gpu_detection_points.py"; fi
+if [ "$1" = core ]; then TESTS="tests/test_gpu_parity.py tests/test_gpu_kat.py tests/test_gpu_close_first.py tests/test_gpu_close_first_edges.py tests/test_gpu_tail_edges.py tests/test_gpu_lean_emit.py tests/test_gpu_detection_points.py"; fi
 # optional: first switch and number of switches (run_fallback_matrix.sh core 4 4: the fifth to the eighth), to take the matrix in parts
 FIRST=${2:-0}
 COUNT=${3:-${#SW[@]}}

@@ -690,6 +690,10 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   // VOFOD_CLOSE_FIRST=0: the full clustering everywhere.
   const bool close_first_on = !switch_off("VOFOD_CLOSE_FIRST");
   const bool dbg_far_only = dbg && dbg[0].far_only;
+  // (the release bound is tested against the count of the map as it is NOW: a map image rebuilt for this call - vofod_write_map, a
+  // scan through the full clustering - has its count still on the way, n_bg_voxels is the previous map's until it is fetched)
+  if (h->cf_off)
+    VCHK(latch_background(h));
   if (h->cf_off && (h->n_bg_voxels > h->cf_off_bg + h->cf_off_bg / 4 + 1000 || h->n_bg_voxels < h->cf_off_bg))
     h->cf_off = false;  // the map has changed a lot since: try the close-first kernel again
   ws.close_first = (close_first_on && rt.use_dilated && !h->cf_off) ? (dbg ? (dbg_far_only ? 2 : 0) : 1) : 0;
