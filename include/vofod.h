@@ -156,9 +156,31 @@ enum { VOFOD_MEM_HOST = 0, VOFOD_MEM_DEVICE = 1 };
  * plain range images and point scans); the caller may overwrite its pose tables when the call returns, as it may its scans.
  * vofod_raycast_begin and the raycast half of VOFOD_SCAN_AUTO_RAYCAST IGNORE col_tfs unless vofod_set_raycast_motion has switched
  * the compensated rays on (below): by default they cast the rigid rays the reference casts, from `range` and the LUT.  col_tfs on a
- * point scan (x, y, z given) is VOFOD_ERR_INVALID_ARG, and so is a device-resident table
- * that is not 4-byte aligned.  sizeof(vofod_scan) is 80 (72 before the field): callers recompile; a zero-initialised scan
+ * point scan (x, y, z given) is VOFOD_ERR_INVALID_ARG unless vofod_set_point_motion has switched it on (MOTION COMPENSATION OF POINT
+ * SCANS below), and so is a device-resident table that is not 4-byte aligned.  sizeof(vofod_scan) is 80 (72 before the field): callers recompile; a zero-initialised scan
  * (`vofod_scan s{}`) is rigid.  The CPU oracle has no motion input: it rejects range images as before and ignores the field. */
+/* MOTION COMPENSATION OF POINT SCANS.  With vofod_set_point_motion(h, 1) a point scan (x, y, z given: what the nodelet holds) may
+ * carry col_tfs too, and the product library applies the poses on the device in front of the unchanged pipeline (k_point_deskew).
+ * Pixel i = row * width + col was measured in column m = (col + shift_by_row[row]) mod width as above, T = col_tfs[m], q = (x[i],
+ * y[i], z[i]) as given, and the point of the pixel is DEFINED as (IEEE float32, each operation rounded once, nothing fused; the rules
+ * apply in this order)
+ *     p     = (+0, +0, +0)                          when q[0] == 0 && q[1] == 0 && q[2] == 0  (either sign of zero: ouster_ros' "no
+ *                                                   return"; no pose applied)
+ *     p     = (qNaN, qNaN, qNaN), bits 0x7fc00000   when any q[a] is not finite
+ *     p     = (qNaN, qNaN, qNaN)                    when lo[a] <= q[a] <= hi[a] on all three axes (the closed exclude box of the
+ *                                                   first crop, as above)
+ *     p[k]  = T[k][0]*q[0] + (T[k][1]*q[1] + (T[k][2]*q[2] + T[k][3]))           otherwise
+ * The call's `tf` follows in the unchanged pipeline; the two matrices are never multiplied together.  The `range` and `intensity`
+ * columns of the scan are not read by this step.  Fed the points vofod_range_to_points returns for a range image WITHOUT poses, this
+ * definition yields bit for bit what MOTION COMPENSATION yields for that range image with the same table: a pixel without a return
+ * decodes to (+0, +0, +0) and stays, every other q is the same float triple in both.
+ * With the switch on vofod_process_scan, vofod_process_batch and vofod_batch_submit accept such scans (a batch may mix them with plain
+ * point scans, plain range images and compensated range images); vofod_range_to_points stays range-image only.  With the switch off
+ * (the state after vofod_create) every call behaves as before: col_tfs on a point scan is VOFOD_ERR_INVALID_ARG.  Device-resident
+ * columns of such a scan are read in place and never written; their bases and their stride must be multiples of 4 bytes
+ * (VOFOD_ERR_INVALID_ARG), the table 4-byte aligned as above.  The caller may overwrite scans and tables when the call returns.
+ * VOFOD_SCAN_AUTO_RAYCAST on such a scan: the raycast half does what vofod_raycast_begin does with the same scan - rigid rays unless
+ * vofod_set_raycast_motion is on, compensated rays from the same table when it is. */
 /* MOTION-COMPENSATED RAYS.  With vofod_set_raycast_motion(h, 1) the raycast role casts the ray of every pixel of a scan that carries
  * col_tfs from that pixel's own pose.  For pixel i = row * width + col, with m = (col + shift_by_row[row]) mod width as above,
  * T = col_tfs[m], d = lut_directions[3i..] and o = lut_offsets[3i..] (zeros when the handle has none), the beam is DEFINED as (IEEE
@@ -220,7 +242,7 @@ typedef struct vofod_scan {
   const float* col_tfs;   /* NULL: the scan is rigid (everything as today).  Otherwise width * 12 floats in the scan's memspace:
                              col_tfs[12*m ..] is the row-major 3x4 [R|t] that takes a point from the sensor frame at the time of
                              measurement column m into the scan's reference sensor frame - the frame the call's `tf` starts from.
-                             Range images only; see MOTION COMPENSATION above */
+                             Range images, and point scans under vofod_set_point_motion; see MOTION COMPENSATION above */
 } vofod_scan;
 
 /* payload of vofod::PointXYZR (point_types.h:51-56): voxel centre + weight */
@@ -507,6 +529,18 @@ int vofod_set_column_shift(vofod_handle* h, const int32_t* shift_by_row /* heigh
  * ray by ray from the columns' poses (MOTION-COMPENSATED RAYS at vofod_scan; profiled as k_raycast_motion).  Kept across vofod_reset,
  * vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch or a raycast pass is pending. */
 int vofod_set_raycast_motion(vofod_handle* h, int on);
+/* vofod_set_point_motion: a handle property like the column shifts; `on` is taken as on != 0.  Off after vofod_create: col_tfs on a
+ * point scan is VOFOD_ERR_INVALID_ARG.  On: vofod_process_scan, vofod_process_batch and vofod_batch_submit compensate such scans on the
+ * device (MOTION COMPENSATION OF POINT SCANS at vofod_scan; profiled as k_point_deskew, one launch per batch that holds such frames).
+ * Kept across vofod_reset, vofod_map_apply and vofod_map_shift.  VOFOD_ERR_BUSY while a submitted batch is pending. */
+int vofod_set_point_motion(vofod_handle* h, int on);
+/* vofod_deskew_points: the compensated cloud of ONE point scan with col_tfs as the hot path sees it - the counterpart of
+ * vofod_range_to_points: three packed columns of width * height floats in `out_memspace`, computed by the kernel and through the
+ * staging the per-scan entry points use (frame slot 0 of the synchronous workspace).  Needs no switch.  For debug clouds and for
+ * holding the kernel to the definition.  VOFOD_ERR_INVALID_ARG: a range image, a scan without col_tfs, a device-resident table that
+ * is not 4-byte aligned, device-resident columns whose base or stride is no multiple of 4; VOFOD_ERR_SIZE_MISMATCH: width or height
+ * differ from the handle's; VOFOD_ERR_BUSY while ticket 0 is pending. */
+int vofod_deskew_points(vofod_handle* h, const vofod_scan* scan, float* x, float* y, float* z, int32_t out_memspace);
 /* vofod_set_raycast_exact: a handle property with the rules of vofod_set_raycast_motion; `on` is taken as on != 0.  Off after
  * vofod_create: raycast passes sum floats.  On: the passes vofod_raycast_begin and VOFOD_SCAN_AUTO_RAYCAST begin from now on sum
  * fixed-point units (EXACT RAYCAST ACCUMULATION at vofod_scan; profiled as k_raycast_exact, k_ray_sweep_exact).  Kept across vofod_reset,

@@ -86,6 +86,8 @@ sub["R16_MEASURED"] = (P / "r16_raycast_motion.txt").read_text().splitlines()[0]
 sub["R17_MEASURED"] = (P / "r17_raycast_exact.txt").read_text().splitlines()[0].removeprefix("measured: ")
 # §5.13: the first line of profiles/r18_raycast_one_walk.txt
 sub["R18_MEASURED"] = (P / "r18_raycast_one_walk.txt").read_text().splitlines()[0].removeprefix("measured: ")
+# §5.14: the first line of profiles/r21_point_motion.txt
+sub["R21_MEASURED"] = (P / "r21_point_motion.txt").read_text().splitlines()[0].removeprefix("measured: ")
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

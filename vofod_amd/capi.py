@@ -99,7 +99,7 @@ class Scan(C.Structure):
         ("height", C.c_int32),
         ("memspace", C.c_int32),
         ("stamp", C.c_double),
-        ("col_tfs", C.c_void_p),  # float[width * 12]: a pose per measurement column (range images only); NULL = rigid
+        ("col_tfs", C.c_void_p),  # float[width * 12]: a pose per measurement column (range images; point scans under set_point_motion); NULL = rigid
     ]
 
 
@@ -297,13 +297,16 @@ _SIGS = {
     "column_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "set_raycast_motion": (C.c_int, [C.c_void_p, C.c_int]),
     "set_raycast_exact": (C.c_int, [C.c_void_p, C.c_int]),
+    "set_point_motion": (C.c_int, [C.c_void_p, C.c_int]),
+    "deskew_points": (C.c_int, [C.c_void_p, _P(Scan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "raycast_units": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_int32)]),
 }
 
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
-                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units")
+                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units",
+                "set_point_motion", "deskew_points")
 
 
 class MsgHeader(C.Structure):

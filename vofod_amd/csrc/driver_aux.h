@@ -1422,6 +1422,49 @@ int vofod_range_to_points(vofod_handle* h, const vofod_scan* scan, float* x, flo
   return VOFOD_OK;
 }
 
+// The compensated cloud of ONE point scan with col_tfs, by the route the batch takes: staged into frame slot 0 of the synchronous
+// workspace, one job of k_point_deskew, the slot's packed columns copied out.  Needs no switch (vofod_set_point_motion admits such
+// scans to the per-scan entry points; this call is what they would see).
+int vofod_deskew_points(vofod_handle* h, const vofod_scan* scan, float* x, float* y, float* z, int32_t out_memspace)
+{
+  if (!h || !scan || !x || !y || !z || !scan->x || !scan->y || !scan->z || !scan->col_tfs || (out_memspace != VOFOD_MEM_HOST && out_memspace != VOFOD_MEM_DEVICE) ||
+      (scan->memspace != VOFOD_MEM_HOST && scan->memspace != VOFOD_MEM_DEVICE))
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  (void)hipSetDevice(h->device);
+  if (scan->height != h->sp.sensor_vrays || scan->width != h->sp.sensor_hrays)
+    return VOFOD_ERR_SIZE_MISMATCH;
+  if (scan->memspace == VOFOD_MEM_DEVICE && reinterpret_cast<uintptr_t>(scan->col_tfs) % 4 != 0)
+  {
+    h->err = "device-resident col_tfs: the table must be 4-byte aligned";
+    return VOFOD_ERR_INVALID_ARG;
+  }
+  VCHK(busy_check(h, true, false));
+  Workspace& ws = h->ws;
+  const size_t npts = static_cast<size_t>(scan->width) * scan->height;
+  const float tf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  bool host_copies = false;
+  VCHK(stage_inputs(h, ws, scan, tf, 1, npts, host_copies));  // (refuses device columns whose base or stride is no multiple of 4)
+  VCHK(deskew_points(h, ws, npts));
+  float* out[3] = {x, y, z};
+  for (int c = 0; c < 3; c++)
+    HIPCHK(hipMemcpyAsync(out[c], ws.d_stage + static_cast<size_t>(c) * ws.pt_cap, npts * sizeof(float), out_memspace == VOFOD_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                          h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VOFOD_OK;
+}
+
+// A handle property, as the column shifts: off after vofod_create, kept across vofod_reset, vofod_map_apply and vofod_map_shift.
+int vofod_set_point_motion(vofod_handle* h, int on)
+{
+  if (!h)
+    return VOFOD_ERR_INVALID_ARG;
+  std::scoped_lock lck(h->mtx);
+  VCHK(busy_check(h, true, true));
+  h->point_motion = on != 0;
+  return VOFOD_OK;
+}
+
 // A sensor property: the measurement column of pixel (row, col) is (col + shift_by_row[row]) mod width.  The device table holds the
 // shifts reduced to [0, width), so the kernel's mod is one compare.
 int vofod_set_column_shift(vofod_handle* h, const int32_t* shift_by_row)

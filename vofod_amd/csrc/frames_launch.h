@@ -173,14 +173,15 @@ int route_submitted(vofod_handle* h, const Workspace& ws, uint32_t n, LaunchRout
 // a range image (include/vofod.h): no point columns, only the sensor's range column
 inline bool is_range_image(const vofod_scan& s) { return !s.x && !s.y && !s.z && s.range; }
 
-// a pose per column (vofod_scan::col_tfs): range images only; a device-resident table is read in place with 4-byte loads at least
+// a pose per column (vofod_scan::col_tfs): range images, and point scans once vofod_set_point_motion has switched them on; a
+// device-resident table is read in place with 4-byte loads at least
 inline int check_col_tfs(vofod_handle* h, const vofod_scan& s)
 {
   if (!s.col_tfs)
     return VOFOD_OK;
-  if (!is_range_image(s))
+  if (!is_range_image(s) && !h->point_motion)
   {
-    h->err = "col_tfs: only a range image (x == y == z == NULL) may carry a pose per column";
+    h->err = "col_tfs: only a range image (x == y == z == NULL) may carry a pose per column unless vofod_set_point_motion is on";
     return VOFOD_ERR_INVALID_ARG;
   }
   if (s.memspace == VOFOD_MEM_DEVICE && reinterpret_cast<uintptr_t>(s.col_tfs) % 4 != 0)
@@ -204,26 +205,27 @@ int pose_slot(vofod_handle* h, Workspace& ws, size_t k, const float* src, hipStr
   return VOFOD_OK;
 }
 
-// Pose tables of the batch's motion jobs (the first n_mjobs of the job list, in frame order): device-resident tables are read where
-// they lie, host-resident ones go to the workspace's pose block - table j of the list into slot j - with ONE 2-D copy when they lie
-// at a constant pitch (one numpy block per batch), otherwise one copy each.  On the stream of the staging copies, in front of the event
-// vofod_batch_submit waits for: the caller may overwrite its tables when submit returns.
+// Pose tables of the batch's scans with col_tfs - the motion jobs of the range list (its first n_mjobs) and the point jobs, each list
+// in frame order: device-resident tables are read where they lie, host-resident ones go to the workspace's pose block - the k-th host
+// table of the batch into slot k, whichever list its job is in - with ONE 2-D copy when they lie at a constant pitch (one numpy block
+// per batch), otherwise one copy each.  On the stream of the staging copies, in front of the event vofod_batch_submit waits for: the
+// caller may overwrite its tables when submit returns.
 int stage_pose_tables(vofod_handle* h, Workspace& ws, const vofod_scan* scans, uint32_t n)
 {
   const size_t tab = static_cast<size_t>(h->sp.sensor_hrays) * 12;  // floats per table
-  std::vector<const float*> host;                                     // the host tables, and the job each belongs to
-  std::vector<uint32_t> job_of;
-  uint32_t j = 0;
+  std::vector<const float*> host;                                     // the host tables, and the job entry each belongs to
+  std::vector<const float**> entry_of;
+  uint32_t jm = 0, jp = 0;
   for (uint32_t f = 0; f < n; f++)
   {
     if (!scans[f].col_tfs)
       continue;
+    const float** entry = is_range_image(scans[f]) ? &ws.h_rjobs.p[jm++].poses : &ws.h_pjobs.p[jp++].poses;
     if (scans[f].memspace != VOFOD_MEM_DEVICE)
     {
       host.push_back(scans[f].col_tfs);
-      job_of.push_back(j);
+      entry_of.push_back(entry);
     }
-    j++;
   }
   if (host.empty())
     return VOFOD_OK;
@@ -235,17 +237,16 @@ int stage_pose_tables(vofod_handle* h, Workspace& ws, const vofod_scan* scans, u
   {
     float* slot = nullptr;
     VCHK(pose_slot(h, ws, k, constant ? nullptr : host[k], h->stream, slot));
-    ws.h_rjobs.p[job_of[k]].poses = slot;
+    *entry_of[k] = slot;
   }
   if (constant)
     HIPCHK(hipMemcpy2DAsync(ws.d_poses, tab * sizeof(float), host[0], static_cast<size_t>(pitch), tab * sizeof(float), host.size(), hipMemcpyHostToDevice, h->stream));
   return VOFOD_OK;
 }
 
-// the device copy of the pose table of the call's FIRST scan as stage_pose_tables left it in the workspace's job list (the motion jobs
-// lead the list in frame order: a first scan with a table owns job 0); nullptr when the scan has none.  A re-run keeps the list of its
-// first launch.
-inline const float* staged_pose_table(const Workspace& ws, const vofod_scan& s) { return s.col_tfs && ws.n_mjobs ? ws.h_rjobs.p[0].poses : nullptr; }
+// the device copy of the pose table of the call's FIRST scan as stage_inputs left it in the workspace (a range image's or a point
+// scan's); nullptr when the scan has none.  A re-run keeps that of its first launch.
+inline const float* staged_pose_table(const Workspace& ws, const vofod_scan& s) { return s.col_tfs ? ws.first_poses : nullptr; }
 
 // ---- stage inputs (filterAndTransform :621-684 reads them)
 // (the re-run of a batch that overflowed the LDS kernels keeps the frame arguments and the staged columns of its first
@@ -260,10 +261,14 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
 {
   bool staged_2d = false;
   ws.det_valid = false;  // (the workspace is taken: what vofod_detection_points answered from is about to be overwritten)
-  ws.n_rjobs = ws.n_mjobs = 0;
+  ws.n_rjobs = ws.n_mjobs = ws.n_pjobs = 0;
+  ws.first_poses = nullptr;
   // the range images of the batch, in frame order for now (a pose table: the caller's, for now)
   vrd::RangeJob* const jobs = ws.h_rjobs.p;
   uint32_t n_jobs = 0;
+  // ... and its point scans with a pose per column, in frame order
+  vpd::PointJob* const pjobs = ws.h_pjobs.p;
+  uint32_t n_pjobs = 0;
   auto slot = [&](uint32_t f) { return ws.d_stage + static_cast<size_t>(f) * ws.pt_cap * 5; };
   // the frame's arguments point at the packed x | y | z columns of its staging slot (copied there, or decoded there by k_range_decode)
   auto slot_args = [&](uint32_t f) {
@@ -286,7 +291,11 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
     {
       HIPCHK(hipMemcpy2DAsync(ws.d_stage, sizeof(float) * 5 * ws.pt_cap, x0, static_cast<size_t>(pitch), npts * 12, n, hipMemcpyHostToDevice, h->stream));
       for (uint32_t f = 0; f < n; f++)
+      {
         VCHK(slot_args(f));
+        if (scans[f].col_tfs)  // k_point_deskew works in place over the slot
+          pjobs[n_pjobs++] = vpd::PointJob{ws.h_args[f].x, ws.h_args[f].y, ws.h_args[f].z, slot(f), 4, scans[f].col_tfs};
+      }
       staged_2d = true;
     }
   }
@@ -321,6 +330,20 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
     if (!is_range_image(s))
     {
       VCHK(stage_cloud(h, ws, f, s.x, s.y, s.z, nullptr, nullptr, s.stride_bytes, npts, s.memspace, FA_SCAN, tfs + 12 * f));
+      if (!s.col_tfs)
+        continue;
+      // a point scan with poses: k_point_deskew reads the columns where stage_cloud has left them for the kernels - the caller's
+      // device memory, the struct block of a host scan, the slot itself - and writes the packed columns of the slot, which the
+      // frame's arguments point at from here on
+      if (s.memspace == VOFOD_MEM_DEVICE &&
+          (s.stride_bytes % 4 != 0 || (reinterpret_cast<uintptr_t>(s.x) | reinterpret_cast<uintptr_t>(s.y) | reinterpret_cast<uintptr_t>(s.z)) % 4 != 0))
+      {
+        h->err = "device-resident point scan with col_tfs: the columns' bases and stride must be multiples of 4 bytes";
+        return VOFOD_ERR_INVALID_ARG;
+      }
+      const FrameArgs& a = ws.h_args[f];
+      pjobs[n_pjobs++] = vpd::PointJob{a.x, a.y, a.z, slot(f), a.stride, s.col_tfs};
+      VCHK(slot_args(f));
       continue;
     }
     // a range image: device-resident ranges are read where they lie, a host column goes to column 4 of the slot (gathered when strided)
@@ -343,10 +366,45 @@ int stage_inputs(vofod_handle* h, Workspace& ws, const vofod_scan* scans, const 
   // still in frame order; the whole list goes up with one copy
   ws.n_mjobs = static_cast<uint32_t>(std::stable_partition(jobs, jobs + n_jobs, [](const vrd::RangeJob& job) { return job.poses != nullptr; }) - jobs);
   ws.n_rjobs = n_jobs - ws.n_mjobs;
-  if (ws.n_mjobs)
+  ws.n_pjobs = n_pjobs;
+  if (ws.n_mjobs || n_pjobs)
     VCHK(stage_pose_tables(h, ws, scans, n));
+  // (a first scan with a table owns job 0 of its list: the motion jobs lead the range list in frame order)
+  ws.first_poses = !scans[0].col_tfs ? nullptr : is_range_image(scans[0]) ? jobs[0].poses : pjobs[0].poses;
   if (n_jobs)
     HIPCHK(hipMemcpyAsync(ws.d_rjobs, jobs, sizeof(vrd::RangeJob) * n_jobs, hipMemcpyHostToDevice, h->stream));
+  if (n_pjobs)
+    HIPCHK(hipMemcpyAsync(ws.d_pjobs, pjobs, sizeof(vpd::PointJob) * n_pjobs, hipMemcpyHostToDevice, h->stream));
+  return VOFOD_OK;
+}
+
+// k_point_deskew over the job list stage_inputs left in the workspace: ONE launch per batch on the stream of the staging copies (no
+// such frame: no launch), the instantiation chosen by what every job of the batch allows
+int deskew_points(vofod_handle* h, Workspace& ws, size_t npts)
+{
+  if (!ws.n_pjobs || !npts)
+    return VOFOD_OK;
+  bool vec = npts % 4 == 0 && ws.pt_cap % 4 == 0, pose16 = true;
+  for (uint32_t j = 0; j < ws.n_pjobs; j++)
+  {
+    const vpd::PointJob& job = ws.h_pjobs.p[j];
+    vec = vec && job.stride == 4 &&
+          (reinterpret_cast<uintptr_t>(job.x) | reinterpret_cast<uintptr_t>(job.y) | reinterpret_cast<uintptr_t>(job.z) | reinterpret_cast<uintptr_t>(job.dst)) % 16 == 0;
+    pose16 = pose16 && reinterpret_cast<uintptr_t>(job.poses) % 16 == 0;
+  }
+  vrd::MotionArgs ma{};
+  ma.shift = h->d_col_shift.p;
+  ma.width = static_cast<uint32_t>(h->sp.sensor_hrays);
+  exclude_box(h, ma.lo, ma.hi);
+  const uint32_t n_px = static_cast<uint32_t>(npts), per_block = vpd::PD_THREADS * (vec ? 4u : 1u);
+  const dim3 grid((n_px + per_block - 1) / per_block, ws.n_pjobs);
+  auto pick = [&](auto v) {
+    constexpr bool V = decltype(v)::value;
+    return pose16 ? vpd::k_point_deskew_t<V, true> : vpd::k_point_deskew_t<V, false>;  // (aligned tables: fetched through LDS)
+  };
+  auto kern = vec ? pick(std::true_type{}) : pick(std::false_type{});
+  KLAUNCH_AS(h, "k_point_deskew", kern, grid, dim3(vpd::PD_THREADS), ws.d_pjobs.p, n_px, ws.pt_cap, ma);
+  HIPCHK(hipGetLastError());
   return VOFOD_OK;
 }
 
@@ -653,7 +711,10 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
     host_copies = false;
   H2DGuard h2d_guard{ws.ev_h2d, host_copies};
   if (!rerun)
+  {
     VCHK(decode_ranges(h, ws, npts));
+    VCHK(deskew_points(h, ws, npts));
+  }
 
   GridParams& g = call.g;
   const float leaf[3] = {sp.voxel_size, sp.voxel_size, sp.voxel_size};

@@ -31,6 +31,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "column_pose.h"
 #include "kernels_brick_lds.h"
 #include "kernels_slab.h"
 
@@ -87,15 +88,6 @@ struct FrameScratch
   float4* frag;              // [F][pt_cap]: the fragile points of the input pass: transformed coordinates, w: their brick code (written once the frame's lattice is known)
   uint32_t keys_cap;         // words of a frame's code list (SlabArrays::keys): the point capacity rounded up to IN_SEG_ALIGN - 16 per-wave segments
 };
-
-// 16-byte load through the global address space (the column pointers come out of a struct in memory: the compiler would
-// otherwise emit flat loads, which also probe the LDS aperture)
-__device__ __forceinline__ float4 ldg_f4(const char* p)
-{
-  typedef float gf4 __attribute__((ext_vector_type(4)));
-  const gf4 v = *reinterpret_cast<const __attribute__((address_space(1))) gf4*>(reinterpret_cast<uintptr_t>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-}
 
 // ---- one pass over the input ---------------------------------------------------------------------------------------
 // The lattice of a frame hangs on its own bounding box (voxel_grid_weighted.cpp:72-106: offset = floor(min * inv) * leaf -

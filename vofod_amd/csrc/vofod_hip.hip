@@ -34,6 +34,7 @@
 #include "kernels_voxelize.h"
 #include "mapsync.h"
 #include "range_decode.h"
+#include "point_deskew.h"
 #include "detection_points.h"
 #include "map_shift.h"
 
@@ -280,6 +281,12 @@ struct Workspace
   PinBuf<vrd::RangeJob> h_rjobs;
   uint32_t n_mjobs = 0, n_rjobs = 0;
   DevBuf<float> d_poses;
+  // point scans with a pose per column (point_deskew.h): their job list, in frame order, written and uploaded like the range jobs; their
+  // host tables take slots of the same pose block (a frame is a range image or a point scan: F tables in all)
+  DevBuf<vpd::PointJob> d_pjobs;
+  PinBuf<vpd::PointJob> h_pjobs;
+  uint32_t n_pjobs = 0;
+  const float* first_poses = nullptr;  // the device copy of the pose table of the batch's FIRST scan (nullptr: it has none)
   DevBuf<PackedFrame> d_packed;
   PinBuf<PackedFrame> h_packed;
   bool mapbits_patched = false;  // k_finalize_far kept the map's occupancy image and counters up to date with this scan's update
@@ -403,6 +410,8 @@ private:
     HIP_TRY(d_stage.alloc(5 * static_cast<size_t>(F_) * pt_cap_));
     HIP_TRY(d_rjobs.alloc(F_));
     HIP_TRY(h_rjobs.alloc(F_));
+    HIP_TRY(d_pjobs.alloc(F_));
+    HIP_TRY(h_pjobs.alloc(F_));
     HIP_TRY(d_packed.alloc(F_));
     HIP_TRY(d_tailc.alloc(vtd::TP_MAXC * static_cast<size_t>(F_)));
     HIP_TRY(d_dets.alloc(F_));
@@ -519,6 +528,7 @@ struct vofod_handle
   DevBuf<uint8_t> d_mask;
   DevBuf<uint32_t> d_col_shift;  // vofod_set_column_shift: one shift per row, reduced to [0, width); zeros until set
   bool raycast_motion = false;   // vofod_set_raycast_motion: the raycast role casts a scan with col_tfs ray by ray from the columns' poses (k_raycast_motion)
+  bool point_motion = false;     // vofod_set_point_motion: the per-scan entry points accept col_tfs on a point scan (k_point_deskew)
   bool raycast_exact = false;    // vofod_set_raycast_exact: the next raycast pass accumulates fixed-point units (k_raycast_exact)
   bool ray_pass_exact = false;   // the pass between begin and finish holds units in d_ray (the representation belongs to the pass: begin records it)
   int32_t ray_log2_units = -1;   // S and QMAX of EXACT RAYCAST ACCUMULATION, fixed at create (-1: no S fits, the switch is refused)

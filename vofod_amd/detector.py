@@ -38,7 +38,7 @@ class ScanData:
     stride_bytes: int = 4
     memspace: int = capi.MEM_HOST
     stamp: float = 0.0
-    col_tfs: object = None  # range images only: float32 [width, 3, 4] (or a device address), a pose per measurement column
+    col_tfs: object = None  # range images, and point scans under VoFOD.set_point_motion: float32 [width, 3, 4] (or a device address), a pose per measurement column
 
     @classmethod
     def range_image(cls, range, width: int, height: int, intensity=None, stride_bytes: int = 4, memspace: int = capi.MEM_HOST, stamp: float = 0.0, col_tfs=None) -> "ScanData":
@@ -199,6 +199,11 @@ class VoFOD:
         """vofod_set_raycast_motion: with it on, raycast_begin and the raycast half of SCAN_AUTO_RAYCAST cast a scan that carries
         `col_tfs` ray by ray from the columns' poses; off (the state after creation) they cast the rigid rays"""
         return self._check(self.lib.set_raycast_motion(self.h, int(bool(on))), "vofod_set_raycast_motion", allow)
+
+    def set_point_motion(self, on: bool = True, allow: Sequence[int] = ()):
+        """vofod_set_point_motion: with it on, process_scan, process_batch and batch_submit accept a point scan that carries `col_tfs`
+        and apply the columns' poses on the device (k_point_deskew); off (the state after creation) such a scan is refused"""
+        return self._check(self.lib.set_point_motion(self.h, int(bool(on))), "vofod_set_point_motion", allow)
 
     def set_raycast_exact(self, on: bool = True, allow: Sequence[int] = ()):
         """vofod_set_raycast_exact: with it on, the raycast passes begun from now on sum fixed-point units in uint32 (order
@@ -378,6 +383,19 @@ class VoFOD:
         xyz = [np.full(n, np.nan, dtype=np.float32) for _ in range(3)]
         self._check(self.lib.range_to_points(self.h, C.byref(cs), *(capi.ptr(a) for a in xyz), capi.MEM_HOST), "vofod_range_to_points", allow)
         return tuple(xyz)
+
+    def deskew_points(self, scan: ScanData, out=None, allow: Sequence[int] = ()):
+        """The compensated cloud of a point scan with `col_tfs` as the hot path sees it (vofod_deskew_points): three float32 arrays of
+        w*h values, or - with `out` = three device addresses - written to device memory (returns None).  With a status in `allow`
+        returned by the call: that status."""
+        cs = scan.as_c()
+        n = scan.width * scan.height
+        if out is not None:
+            st = self._check(self.lib.deskew_points(self.h, C.byref(cs), *(C.c_void_p(int(a)) for a in out), capi.MEM_DEVICE), "vofod_deskew_points", allow)
+            return None if st == capi.OK else st
+        xyz = [np.full(n, np.nan, dtype=np.float32) for _ in range(3)]
+        st = self._check(self.lib.deskew_points(self.h, C.byref(cs), *(capi.ptr(a) for a in xyz), capi.MEM_HOST), "vofod_deskew_points", allow)
+        return tuple(xyz) if st == capi.OK else st
 
     def detection_points(self, source: int = capi.POINTS_SYNC, device_out=None, allow: Sequence[int] = ()):
         """Member voxels and AABB of the detections returned last from `source` (vofod_detection_points): capi.POINTS_SYNC for the
