@@ -101,7 +101,8 @@ def test_bench_byte_model_names_the_kernels_of_the_batched_path():
     priced = set(re.findall(r'"(k_[a-z0-9_]+)', table))
     driver = (root / "vofod_amd" / "csrc" / "vofod_hip.hip").read_text()
     launched = set(re.findall(r"KLAUNCH(?:_LDS)?\(h, (?:vk::)?(k_[a-z0-9_]+)", driver))
-    launched |= set(re.findall(r'VOFOD_FRAME_LAUNCH\("(k_[a-z0-9_]+)"', driver))  # (the frame kernel's instantiations are profiled under their algorithmic names)
+    # (the frame kernel's instantiations are profiled under their algorithmic names: the labels launch_frame_kernel chooses from)
+    launched |= set(re.findall(r'"(k_[a-z0-9_]+)"', driver[driver.index("const char* label = "):].split(";", 1)[0]))
     names = ("k_bbox", "k_frame_lds_full", "k_frame_lds_far")
     streaming = {k for k in launched if k in names}
     assert streaming == set(names)

@@ -70,7 +70,7 @@ def test_bench_workload_256_frames_os1_128(oracle, hip, fallback, monkeypatch):
     (k_frame_lds_far, which reads the input itself, -> k_tail_far), every frame against the oracle - by default and under each production fallback:
     the full clustering (what a cold map takes), the host tail (what a capacity of the device tail falls back to), and frames
     beyond the LDS image (every frame here holds more than 4096 bricks: the batch is run again on the
-    global-memory kernels).  The switches are read on every call (vofod_hip.hip switch_off)."""
+    global-memory kernels).  The switches are read on every call (chain_plan.h read_switches)."""
     if fallback:
         k, v = fallback.split("=")
         monkeypatch.setenv(k, v)

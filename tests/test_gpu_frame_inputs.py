@@ -354,7 +354,7 @@ def test_device_layouts(default_case, layout):
 @pytest.mark.parametrize("vrays,hrays", [(17, 1021), (15, 1022), (15, 1021)])
 def test_point_counts_that_are_no_multiple_of_four(oracle, hip, vrays, hrays):
     """w*h % 4 = 1, 2, 3 (17 357, 15 330, 15 315 points): plain host columns, staged as they are, but the packed pass
-    reads four points per 16-byte load and takes whole quads only: launch_voxelize asks (n & 3) == 0 of every frame - strided.  The counts end inside an input round of 8 192 points: the n_pts-1 clamp of the loads
+    reads four points per 16-byte load and takes whole quads only: launch_frames asks (n & 3) == 0 of every frame - strided.  The counts end inside an input round of 8 192 points: the n_pts-1 clamp of the loads
     and the i0 + j < n_pts test drop the round's tail."""
     shape = (vrays, hrays, 33.2, 120.0)
     n = vrays * hrays

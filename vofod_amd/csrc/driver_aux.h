@@ -277,7 +277,7 @@ int grow_workspace(vofod_handle* h, Workspace& ws, const char* what, uint32_t F,
 }
 
 // voxelise one device/host cloud into `ws` (frame 0), growing the workspace to the lattice it needs
-int voxelize_cloud(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const vofod_cloud_view* in, GridParams& g, const float leaf[3], bool align, const float* align_center, FrameHdr& hdr)
+int voxelize_cloud(vofod_handle* h, Workspace& ws, const vofod_cloud_view* in, GridParams& g, const float leaf[3], bool align, const float* align_center, FrameHdr& hdr)
 {
   const uint32_t n = static_cast<uint32_t>(in->n);
   // Growth with headroom: a workspace grows by releasing and allocating its three dozen arrays (2.6 ms), and the cloud of
@@ -290,7 +290,7 @@ int voxelize_cloud(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const vofod_
     VCHK(stage_cloud(h, ws, 0, in->x, in->y, in->z, in->intensity, nullptr, in->stride_bytes, n, in->memspace, 0, nullptr));
     const float zero[3] = {0, 0, 0};
     fill_grid_params(h, g, leaf, align, align ? align_center : zero, ws);
-    VCHK(launch_voxelize(h, ws, lf, g, 1, n, false, true));
+    VCHK(launch_lattice(h, ws, g, 1, n));  // (the lattice's size is inspected before the bitmap is touched)
     HIPCHK(hipMemcpyAsync(&ws.h_packed[0].hdr, ws.d_hdrs, sizeof(FrameHdr), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     hdr = ws.h_packed[0].hdr;
@@ -310,7 +310,7 @@ int voxelize_cloud(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const vofod_
     hdr.V = 0;
     return VOFOD_OK;
   }
-  VCHK(launch_voxelize_rest(h, ws, lf, g, 1, n, false));
+  VCHK(launch_bitmap_chain(h, ws, g, 1, n, true));
   HIPCHK(hipMemcpyAsync(&ws.h_packed[0].hdr, ws.d_hdrs, sizeof(FrameHdr), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   hdr = ws.h_packed[0].hdr;
@@ -368,8 +368,7 @@ int sepclusters_begin_locked(vofod_handle* h, int* sure_out)
   view.memspace = VOFOD_MEM_DEVICE;
   const float leaf[3] = {lsz, lsz, lsz};
   FrameHdr hdr;
-  LaunchFlags lf;  // (of this role's one launch: voxelisation, then the clustering below)
-  VCHK(voxelize_cloud(h, h->sepws, lf, &view, s.g, leaf, false, nullptr, hdr));
+  VCHK(voxelize_cloud(h, h->sepws, &view, s.g, leaf, false, nullptr, hdr));
   Workspace& ws = h->sepws;
   tr[1] = ms_since(t0);
   VCHK(counted_tail(h, ws, hdr.V, P, s.d_sure));
@@ -377,7 +376,9 @@ int sepclusters_begin_locked(vofod_handle* h, int* sure_out)
 
   // clusterCloud(vmap_pc_ds, max_voxel_dist) :1171
   const float cmax = static_cast<float>(std::max({h->mg.sx, h->mg.sy, h->mg.sz})) + 2 * lsz;
-  VCHK(launch_cluster(h, ws, lf, s.g, 1, static_cast<float>(max_voxel_dist), cmax));
+  vofod_handle::ClusterTables* ct = nullptr;
+  VCHK(cluster_tables(h, s.g, static_cast<float>(max_voxel_dist), cmax, &ct));
+  VCHK(launch_cluster(h, ws, plan_cluster_only(h, ws, ct), s.g, ct));
   tr[3] = ms_since(t0);
   // sure voxels per cluster :1175-1183 and the latch :1188-1206
   HIPCHK(hipMemsetAsync(s.d_nsure, 0, sizeof(uint32_t) * std::max(hdr.V, 1u), h->stream));
@@ -1706,8 +1707,7 @@ int vofod_voxel_grid_weighted(vofod_handle* h, const vofod_cloud_view* in, float
       *grid = vofod_grid_desc{{leaf, leaf, leaf}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
     return VOFOD_OK;
   }
-  LaunchFlags lf;
-  const int r = voxelize_cloud(h, h->aux, lf, in, g, l, align != 0, align_center, hdr);
+  const int r = voxelize_cloud(h, h->aux, in, g, l, align != 0, align_center, hdr);
   if (r != VOFOD_OK)
   {
     if (n_out)
@@ -1734,8 +1734,7 @@ int vofod_voxel_grid_counted(vofod_handle* h, const vofod_cloud_view* in, float 
       *n_out = 0;
     return VOFOD_OK;
   }
-  LaunchFlags lf;
-  int r = voxelize_cloud(h, h->aux, lf, in, g, l, false, nullptr, hdr);
+  int r = voxelize_cloud(h, h->aux, in, g, l, false, nullptr, hdr);
   if (r != VOFOD_OK)
   {
     if (n_out)
@@ -1825,8 +1824,9 @@ int vofod_cluster(vofod_handle* h, const vofod_point_xyzr* pts, const uint32_t* 
   float cmax = 0;
   for (int a = 0; a < 3; a++)
     cmax = std::max({cmax, std::fabs(grid->offset[a]), std::fabs(grid->offset[a] + grid->leaf[a] * (grid->div_b[a] + 1))});
-  LaunchFlags lf;  // (the voxel records came from the caller: no voxelisation stage has left anything for the clustering)
-  VCHK(launch_cluster(h, ws, lf, g, 1, tolerance, cmax));
+  vofod_handle::ClusterTables* ct = nullptr;
+  VCHK(cluster_tables(h, g, tolerance, cmax, &ct));
+  VCHK(launch_cluster(h, ws, plan_cluster_only(h, ws, ct), g, ct));
   HIPCHK(hipMemcpyAsync(labels, ws.d_labels, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   if (n_clusters)

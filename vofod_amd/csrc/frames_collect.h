@@ -5,21 +5,12 @@
 namespace
 {
 
-// VOFOD_LDS_PROF=2: the frame kernel's stamps of this batch are printed when it is collected
-int print_deferred_prof(vofod_handle* h, Workspace& ws, uint32_t n)
-{
-  if (!ws.prof_deferred || !h->d_prof_ccl)
-    return VOFOD_OK;
-  ws.prof_deferred = false;
-  return print_frame_prof(h, ws.prof_slot0, n, false);
-}
-
 // The frames' status words, wherever they came back, into the packed slots.  A frame that held more bricks than the LDS
 // clustering kernel takes: nothing of this batch was used (batches never update the map); the caller runs it again on the
 // global-memory kernels.
 int adopt_status(vofod_handle* h, Workspace& ws, uint32_t n)
 {
-  if (ws.dtail)
+  if (ws.plan.dtail)
     for (uint32_t f = 0; f < n; f++)
       ws.h_packed[f].hdr.status = ws.h_dets[f].status;
   for (uint32_t f = 0; f < n; f++)
@@ -37,14 +28,8 @@ int adopt_status(vofod_handle* h, Workspace& ws, uint32_t n)
 // a map-updating scan has changed the map under its occupancy image
 void book_map_images(vofod_handle* h, Workspace& ws)
 {
-  bool keep = false;
-  if (ws.mapbits_patched)
-  {
-    // (the image was patched by k_finalize_far - unless the scan has to run again or left the map: then it is rebuilt)
-    keep = ws.h_packed[0].hdr.status == VOFOD_OK && h->mapbits_valid;
-    ws.mapbits_patched = false;
-  }
-  if (keep)
+  // (the image was patched by k_finalize_far - unless the scan has to run again or left the map: then it is rebuilt)
+  if (ws.plan.mapbits_patched && ws.h_packed[0].hdr.status == VOFOD_OK && h->mapbits_valid)
   {
     h->bgcount_stale = true;  // (the counters on the device are newer than the host's sum: fetched when somebody needs it)
     h->mapbits_gen++;         // (the dilated image of the batches is of an older state)
@@ -534,7 +519,7 @@ int collect_frames(vofod_handle* h, Workspace& ws, FrameCall& call, vofod_detect
       dev_ms[i] = ms;
     }
 
-  if (ws.dtail)
+  if (ws.plan.dtail)
   {
     uint32_t fb = 0;
     for (uint32_t f = 0; f < n; f++)
@@ -545,7 +530,6 @@ int collect_frames(vofod_handle* h, Workspace& ws, FrameCall& call, vofod_detect
       return device_tail_overflow_records(h, ws, call, fb, out, cap, n_out_per_frame, n_out);
     // a frame exceeded a capacity of the device tail: the host tail redoes the batch from the full tables
     // (capacities of k_tail_prep - members, clusters, radius: no flood fill has run yet, also on a map-updating scan)
-    ws.dtail = false;
     VCHK(read_back_full(h, ws, call.g, n));
     HIPCHK(hipStreamSynchronize(h->stream));
   }

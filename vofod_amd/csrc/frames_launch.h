@@ -21,23 +21,19 @@ struct FrameCall
   const vofod_dyn_params* dp = nullptr;
   GridParams g{};
   bool rc_done = false;     // ++its and the raycast role of VOFOD_SCAN_AUTO_RAYCAST have run ahead of the device tail
-  bool far_single = false;  // a single map-updating scan clustered close first on the general path (kernels_far.h)
   hipStream_t tail_stream_used = nullptr;  // where the device tail's last operation was enqueued
   DevEvent ev[5];  // debug output: stage boundaries on the chain's stream
   clk::time_point t0 = clk::now();
   double tr_launch = 0, tr_sync1 = 0;  // VOFOD_TRACE
 };
 
-// How a launch is routed.  What differs between a submitted and a synchronous launch is decided here, once.
+// Which streams a launch takes (route_submitted): what differs between a submitted and a synchronous launch.  Which kernels it runs is
+// the plan's (chain_plan.h).
 struct LaunchRoute
 {
-  bool no_update = false;
-  bool use_dilated = false;       // read-only batches: the map's dilated image answers hasCloseTo with one bit per voxel
   bool staged = false;            // submitted, 128 frames and more: three-stage pipeline on the streaming / frame / tail streams
   hipStream_t chain = nullptr;    // submitted: the stream of the chain (the ticket's own, or the streaming stage's); nullptr: the handle's
   int own_tail = -1;              // submitted small batch: the ticket whose stream and flood-fill buffers the device tail takes
-  bool single_update = false;     // one map-updating scan, synchronous: the reference's own mode
-  bool dtail = false;             // the classification tail runs on the device (otherwise the full tables come back for the host tail)
 };
 
 // h->stream names the stream every KLAUNCH goes to.  A scope that sends the launches elsewhere (or moves h->stream itself
@@ -489,19 +485,6 @@ int prepare_map_images(vofod_handle* h, const vofod_dyn_params& dp, float thr_ne
   return VOFOD_OK;
 }
 
-// ---- K1-K6 (filterAndTransform :621-684) - or only the plan of the frame kernel, which reads the input itself
-int voxelize_frames(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams& g, uint32_t n, size_t npts, const vofod_dyn_params& dp, bool no_update, vofod_handle::ClusterTables*& ct)
-{
-  // the clustering family is known up front, so the emission kernel can register the voxels in their bricks
-  VCHK(cluster_tables(h, g, static_cast<float>(dp.ground_points_max_distance), map_cmax(h), &ct));
-  g.sparse_prefix = want_bricks(ct, ws) ? 1u : 0u;
-  // (Fusing the brick registration into k_emit was measured slower - 194 us vs 96 + 50 us for 32 frames: the returning
-  // atomicOr sits inside the load-balanced emission loop - so it stays a kernel of its own.)
-  const bool lds_plan = plan_lds_ccl(h, ct, ws, no_update && n >= 4);
-  h->lds_ccl_off = false;  // one-shot: only the re-run of the batch that overflowed stays off the LDS kernels
-  return launch_voxelize(h, ws, lf, g, n, static_cast<uint32_t>(npts), false, false, nullptr, lds_plan);
-}
-
 // staged pipeline: the chain moves from the streaming stage's stream to a frame stream
 int enter_frame_stream(vofod_handle* h, Workspace& ws)
 {
@@ -520,8 +503,8 @@ int enter_frame_stream(vofod_handle* h, Workspace& ws)
 // A single map-updating scan without debug output (the reference's own mode) clusters close first on the general path
 // (kernels_far.h): close bits from hasCloseTo's stencil with every voxel as its own cluster, then edges and unions around the
 // far voxels only - instead of the six brick kernels over the whole frame.
-int cluster_far_single(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridParams& g, const vofod_handle::ClusterTables* ct, const vofod_dyn_params& dp, const CloseParams& cpar,
-                       const UpdateParams& up, float thr_new)
+int cluster_far_single(vofod_handle* h, Workspace& ws, const vplan::ChainPlan& plan, const GridParams& g, const vofod_handle::ClusterTables* ct, const CloseParams& cpar, const UpdateParams& up,
+                       float thr_new)
 {
   const uint32_t gv = (ws.vox_cap + 255u) / 256u;
   uint32_t* far_list = ws.d_labels;  // (labels are not written on this path)
@@ -531,35 +514,31 @@ int cluster_far_single(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const Gr
   const uint32_t items = FAR_MAX * 2u * static_cast<uint32_t>(ct->n_rows);
   KLAUNCH(h, k_far_edges, dim3((items + 255u) / 256u), dim3(256), g, ct->cp, ct->d_rows, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va, far_list);
   KLAUNCH(h, k_far_final, dim3(1), dim3(1024), g, ws.d_hdrs, ws.va, far_list, up, ws.d_table, ws.d_cand);
-  // The occupancy image is patched where the update flips a bit (valid while one voxel of the scan falls into one map cell -
-  // the aligned lattice - and the flood fills' frontier value is no background value: their writes then flip nothing).
-  ws.mapbits_patched = g.align && static_cast<float>(dp.voxel_map__thresholds__frontiers) <= thr_new;
-  KLAUNCH(h, k_finalize_far, dim3(gv), dim3(256), g, h->mg, up, ws.d_hdrs, ws.va, h->d_map, h->d_flags, ws.d_bitmaps, ws.mapbits_patched ? h->d_mapbits : nullptr, h->d_bgcount, thr_new);
-  lf.closefar_fused = true;
-  lf.finalize_fused = true;
+  // The occupancy image is patched where the update flips a bit (plan.mapbits_patched: valid while one voxel of the scan falls into
+  // one map cell - the aligned lattice - and the flood fills' frontier value is no background value: their writes then flip nothing).
+  KLAUNCH(h, k_finalize_far, dim3(gv), dim3(256), g, h->mg, up, ws.d_hdrs, ws.va, h->d_map, h->d_flags, ws.d_bitmaps, plan.mapbits_patched ? h->d_mapbits : nullptr, h->d_bgcount, thr_new);
   return VOFOD_OK;
 }
 
 // ---- K8/K9 findCloseFarClusters :703-750 (tables and images were prepared before the chain was enqueued) and
 // ---- K10 updateVMaps :943-950 + cluster table + candidate members: whatever the clustering has not done already
-int closefar_and_finalize(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, const GridParams& g, uint32_t n, const CloseParams& cpar, const UpdateParams& up, bool use_dilated, bool keep_dirty,
-                          vofod_scan_debug* dbg, const DevEvent* ev)
+int closefar_and_finalize(vofod_handle* h, Workspace& ws, const vplan::ChainPlan& plan, const GridParams& g, const CloseParams& cpar, const UpdateParams& up, vofod_scan_debug* dbg, const DevEvent* ev)
 {
   const uint32_t gv = (ws.vox_cap + 255u) / 256u;
-  if (!lf.closefar_fused)
+  if (plan.closefar != vplan::CloseFar::Fused)
   {
     // few frames: the undecided voxels go through a list to a sweep kernel with 16 lanes per voxel (ws.d_cand is free until
     // k_finalize); many frames: swept in place
-    const bool split = n < 8 && !use_dilated;
-    KLAUNCH(h, k_closefar, fgrid(g, gv), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_labels, use_dilated ? h->d_mapclose : nullptr,
+    const bool split = plan.closefar == vplan::CloseFar::Split;
+    KLAUNCH(h, k_closefar, fgrid(g, gv), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_labels, plan.use_dilated ? h->d_mapclose : nullptr,
             split ? ws.d_cand : nullptr, ws.d_hdrs);
     if (split)
       KLAUNCH(h, k_closefar_sweep, fgrid(g, (ws.vox_cap * 16u + 255u) / 256u), dim3(256), g, h->mg, cpar, h->d_crows, ws.d_hdrs, h->d_mapbits, ws.va, ws.d_cand);
   }
   if (dbg)
     HIPCHK(hipEventRecord(ev[3], h->stream));
-  if (!lf.finalize_fused)
-    KLAUNCH(h, k_finalize, fgrid(g, gv), dim3(256), g, h->mg, up, ws.d_hdrs, ws.va, ws.d_labels, h->d_map, h->d_flags, ws.d_table, ws.d_cand, keep_dirty ? nullptr : ws.d_bitmaps);
+  if (plan.finalize == vplan::Finalize::Finalize)
+    KLAUNCH(h, k_finalize, fgrid(g, gv), dim3(256), g, h->mg, up, ws.d_hdrs, ws.va, ws.d_labels, h->d_map, h->d_flags, ws.d_table, ws.d_cand, plan.keep_dirty ? nullptr : ws.d_bitmaps);
   return VOFOD_OK;
 }
 
@@ -586,7 +565,7 @@ int raycast_ahead_of_tail(vofod_handle* h, Workspace& ws, FrameCall& call)
 // but the records.
 // (round 4: a single map-updating scan - the reference's own mode - takes the device tail too: no cluster table down, explore
 // jobs up, results down between the kernels; the flood fills then write their frontiers to the map itself, vofod_nodelet.cpp:1712-1715)
-int launch_device_tail(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, const LaunchRoute& rt, FrameCall& call)
+int launch_device_tail(vofod_handle* h, Workspace& ws, const vplan::ChainPlan& plan, const LaunchRoute& rt, FrameCall& call)
 {
   const uint32_t n = call.n;
   const GridParams& g = call.g;
@@ -615,16 +594,16 @@ int launch_device_tail(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, co
   else
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_explore, 0));  // (a synchronous call: wait for the tails of batches in flight)
   const vt::TailParams tp = tail_params(h, dp);
-  const vc::ExploreParams ep = explore_params(dp, static_cast<float>(dp.voxel_map__thresholds__new_obstacles), rt.no_update);
+  const vc::ExploreParams ep = explore_params(dp, static_cast<float>(dp.voxel_map__thresholds__new_obstacles), plan.no_update);
   // the records (135 KB) go straight into the pinned host slots from the last tail kernel: no copy command on any stream (see k_tail_finish)
   static const bool diag_no_tail = std::getenv("VOFOD_DIAG_NO_TAIL") != nullptr;  // (diagnostics: timing of the pipeline without the tail kernel - results are wrong)
   if (diag_no_tail && n >= 128u)
     ;
-  else if ((lf.far_ran && ws.close_first == 1) || call.far_single)
+  else if (plan.tail == vplan::Tail::Far)
     // close-first frames: ordered lists from the frame kernel (or k_far_final), the whole tail in one kernel of one wave per frame
     KLAUNCH(h, vtd::k_tail_far, dim3((n + vtd::TAIL_WPB - 1) / vtd::TAIL_WPB), dim3(64 * vtd::TAIL_WPB), g, ws.d_hdrs, ws.d_args, ws.d_table, ws.d_cand, ws.va, h->mg, tp, ep, eb.d_jobs, eb.d_members, h->d_map, eb.d_overlay, eb.d_stack, eb.d_explored, eb.d_touched,
-            eb.d_ovl_list, eb.d_ovl_count, eb.d_results, eb.d_visited, ws.d_dets, ws.h_dets_dev, call.far_single ? ws.d_tailc : static_cast<vtd::TailCluster*>(nullptr),
-            (ws.prof_deferred && h->d_prof_ccl && !call.far_single) ? h->d_prof_ccl + 32 * static_cast<size_t>(ws.prof_slot0) : static_cast<unsigned long long*>(nullptr));
+            eb.d_ovl_list, eb.d_ovl_count, eb.d_results, eb.d_visited, ws.d_dets, ws.h_dets_dev, plan.far_single ? ws.d_tailc : static_cast<vtd::TailCluster*>(nullptr),
+            (ws.prof_deferred && h->d_prof_ccl && !plan.far_single) ? h->d_prof_ccl + 32 * static_cast<size_t>(ws.prof_slot0) : static_cast<unsigned long long*>(nullptr));
   else
   {
     KLAUNCH(h, vtd::k_tail_prep, dim3(n), dim3(vtd::TP_THREADS), g, ws.d_hdrs, ws.d_args, ws.d_table, ws.d_cand, ws.va, h->mg, tp, eb.d_jobs, ws.d_job_be, ws.d_job_be + ws.F, eb.d_members, ws.d_tailc,
@@ -640,7 +619,9 @@ int launch_device_tail(vofod_handle* h, Workspace& ws, const LaunchFlags& lf, co
 }
 
 // The launch half.  `call` is filled for the collect half of a synchronous call; a submitted batch leaves what its collect
-// half needs in the workspace (pending, job_n, job_g, job_tfs, job_scans, job_dp, dtail, ev_done).
+// half needs in the workspace (pending, job_n, job_g, job_tfs, job_scans, job_dp, plan, ev_done).
+// The kernel chain is decided once, by plan_chain (chain_plan.h), when everything it depends on is known - the staged inputs,
+// the cluster tables, the latches - and before the first kernel of the chain is enqueued; the stages below execute the plan.
 int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
 {
   const vofod_static_params& sp = h->sp;
@@ -679,13 +660,11 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
       HIPCHK(ev[i].create(hipEventCreate));
   const float thr_new = static_cast<float>(dp.voxel_map__thresholds__new_obstacles);
 
-  // ---- the routing decisions that do not depend on the frames
+  // ---- the switches, read once per call; where the chain goes (the streams of a submitted launch)
+  const vplan::Switches sw = vplan::read_switches();
+  const bool no_update = call.flags & VOFOD_SCAN_NO_MAP_UPDATE;
+  const bool use_dilated = vplan::wants_dilated(sw, no_update, n);  // (the one decision the map images need ahead of the plan)
   LaunchRoute rt;
-  const bool no_update = rt.no_update = call.flags & VOFOD_SCAN_NO_MAP_UPDATE;
-  rt.use_dilated = !switch_off("VOFOD_DILATE") && no_update && n >= 4;  // (VOFOD_DILATE=0: stencil sweep)
-  rt.single_update = !no_update && n == 1 && !submitted;
-  const bool dtail_on = !switch_off("VOFOD_DEVICE_TAIL");
-  rt.dtail = dtail_on && !dbg && ((n >= 4 && no_update) || rt.single_update);
   if (submitted)
     VCHK(route_submitted(h, ws, n, rt));
   StreamScope chain_scope(h, rt.chain);
@@ -723,59 +702,76 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   h->hg.idxToCoord(zero, align_center);  // :664
   fill_grid_params(h, g, leaf, true, align_center, ws);
   CloseParams cpar{};
-  VCHK(prepare_map_images(h, dp, thr_new, rt.use_dilated, !h->background_pts_sufficient || dbg, cpar));
+  VCHK(prepare_map_images(h, dp, thr_new, use_dilated, !h->background_pts_sufficient || dbg, cpar));
   if (dbg)
     HIPCHK(hipEventRecord(ev[0], h->stream));
-  LaunchFlags lf;
-  vofod_handle::ClusterTables* ct = nullptr;
-  VCHK(voxelize_frames(h, ws, lf, g, n, npts, dp, no_update, ct));
-  if (dbg)
-    HIPCHK(hipEventRecord(ev[1], h->stream));
-  if (rt.staged)
-    VCHK(enter_frame_stream(h, ws));
 
-  // ---- K7 clusterCloud :932
-  UpdateParams up{};
-  up.score_point = static_cast<float>(dp.voxel_map__scores__point);
-  up.score_unknown = static_cast<float>(dp.voxel_map__scores__unknown);
-  up.min_points = dp.classification__min_points;
-  up.cand_max_extent = static_cast<float>(dp.classification__max_size * (1.0 + 1e-4) + 1e-3 * sp.voxel_size);
-  up.no_update = no_update;
-  // k_slab rewrites the bitmap densely and the brick clustering reads it at set bits only: no need to clean it after use;
-  // then the LDS clustering kernel can write the cluster table and the candidate list itself (nothing left for k_finalize)
-  const bool frame_path = lf.frame_fused;  // brick-first frame kernel: the global occupancy bitmaps are not touched at all
-  const bool bitmap_was_clean = ws.bitmap_clean;
-  const bool keep_dirty = frame_path || (lf.slab_bitmap && g.sparse_prefix);
-  // Read-only batches cluster close first (k_frame_lds): only the far clusters are ever used (vofod_nodelet.cpp:946-963).  The
-  // debug view of ALL clusters keeps the full clustering; dbg[0].far_only asks for the production path's view instead.
-  // VOFOD_CLOSE_FIRST=0: the full clustering everywhere.
-  const bool close_first_on = !switch_off("VOFOD_CLOSE_FIRST");
-  const bool dbg_far_only = dbg && dbg[0].far_only;
+  // ---- the plan (chain_plan.h): its inputs, gathered; the two latches as they stand now
+  vofod_handle::ClusterTables* ct = nullptr;
+  VCHK(cluster_tables(h, g, static_cast<float>(dp.ground_points_max_distance), map_cmax(h), &ct));
+  const bool rerun_off_lds = h->lds_ccl_off;
+  h->lds_ccl_off = false;  // one-shot: only the re-run of the batch that overflowed stays off the LDS kernels
   // (the release bound is tested against the count of the map as it is NOW: a map image rebuilt for this call - vofod_write_map, a
   // scan through the full clustering - has its count still on the way, n_bg_voxels is the previous map's until it is fetched)
   if (h->cf_off)
     VCHK(latch_background(h));
   if (h->cf_off && (h->n_bg_voxels > h->cf_off_bg + h->cf_off_bg / 4 + 1000 || h->n_bg_voxels < h->cf_off_bg))
     h->cf_off = false;  // the map has changed a lot since: try the close-first kernel again
-  ws.close_first = (close_first_on && rt.use_dilated && !h->cf_off) ? (dbg ? (dbg_far_only ? 2 : 0) : 1) : 0;
-  call.far_single = close_first_on && !h->cf_off && !dbg && rt.single_update && dtail_on && !frame_path && !keep_dirty && ct->n_rows > 0 && ws.vox_cap >= FAR_MAX;
-  if (call.far_single)
-    VCHK(cluster_far_single(h, ws, lf, g, ct, dp, cpar, up, thr_new));
+  vplan::PlanInputs in = plan_inputs(h, ws, ct, sw);
+  in.lds_ccl_off = rerun_off_lds;
+  in.n = n;
+  in.no_update = no_update;
+  in.submitted = submitted;
+  in.dbg = dbg != nullptr;
+  in.dbg_far_only = dbg && dbg[0].far_only;
+  in.auto_raycast = call.flags & VOFOD_SCAN_AUTO_RAYCAST;
+  const RefLattice ref_lattice = fill_ref_lattice(g);  // the frame kernel's bricks and cell codes refer to it
+  in.ref_lattice_on = ref_lattice.on != 0;
+  in.layout_packed = true;  // packed, 16-byte aligned float columns, a multiple of 4 points each: the frame kernel's input pass uses 16-byte loads
+  for (uint32_t f = 0; f < n && in.layout_packed; f++)
+  {
+    const FrameArgs& a = ws.h_args[f];
+    in.layout_packed = a.stride == 4 && (a.n & 3u) == 0 && a.n >= 4 && ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.z)) & 15u) == 0;
+  }
+  in.patchable = g.align && static_cast<float>(dp.voxel_map__thresholds__frontiers) <= thr_new;
+  const vplan::ChainPlan& plan = ws.plan = vplan::plan_chain(in);
+  if (trace_on())
+    std::fprintf(stderr, "[vofod trace] n=%u plan: %s, %s, %s, %s, %s\n", n, name(plan.voxeliser), name(plan.clusterer), name(plan.closefar), name(plan.finalize), name(plan.tail));
+  g.sparse_prefix = plan.bricks ? 1u : 0u;
+
+  // ---- K1-K6 (filterAndTransform :621-684) - or only what the frame kernel, which reads the input itself, needs ahead of it
+  VCHK(launch_voxelize(h, ws, plan, g, n, static_cast<uint32_t>(npts)));
+  if (dbg)
+    HIPCHK(hipEventRecord(ev[1], h->stream));
+  if (rt.staged)
+    VCHK(enter_frame_stream(h, ws));
+
+  // ---- K7 clusterCloud :932.  Read-only batches cluster close first (k_frame_lds): only the far clusters are ever used
+  // (vofod_nodelet.cpp:946-963).  The debug view of ALL clusters keeps the full clustering; dbg[0].far_only asks for the
+  // production path's view instead.
+  UpdateParams up{};
+  up.score_point = static_cast<float>(dp.voxel_map__scores__point);
+  up.score_unknown = static_cast<float>(dp.voxel_map__scores__unknown);
+  up.min_points = dp.classification__min_points;
+  up.cand_max_extent = static_cast<float>(dp.classification__max_size * (1.0 + 1e-4) + 1e-3 * sp.voxel_size);
+  up.no_update = no_update;
+  if (plan.far_single)
+    VCHK(cluster_far_single(h, ws, plan, g, ct, cpar, up, thr_new));
+  else if (plan.frame())
+    VCHK(launch_frame_kernel(h, ws, plan, g, n, ct, ref_lattice, up));
   else
-    VCHK(launch_cluster(h, ws, lf, g, n, static_cast<float>(dp.ground_points_max_distance), map_cmax(h), rt.use_dilated ? h->d_mapclose : nullptr,
-                        (keep_dirty && no_update) ? &up : nullptr));
+    VCHK(launch_cluster(h, ws, plan, g, ct));
   if (dbg)
     HIPCHK(hipEventRecord(ev[2], h->stream));
-  VCHK(closefar_and_finalize(h, ws, lf, g, n, cpar, up, rt.use_dilated, keep_dirty, dbg, ev));
-  ws.bitmap_clean = frame_path ? bitmap_was_clean : !keep_dirty;
+  VCHK(closefar_and_finalize(h, ws, plan, g, cpar, up, dbg, ev));
+  ws.bitmap_clean = plan.bitmap_clean_after;
 
   // ---- the tail on the device, or the read-back of what the host tail needs
-  ws.dtail = rt.dtail;
   call.tail_stream_used = h->stream;
-  if (rt.dtail && rt.single_update && (call.flags & VOFOD_SCAN_AUTO_RAYCAST))
+  if (plan.raycast_ahead)
     VCHK(raycast_ahead_of_tail(h, ws, call));
-  if (rt.dtail)
-    VCHK(launch_device_tail(h, ws, lf, rt, call));
+  if (plan.dtail)
+    VCHK(launch_device_tail(h, ws, plan, rt, call));
   else
     VCHK(read_back_full(h, ws, g, n));
   if (dbg)
@@ -787,7 +783,7 @@ int launch_frames(vofod_handle* h, Workspace& ws, FrameCall& call)
   h2d_guard.armed = false;
   if (host_copies)
     HIPCHK(hipEventSynchronize(ws.ev_h2d));  // (the whole chain is enqueued by now: the device works while the host waits for the link)
-  HIPCHK(hipEventRecord(ws.ev_done, rt.dtail ? call.tail_stream_used : h->stream));
+  HIPCHK(hipEventRecord(ws.ev_done, plan.dtail ? call.tail_stream_used : h->stream));
   ws.pending = true;
   ws.job_n = n;
   ws.job_g = g;

@@ -79,6 +79,34 @@ __device__ __forceinline__ bool brick_pair_conn(const GridParams& g, const Brick
   return conn;
 }
 
+// register voxel `rank` (lattice cell i,j,k) in its 4x4x4 brick; returns true for the brick's first voxel
+__device__ __forceinline__ bool brick_mark(const FrameHdr& h, const BrickArrays& ba, int i, int j, int k, uint32_t rank, uint32_t& b)
+{
+  int bit;
+  b = brick_of(h, i, j, k, bit);
+  (void)rank;
+  return atomicOr(&ba.bricks[b], 1ull << bit) == 0ull;
+}
+
+// append the bricks whose first voxel sits in this wave to the frame's brick list: one counter atomic per wave
+__device__ __forceinline__ void brick_append(FrameHdr& h, const BrickArrays& ba, bool first, uint32_t b)
+{
+  const unsigned long long m = __ballot(first);
+  if (!m)
+    return;
+  const int lane = threadIdx.x & 63;
+  const int leader = __ffsll(static_cast<long long>(m)) - 1;
+  uint32_t base = 0;
+  if (lane == leader)
+    base = atomicAdd(&h.n_bricks, static_cast<uint32_t>(__popcll(m)));
+  base = __shfl(base, leader);
+  if (first)
+  {
+    ba.blist[base + __popcll(m & ((1ull << lane) - 1ull))] = b;
+    ba.bparent[b] = b;
+  }
+}
+
 // mark every voxel in its brick word; the first voxel of a brick registers it
 __global__ __launch_bounds__(256) void k_brick_set(const GridParams g, const BrickParams bp, FrameHdr* hdrs, VoxelArrays va_all, BrickArrays ba_all)
 {

@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "chain_plan.h"
 #include "common.h"
 #include "device_mem.h"
 #include "host_tail.h"
@@ -214,30 +215,6 @@ struct Prof
   } while (0)
 #define KLAUNCH(h, kern, grid, block, ...) KLAUNCH_AS(h, #kern, kern, grid, block, __VA_ARGS__)
 
-// VOFOD_<NAME>=0 switches a fast path off (README "Environment switches").  Read on every call, not cached: a dozen getenv per
-// batch cost ~1 us, and the tests flip the fallbacks inside one process (a `static const` here made every switch stick to
-// its first reading - and every in-process fallback test after the first call vacuous).
-inline bool switch_off(const char* name)
-{
-  const char* v = std::getenv(name);
-  return v && std::atoi(v) == 0;
-}
-
-// What the stages of ONE launch tell each other: created by the caller of launch_voxelize, handed on to launch_cluster and the
-// tail launch, dropped with the call.  Nothing here outlives a launch - the state of a pending ticket lives in Workspace.
-struct LaunchFlags
-{
-  RefLattice ref_lattice{};     // frame kernel: the reference lattice its bricks and cell codes refer to (on = 0: general kernels)
-  bool frame_fused = false;     // launch_voxelize planned the frame kernel: launch_cluster runs k_frame_lds (input pass, voxel records and clustering in one kernel)
-  bool in_packed = false;       // the batch's columns are packed, 16-byte aligned floats, a multiple of 4 points each: the frame kernel's input pass uses 16-byte loads
-  bool lean_emit = false;       // the per-root slots were left alone: launch_cluster must run the LDS clustering kernel
-  bool bricks_preset = false;   // k_emit already registered the voxels in their bricks (fused brick_set)
-  bool slab_bitmap = false;     // the current bitmaps were written by k_slab (dense, zeros included)
-  bool far_ran = false;         // launch_cluster ran k_frame_lds_far: the cluster table and the member list are in the order k_tail_far reads
-  bool finalize_fused = false;  // the clustering wrote the cluster table / candidate list too (nothing left for k_finalize)
-  bool closefar_fused = false;  // the clustering answered hasCloseTo as well (dilated image inside k_flatten / the frame kernel)
-};
-
 // A plain struct of pointers (what the kernels take by value; vr::SepState) cannot hold an owner: the owner stands beside it, and
 // the struct's member `v` is the view of the owner's allocation.
 template <class T>
@@ -252,7 +229,7 @@ struct Workspace
 {
   uint32_t F = 0, pt_cap = 0, vox_cap = 0, words_cap = 0, nblk_cap = 0, bricks_cap = 0;
   // BrickArrays, VoxelArrays, SlabArrays and FrameScratch go to the kernels by value: they hold plain pointers, and the storage
-  // behind every member has its owner here (sa.keys shares d_ptrank's)
+  // behind every member has its owner here (sa.keys is the view of d_keys)
   BrickArrays ba{};
   VoxelArrays va{};
   SlabArrays sa{};  // key list / extras of the LDS-slab voxelisation
@@ -270,7 +247,7 @@ struct Workspace
   DevBuf<uint32_t> d_labels;
   DevBuf<ClusterRec> d_table;
   DevBuf<CandMember> d_cand;
-  DevBuf<uint32_t> d_ptrank;
+  DevBuf<uint32_t> d_keys;  // per frame: the key list of the slab voxeliser, the code list of the frame kernel (fs.keys_cap entries)
   DevBuf<float> d_stage;  // F * pt_cap * 5 words: x, y, z, intensity, range of host-resident inputs
   DevBuf<char> d_stage_aos;  // host-resident array-of-structs clouds (the nodelet's 48-byte ouster_ros::Point) cross the link as they are:
   size_t aos_pitch = 0;      // F * aos_pitch bytes, allocated on first use; the kernels read x / y / z in place at the struct's stride
@@ -289,11 +266,9 @@ struct Workspace
   const float* first_poses = nullptr;  // the device copy of the pose table of the batch's FIRST scan (nullptr: it has none)
   DevBuf<PackedFrame> d_packed;
   PinBuf<PackedFrame> h_packed;
-  bool mapbits_patched = false;  // k_finalize_far kept the map's occupancy image and counters up to date with this scan's update
   bool prof_deferred = false;  // VOFOD_LDS_PROF=2: the frame kernel's stamps of this batch are printed when it is collected
   uint32_t prof_slot0 = 0;
-  int close_first = 0;  // k_frame_lds: 1 = cluster the far voxels only (read-only batches), 2 = the same with labels for the far-only debug view
-  bool dtail = false;  // ... or its classification tail ran on the device (kernels_tail.h): only detection records come back
+  vplan::ChainPlan plan;  // the kernel chain of the launch this workspace holds (chain_plan.h): what the collect half reads of it
   DevBuf<vtd::TailCluster> d_tailc;
   DevBuf<vtd::FrameDets> d_dets;
   PinBuf<vtd::FrameDets> h_dets;  // mapped, coherent
@@ -403,10 +378,10 @@ private:
     HIP_TRY(d_cand.alloc(FV));
     // (the frame kernel's code list: every wave of a frame's workgroup appends to a segment of its own - whole rounds of the input pass)
     fs.keys_cap = (pt_cap_ + IN_SEG_ALIGN - 1u) / IN_SEG_ALIGN * IN_SEG_ALIGN;
-    HIP_TRY(d_ptrank.alloc(static_cast<size_t>(F_) * fs.keys_cap));
+    HIP_TRY(d_keys.alloc(static_cast<size_t>(F_) * fs.keys_cap));
     HIP_TRY(alloc_view(sa_extras, sa.extras, static_cast<size_t>(F_) * pt_cap_));
     HIP_TRY(alloc_view(sa_counts, sa.counts, 2 * static_cast<size_t>(F_)));
-    sa.keys = d_ptrank;
+    sa.keys = d_keys;
     HIP_TRY(d_stage.alloc(5 * static_cast<size_t>(F_) * pt_cap_));
     HIP_TRY(d_rjobs.alloc(F_));
     HIP_TRY(h_rjobs.alloc(F_));
@@ -583,6 +558,8 @@ struct vofod_handle
   bool sep_pending = false;
   int sep_start_its = 0;
 };
+
+#include "frame_prof.h"
 
 namespace
 {
@@ -1068,7 +1045,7 @@ RefLattice fill_ref_lattice(const GridParams& g)
 }
 
 // K3-K6 of the general voxeliser through the global occupancy bitmaps: bitmap (cleared first where `clear`) -> ranks -> weighted cloud
-int launch_bitmap_chain(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t n, uint32_t max_pts, bool clear, const BrickParams& bpv, int emit_bricks, uint32_t lean_bit, bool want_ptrank)
+int launch_bitmap_chain(vofod_handle* h, Workspace& ws, const GridParams& g, uint32_t n, uint32_t max_pts, bool clear)
 {
   const uint32_t gx = std::max(1u, std::min((max_pts + 255u) / 256u, 1024u));
   if (clear)
@@ -1077,145 +1054,76 @@ int launch_bitmap_chain(vofod_handle* h, Workspace& ws, const GridParams& g, uin
   KLAUNCH(h, k_setbits, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps);
   KLAUNCH(h, k_scan_a, fgrid(g, ws.nblk_cap), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap);
   KLAUNCH(h, k_scan_b, dim3(n), dim3(1024), g, ws.d_hdrs, ws.d_blocksums, ws.nblk_cap);
-  KLAUNCH(h, k_emit, fgrid(g, ws.nblk_cap * emit_split(n)), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap, ws.d_wprefix, ws.va, bpv, ws.ba, emit_bricks, lean_bit, emit_split(n));
-  KLAUNCH(h, k_count, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va, want_ptrank ? ws.d_ptrank : nullptr, ws.pt_cap);
+  KLAUNCH(h, k_emit, fgrid(g, ws.nblk_cap * emit_split(n)), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap, ws.d_wprefix, ws.va, 0u, emit_split(n));
+  KLAUNCH(h, k_count, fgrid(g, gx), dim3(256), ws.d_args, g, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va);
   HIPCHK(hipGetLastError());
   return VOFOD_OK;
 }
 
-// kernel chain K1-K6 over frames [0,n): bbox -> lattice -> occupancy bitmap -> ranks -> weighted cloud
-int launch_voxelize(vofod_handle* h, Workspace& ws, LaunchFlags& lf, GridParams& g, uint32_t n, uint32_t max_pts, bool want_ptrank, bool two_phase, const BrickParams* bricks = nullptr,
-                    bool lean_hint = false)
+// the frames' arguments and fresh headers: all the frame kernel (kernels_frame.h), which reads the input itself, needs ahead of it
+int launch_frame_args(vofod_handle* h, Workspace& ws, GridParams& g, uint32_t n)
 {
-  BrickParams bpv{};
-  if (bricks)
-    bpv = *bricks;
-  bpv.bricks_cap = ws.bricks_cap;
-  lf.bricks_preset = bricks != nullptr;
   g.n_frames = n;
-  // lean emission: the LDS clustering kernel will follow and initialises the per-root slots itself (see plan_lds_ccl)
-  lf.lean_emit = lean_hint && !bricks && !two_phase;
   HIPCHK(hipMemcpyAsync(ws.d_args, ws.h_args.data(), sizeof(FrameArgs) * n, hipMemcpyHostToDevice, h->stream));
-  const uint32_t gb = std::max(1u, std::min((max_pts + 2047u) / 2048u, 1024u));  // 8 points per thread: few header atomics
-  // Batches whose clustering will run inside LDS (plan_lds_ccl): the brick-first frame kernel (kernels_frame.h) reads the input
-  // itself (round 5; rounds 2-4 had a streaming kernel in front, k_key1, which is gone), builds the voxel records and clusters them on the same LDS
-  // image - launched by launch_cluster.  It needs the batch's reference lattice (bricks of the operation area's lattice in the
-  // LDS bitmap); where that does not fit, the general kernels below take the batch.
-  bool frame_plan = lf.lean_emit && n >= 4 && !want_ptrank && !two_phase;
-  if (frame_plan)
-  {
-    lf.ref_lattice = fill_ref_lattice(g);
-    frame_plan = lf.ref_lattice.on != 0;
-  }
-  if (!frame_plan)
-    lf.lean_emit = false;  // the general emission kernels initialise every per-voxel slot; the global clustering kernels follow
-  const uint32_t lean_bit = lf.lean_emit ? 0x80000000u : 0u;
   KLAUNCH(h, k_init_hdr, dim3(n), dim3(64), ws.d_hdrs);
-  if (frame_plan)
+  return VOFOD_OK;
+}
+
+// K1-K2 over frames [0,n): bbox -> lattice.  (A cloud voxelisation inspects the lattice's size before the bitmap is touched.)
+int launch_lattice(vofod_handle* h, Workspace& ws, GridParams& g, uint32_t n, uint32_t max_pts)
+{
+  VCHK(launch_frame_args(h, ws, g, n));
+  const uint32_t gb = std::max(1u, std::min((max_pts + 2047u) / 2048u, 1024u));  // 8 points per thread: few header atomics
+  KLAUNCH(h, k_bbox, fgrid(g, gb), dim3(256), ws.d_args, g, ws.d_hdrs);
+  KLAUNCH(h, k_grid, dim3(n), dim3(64), g, ws.d_hdrs);
+  return VOFOD_OK;
+}
+
+// K1-K6 over frames [0,n) as planned: the general voxelisers - or, for the frame kernel (launched by launch_frame_kernel: input
+// pass, voxel records and clustering on one LDS image; rounds 2-4 had a streaming kernel in front, k_key1, which is gone), only
+// what it needs ahead of it
+int launch_voxelize(vofod_handle* h, Workspace& ws, const vplan::ChainPlan& plan, GridParams& g, uint32_t n, uint32_t max_pts)
+{
+  if (plan.frame())
   {
-    bool packed = true;
-    for (uint32_t f = 0; f < n && packed; f++)
-    {
-      const FrameArgs& a = ws.h_args[f];
-      packed = a.stride == 4 && (a.n & 3u) == 0 && a.n >= 4 && ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.z)) & 15u) == 0;
-    }
-    lf.in_packed = packed;
+    VCHK(launch_frame_args(h, ws, g, n));
     if (!h->ev_stagger)
       HIPCHK(h->ev_stagger.create(hipEventCreateWithFlags, hipEventDisableTiming));
     HIPCHK(hipEventRecord(h->ev_stagger, h->stream));  // the next batch's chain may start now
     h->ev_stagger_set = true;
-    lf.frame_fused = true;
     HIPCHK(hipGetLastError());
     return VOFOD_OK;
   }
-  KLAUNCH(h, k_bbox, fgrid(g, gb), dim3(256), ws.d_args, g, ws.d_hdrs);
-  KLAUNCH(h, k_grid, dim3(n), dim3(64), g, ws.d_hdrs);
-  if (two_phase)
-    return VOFOD_OK;  // caller inspects the lattice size before the bitmap is touched
-  // Lattices of at most SLAB_MAX slabs of 1 Mi cells: the bitmap is built slab by slab in LDS (kernels_slab.h).
-  // VOFOD_SLABS=0 keeps the global-atomic kernels (also used for the counted grid, which needs every point's rank).
-  const bool slabs_on = !switch_off("VOFOD_SLABS");
-  constexpr uint32_t SLAB_MAX = 32;
-  const uint32_t n_slabs = (ws.words_cap + SLAB_WORDS64 - 1) / SLAB_WORDS64;
-  if (slabs_on && n >= 4 && !want_ptrank && !bricks && n_slabs <= SLAB_MAX)  // a single frame is served faster by the whole chip through the global bitmap
+  VCHK(launch_lattice(h, ws, g, n, max_pts));
+  if (plan.voxeliser == vplan::Voxeliser::Bitmap)
+    return launch_bitmap_chain(h, ws, g, n, max_pts, plan.clear_bitmap);
+  // the bitmap is built slab by slab in LDS (kernels_slab.h)
+  if (plan.clear_bitmap)
+    HIPCHK(hipMemsetAsync(ws.d_bitmaps, 0, sizeof(unsigned long long) * ws.F * (static_cast<size_t>(ws.words_cap) + 2), h->stream));
+  HIPCHK(hipMemsetAsync(ws.sa.counts, 0, sizeof(uint32_t) * 2 * n, h->stream));
+  const uint32_t gk = std::max(1u, (max_pts + KEY_THREADS * KEY_PPT - 1) / (KEY_THREADS * KEY_PPT));
+  KLAUNCH(h, k_key, fgrid(g, gk), dim3(KEY_THREADS), ws.d_args, g, ws.d_hdrs, ws.sa, ws.pt_cap);
+  ws.bitmap_clean = false;
+  const bool slab_emit = plan.voxeliser == vplan::Voxeliser::SlabEmit;
+  if (slab_emit)
   {
-    lf.slab_bitmap = true;
-    if (!ws.bitmap_clean && !g.sparse_prefix)  // voxel-level clustering: neighbour windows run into the words past the lattice, they must read as zero
-      HIPCHK(hipMemsetAsync(ws.d_bitmaps, 0, sizeof(unsigned long long) * ws.F * (static_cast<size_t>(ws.words_cap) + 2), h->stream));
-    HIPCHK(hipMemsetAsync(ws.sa.counts, 0, sizeof(uint32_t) * 2 * n, h->stream));
-    const uint32_t gk = std::max(1u, (max_pts + KEY_THREADS * KEY_PPT - 1) / (KEY_THREADS * KEY_PPT));
-    KLAUNCH(h, k_key, fgrid(g, gk), dim3(KEY_THREADS), ws.d_args, g, ws.d_hdrs, ws.sa, ws.pt_cap);
-    // VOFOD_SLAB_EMIT=0 keeps the separate emission kernels for every batch size
-    const bool slab_emit_on = !switch_off("VOFOD_SLAB_EMIT");
-    ws.bitmap_clean = false;
-    DevBuf<unsigned long long>& d_prof_se = h->d_prof_slab;  // VOFOD_LDS_PROF=1 (diagnostics): per-handle stamp buffer
-    if (!d_prof_se && std::getenv("VOFOD_LDS_PROF"))
-      HIPCHK(d_prof_se.alloc(16 * 4096));
-    if (slab_emit_on && n >= 128)
-    {
-      // batches that fill the chip: one workgroup per frame walks the slabs in order and emits the voxel records itself
-      KLAUNCH(h, k_slab_emit, dim3(n), dim3(SLAB_THREADS), g, ws.d_hdrs, ws.sa, ws.pt_cap, ws.d_bitmaps, ws.d_wprefix, ws.va, 1u | lean_bit, d_prof_se);
-      if (d_prof_se)
-      {
-        unsigned long long t[16];
-        HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipMemcpy(t, d_prof_se, sizeof(t), hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "[k_slab_emit] keys %.1f | zero %.1f mark %.1f count+scan %.1f out+emit %.1f us (all slabs of frame 0)\n", t[0] * 0.01, t[1] * 0.01, t[2] * 0.01, t[3] * 0.01, t[4] * 0.01);
-        std::vector<unsigned long long> all(16 * n);
-        HIPCHK(hipMemcpy(all.data(), d_prof_se, sizeof(unsigned long long) * 16 * n, hipMemcpyDeviceToHost));
-        unsigned long long t0 = ~0ull, t1 = 0;
-        double dmin = 1e9, dmax = 0, dsum = 0, smax = 0;
-        for (uint32_t f = 0; f < n; f++)
-        {
-          t0 = std::min(t0, all[16 * f + 5]);
-          t1 = std::max(t1, all[16 * f + 6]);
-        }
-        for (uint32_t f = 0; f < n; f++)
-        {
-          const double d = (all[16 * f + 6] - all[16 * f + 5]) * 0.01;
-          dmin = std::min(dmin, d);
-          dmax = std::max(dmax, d);
-          dsum += d;
-          smax = std::max(smax, (all[16 * f + 5] - t0) * 0.01);
-        }
-        {
-          std::vector<std::pair<double, uint32_t>> byd;
-          for (uint32_t f = 0; f < n; f++)
-            byd.push_back({(all[16 * f + 6] - all[16 * f + 5]) * 0.01, f});
-          std::sort(byd.begin(), byd.end());
-          for (size_t q : {size_t(0), byd.size() / 4, byd.size() / 2, 3 * byd.size() / 4, byd.size() - 1})
-          {
-            const uint32_t f = byd[q].second;
-            std::fprintf(stderr, "[k_slab_emit]   frame %u: %.1f us, keys %llu, zero %.1f mark %.1f count %.1f emit %.1f\n", f, byd[q].first, all[16 * f + 7], all[16 * f + 1] * 0.01, all[16 * f + 2] * 0.01,
-                         all[16 * f + 3] * 0.01, all[16 * f + 4] * 0.01);
-          }
-        }
-        std::fprintf(stderr, "[k_slab_emit] %u workgroups: span %.1f us, per-workgroup min %.1f mean %.1f max %.1f us, latest start +%.1f us\n", n, (t1 - t0) * 0.01, dmin, dsum / n, dmax, smax);
-      }
-    }
-    else
-    {
-      // workgroups per frame: all slabs in parallel for small batches, fewer workgroups walking several slabs otherwise
-      const uint32_t slab_g = n <= 32 ? n_slabs : std::max(1u, std::min(n_slabs, 512u / n));
-      KLAUNCH(h, k_slab, fgrid(g, slab_g), dim3(SLAB_THREADS), g, ws.d_hdrs, ws.sa, ws.pt_cap, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap);
-      KLAUNCH(h, k_scan_b, dim3(n), dim3(1024), g, ws.d_hdrs, ws.d_blocksums, ws.nblk_cap);
-      KLAUNCH(h, k_emit, fgrid(g, ws.nblk_cap * emit_split(n)), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap, ws.d_wprefix, ws.va, bpv, ws.ba, 0, 1u | lean_bit, emit_split(n));
-    }
-    // after k_slab_emit only the extras beyond its LDS staging area are left (none on ordinary scans)
-    KLAUNCH(h, k_count_extras, fgrid(g, (slab_emit_on && n >= 128) ? 4 : 24), dim3(256), g, ws.d_hdrs, ws.sa, ws.pt_cap, ws.d_bitmaps, ws.d_wprefix, ws.va);
-    HIPCHK(hipGetLastError());
-    return VOFOD_OK;
+    // batches that fill the chip: one workgroup per frame walks the slabs in order and emits the voxel records itself
+    unsigned long long* d_prof = nullptr;
+    VCHK(slab_emit_prof_buffer(h, d_prof));
+    KLAUNCH(h, k_slab_emit, dim3(n), dim3(SLAB_THREADS), g, ws.d_hdrs, ws.sa, ws.pt_cap, ws.d_bitmaps, ws.d_wprefix, ws.va, 1u, d_prof);
+    if (d_prof)
+      VCHK(print_slab_emit_prof(h, n));
   }
-  return launch_bitmap_chain(h, ws, g, n, max_pts, !ws.bitmap_clean, bpv, bricks ? 1 : 0, lean_bit, want_ptrank);
-}
-
-// the second phase of a two-phase voxelisation (the caller has inspected the lattice k_bbox / k_grid found)
-int launch_voxelize_rest(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridParams& g, uint32_t n, uint32_t max_pts, bool want_ptrank)
-{
-  BrickParams bpv{};
-  bpv.bricks_cap = ws.bricks_cap;
-  lf.bricks_preset = false;  // (two-phase voxelisation never registers bricks in k_emit)
-  return launch_bitmap_chain(h, ws, g, n, max_pts, true, bpv, 0, 0u, want_ptrank);
+  else
+  {
+    KLAUNCH(h, k_slab, fgrid(g, plan.slab_groups), dim3(SLAB_THREADS), g, ws.d_hdrs, ws.sa, ws.pt_cap, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap);
+    KLAUNCH(h, k_scan_b, dim3(n), dim3(1024), g, ws.d_hdrs, ws.d_blocksums, ws.nblk_cap);
+    KLAUNCH(h, k_emit, fgrid(g, ws.nblk_cap * emit_split(n)), dim3(256), g, ws.d_hdrs, ws.d_bitmaps, ws.d_blocksums, ws.nblk_cap, ws.d_wprefix, ws.va, 1u, emit_split(n));
+  }
+  // after k_slab_emit only the extras beyond its LDS staging area are left (none on ordinary scans)
+  KLAUNCH(h, k_count_extras, fgrid(g, slab_emit ? 4 : 24), dim3(256), g, ws.d_hdrs, ws.sa, ws.pt_cap, ws.d_bitmaps, ws.d_wprefix, ws.va);
+  HIPCHK(hipGetLastError());
+  return VOFOD_OK;
 }
 
 // Stencil / brick tables of a clustering problem, cached per (leaf, tolerance, coordinate bound).
@@ -1293,265 +1201,83 @@ int cluster_tables(vofod_handle* h, const GridParams& g, float tol, float cmax, 
   return VOFOD_OK;
 }
 
-// brick-level clustering is used when a 4x4x4 brick is a clique for the tolerance; VOFOD_CCL=voxel forces the
-// voxel-level kernels (the tests compare both families against the oracle)
-bool want_bricks(const vofod_handle::ClusterTables* ct, const Workspace& ws)
+// What plan_chain (chain_plan.h) takes from the handle, a workspace and the cached cluster tables.  The call, the reference
+// lattice, the layout of the staged inputs and `patchable` are the caller's to add.
+vplan::PlanInputs plan_inputs(const vofod_handle* h, const Workspace& ws, const vofod_handle::ClusterTables* ct, const vplan::Switches& sw)
 {
-  const char* force = std::getenv("VOFOD_CCL");
-  if (force && std::strcmp(force, "voxel") == 0)
-    return false;
-  return ct->brick_ok && ws.bricks_cap > 0;
+  vplan::PlanInputs in;
+  in.sw = sw;
+  in.vox_cap = ws.vox_cap;
+  in.words_cap = ws.words_cap;
+  in.bricks_cap = ws.bricks_cap;
+  in.bitmap_clean = ws.bitmap_clean;
+  in.brick_ok = ct->brick_ok;
+  in.lds_ok = ct->lds_ok;
+  in.n_off = ct->bp.n_off;
+  in.pair_table = ct->d_pair.p != nullptr;
+  in.n_rows = ct->n_rows;
+  in.cf_off = h->cf_off;
+  in.lds_ccl_off = h->lds_ccl_off;
+  in.far_max = FAR_MAX;
+  in.lb_max = LB_MAX;
+  in.slab_words64 = SLAB_WORDS64;
+  return in;
 }
 
-// Will launch_cluster run the LDS-resident brick clustering (kernels_brick_lds.h) for this batch?  k_emit then leaves the
-// per-root statistics slots to that kernel.  VOFOD_BRICK_LDS=0 keeps the global-memory kernels.
-bool plan_lds_ccl(const vofod_handle* h, const vofod_handle::ClusterTables* ct, const Workspace& ws, bool allow_lds)
+// The plan of a clustering on its own (vofod_cluster, the sepclusters role): one frame whose map-updating caller reads the
+// labels of every cluster - the general kernels, brick or voxel level.
+vplan::ChainPlan plan_cluster_only(const vofod_handle* h, const Workspace& ws, const vofod_handle::ClusterTables* ct)
 {
-  const bool lds_on = !switch_off("VOFOD_BRICK_LDS");
-  return allow_lds && lds_on && want_bricks(ct, ws) && ct->lds_ok && !h->lds_ccl_off;
+  vplan::PlanInputs in = plan_inputs(h, ws, ct, vplan::read_switches());
+  in.n = 1;
+  in.dbg = true;
+  return vplan::plan_chain(in);
 }
 
-// VOFOD_LDS_PROF (diagnostics): phase durations of the frame kernel's workgroups from the 100 MHz wall clock stamps in slots
-// [s0, s0 + cnt) of the handle's stamp buffer.  =1: after every launch (the stream is synchronised: one batch at a time); =2: when the
-// batch is collected (batches in flight keep their own slots: the phases as they last in the pipeline).
-int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
+// K1-K7 in one kernel: the brick-first frame kernel (kernels_frame.h) reads the input itself, builds the voxel records and
+// clusters them on the same LDS image - the far voxels only where the plan says close first (read-only batches: only the far
+// clusters are ever used, vofod_nodelet.cpp:946-963).  Four instantiations: close first or not, packed 16-byte column loads or
+// strided ones; the profile names the algorithmic variant, k_frame_lds_far / k_frame_lds_full, and the strided input pass by
+// the suffix _strided.
+int launch_frame_kernel(vofod_handle* h, Workspace& ws, const vplan::ChainPlan& plan, const GridParams& g, uint32_t n, const vofod_handle::ClusterTables* ct, const RefLattice& ref_lattice,
+                        const UpdateParams& up)
 {
-  unsigned long long* d_prof = h->d_prof_ccl;
-  std::vector<unsigned long long> t(32 * cnt);
-  if (sync)
-    HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemcpy(t.data(), d_prof + 32 * static_cast<size_t>(s0), sizeof(unsigned long long) * 32 * cnt, hipMemcpyDeviceToHost));
-  if (const char* rawf = std::getenv("VOFOD_LDS_PROF_RAW"))
-  {
-    // raw mode: nothing is formatted while the pipeline runs (the JSON table below costs the host ~100 us per launch: 840 k instead
-    // of 950 k frames/s) - every frame's start, end and CU are kept and written to the named file when the process ends
-    // (tools/cu_gaps.py lays the frames of every CU end to end)
-    struct RawLog
-    {
-      std::vector<unsigned long long> v;  // launch, start, end, hw id per frame
-      std::string path;
-      uint64_t launch = 0;
-      ~RawLog()
-      {
-        if (FILE* fp = std::fopen(path.c_str(), "w"))
-        {
-          for (size_t i = 0; i + 3 < v.size(); i += 4)
-            std::fprintf(fp, "%llu %.2f %.2f %u %u %u %u\n", v[i], v[i + 1] * 0.01, v[i + 2] * 0.01, static_cast<unsigned>(v[i + 3] >> 32) & 15u, static_cast<unsigned>(v[i + 3] >> 13) & 7u,
-                         static_cast<unsigned>(v[i + 3] >> 12) & 1u, static_cast<unsigned>(v[i + 3] >> 8) & 15u);
-          std::fclose(fp);
-        }
-      }
-    };
-    static RawLog log;
-    log.path = rawf;
-    for (uint32_t f = 0; f < cnt; f++)
-      if (t[32 * f + 13])
-      {
-        const unsigned long long rec[4] = {log.launch, t[32 * f], t[32 * f + 13], t[32 * f + 21]};
-        log.v.insert(log.v.end(), rec, rec + 4);
-      }
-    log.launch++;
-    HIPCHK(hipMemsetAsync(d_prof + 32 * static_cast<size_t>(s0), 0, sizeof(unsigned long long) * 32 * cnt, h->stream));
-    return VOFOD_OK;
-  }
-  static const char* names[13] = {"bits", "prefix", "words", "rank-a/b", "rank-c", "emit", "extras", "probe", "adjacent", "far", "exact", "minima+stats", "labels"};  // (rank-a/b includes the counting pass: stamp 14 splits them)
-  std::vector<std::pair<double, uint32_t>> byd;
-  unsigned long long t0 = ~0ull, t1 = 0;
-  for (uint32_t f = 0; f < cnt; f++)
-  {
-    if (!t[32 * f + 13])
-      continue;
-    byd.push_back({(t[32 * f + 13] - t[32 * f]) * 0.01, f});
-    t0 = std::min(t0, t[32 * f]);
-    t1 = std::max(t1, t[32 * f + 13]);
-  }
-  std::sort(byd.begin(), byd.end());
-  double mean = 0;
-  for (auto& b : byd)
-    mean += b.first / byd.size();
-  for (size_t q : {size_t(0), byd.size() / 2, byd.size() - 1})
-  {
-    if (byd.empty())
-      break;
-    const uint32_t f = byd[q].second;
-    if (t[32 * f + 31] == ~0ull)
-    {
-      // a close-first frame: its own phases behind the emission
-      auto us = [&](int a, int b) { return (t[32 * f + b] - t[32 * f + a]) * 0.01; };
-      // (stamps 3 -> 15 -> 14: counting pass and closebits, in the order the kernel runs them)
-      const double t_count = FR_LEAN_WEIGHTS ? us(15, 14) : us(3, 15), t_closebits = FR_LEAN_WEIGHTS ? us(3, 15) : us(15, 14);
-      std::fprintf(stderr,
-                   "[k_frame_lds_far] frame %u: %.1f us | keys %llu V %llu bricks %llu pure-far bricks %llu far clusters %llu candidate members %llu | input+fragile %.1f prefix %.1f words %.1f count %.1f closebits "
-                   "%.1f rank-a/b %.1f rank-c %.1f emit %.1f extras %.1f near+far %.1f open %.1f stats %.1f table %.1f members %.1f\n",
-                   f, byd[q].first, t[32 * f + 27], t[32 * f + 29], t[32 * f + 26], t[32 * f + 24], t[32 * f + 25], t[32 * f + 30], us(0, 1), us(1, 2), us(2, 3), t_count, t_closebits, us(14, 4), us(4, 5),
-                   us(5, 6), us(6, 7), us(7, 8), us(8, 9), us(9, 10), us(10, 11), us(11, 13));
-      continue;
-    }
-    std::fprintf(stderr, "[k_frame_lds] frame %u: %.1f us | keys %llu V %llu bricks %llu extras %llu hits %llu open %llu surviving %llu |", f, byd[q].first, t[32 * f + 27], t[32 * f + 29],
-                 t[32 * f + 26], t[32 * f + 28], t[32 * f + 24], t[32 * f + 25], t[32 * f + 30]);
-    for (int i = 0; i < 13; i++)
-      std::fprintf(stderr, " %s %.1f", names[i], (t[32 * f + i + 1] - t[32 * f + i]) * 0.01);
-    std::fprintf(stderr, " (count %.1f of rank-a/b; %llu bricks outside the largest component, %llu far hits)\n", (t[32 * f + 14] - t[32 * f + 3]) * 0.01, t[32 * f + 31] & 0xffffffffull,
-                 t[32 * f + 31] >> 32);
-  }
-  if (!byd.empty())
-    std::fprintf(stderr, "[k_frame_lds] %zu workgroups: span %.1f us, mean %.1f us\n", byd.size(), (t1 - t0) * 0.01, mean);
-  // VOFOD_LDS_PROF_JSON=<file>: the phase table of the close-first frames of this launch (mean / median / max over the
-  // frames, us), one JSON object per launch appended to the file - profiles/r05_frame_phases.json is made of these
-  if (const char* jf = std::getenv("VOFOD_LDS_PROF_JSON"); jf && !byd.empty() && t[32 * byd[0].second + 31] == ~0ull)
-  {
-    // ("count" and "closebits" keep their names whichever runs first: FR_LEAN_WEIGHTS puts closebits in front)
-    static const int cuts[][2] = {{0, 16}, {16, 17}, {17, 18}, {18, 19}, {19, 20}, {20, 1}, {1, 2}, {2, 3}, {FR_LEAN_WEIGHTS ? 15 : 3, FR_LEAN_WEIGHTS ? 14 : 15}, {FR_LEAN_WEIGHTS ? 3 : 15, FR_LEAN_WEIGHTS ? 15 : 14}, {14, 4}, {4, 5}, {5, 6}, {6, 7}, {7, 8}, {8, 9}, {9, 10}, {10, 11}, {11, 13}, {0, 13}};
-    static const char* cnames[] = {"input", "input_wait", "grid", "grid_wait", "fragile", "fragile_wait", "prefix", "words", "count", "closebits", "rank_ab", "rank_c", "emit", "extras_restore", "cf_edges", "cf_open", "cf_stats", "cf_table", "cf_members", "total"};
-    if (FILE* fp = std::fopen(jf, "a"))
-    {
-      double busy = 0;
-        for (auto& b : byd)
-          busy += b.first;
-        std::fprintf(fp, "{\"frames\": %zu, \"span_us\": %.1f, \"t0_abs_us\": %.1f, \"busy_us_sum\": %.1f, \"phases\": {", byd.size(), (t1 - t0) * 0.01, t0 * 0.01, busy);
-      for (size_t c = 0; c < sizeof(cuts) / sizeof(cuts[0]); c++)
-      {
-        std::vector<double> v;
-        for (auto& b : byd)
-          v.push_back((t[32 * b.second + cuts[c][1]] - t[32 * b.second + cuts[c][0]]) * 0.01);
-        std::sort(v.begin(), v.end());
-        double m = 0;
-        for (double x : v)
-          m += x / v.size();
-        std::fprintf(fp, "%s\"%s\": {\"mean\": %.2f, \"median\": %.2f, \"p90\": %.2f, \"max\": %.2f}", c ? ", " : "", cnames[c], m, v[v.size() / 2], v[v.size() * 9 / 10], v.back());
-      }
-      // where in time the frames' workgroups started and ended relative to the first start (one CU per frame: late starts = a busy chip)
-      std::vector<double> st, en;
-      for (auto& b : byd)
-      {
-        st.push_back((t[32 * b.second] - t0) * 0.01);
-        en.push_back((t[32 * b.second + 13] - t0) * 0.01);
-      }
-      std::sort(st.begin(), st.end());
-      std::sort(en.begin(), en.end());
-      std::fprintf(fp, "}, \"start_us\": {\"median\": %.1f, \"max\": %.1f}, \"end_us\": {\"median\": %.1f, \"max\": %.1f}", st[st.size() / 2], st.back(), en[en.size() / 2], en.back());
-      {
-        // the classification tail of the same frames (k_tail_far's stamps): boxes + gates, flood fills, records; and how long after
-        // the frame's own end its tail started
-        std::vector<double> bx, ex, fi, to, lag;
-        for (auto& b : byd)
-        {
-          const unsigned long long a0 = t[32 * b.second + 22], pk = t[32 * b.second + 23];
-          if (!a0)
-            continue;
-          const double d1 = (pk & 0xfffffull) * 0.01, d2 = ((pk >> 20) & 0xfffffull) * 0.01, d3 = ((pk >> 40) & 0xfffffull) * 0.01;
-          bx.push_back(d1);
-          ex.push_back(d2 - d1);
-          fi.push_back(d3 - d2);
-          to.push_back(d3);
-          lag.push_back((static_cast<double>(a0) - static_cast<double>(t[32 * b.second + 13])) * 0.01);
-        }
-        if (!to.empty())
-        {
-          auto q = [&](std::vector<double>& v, const char* name, bool last) {
-            std::sort(v.begin(), v.end());
-            double m = 0;
-            for (double x : v)
-              m += x / v.size();
-            std::fprintf(fp, "\"%s\": {\"mean\": %.2f, \"median\": %.2f, \"p90\": %.2f, \"max\": %.2f}%s", name, m, v[v.size() / 2], v[v.size() * 9 / 10], v.back(), last ? "" : ", ");
-          };
-          std::fprintf(fp, ", \"tail\": {");
-          q(bx, "boxes_gates", false);
-          q(ex, "flood_fills", false);
-          q(fi, "records", false);
-          q(to, "total", false);
-          q(lag, "start_after_frame_end", true);
-          std::fprintf(fp, "}");
-        }
-      }
-      std::fprintf(fp, "}\n");
-      std::fclose(fp);
-    }
-  }
-  HIPCHK(hipMemset(d_prof + 32 * static_cast<size_t>(s0), 0, sizeof(unsigned long long) * 32 * cnt));
-          return VOFOD_OK;
-  }
+  BrickParams bp = ct->bp;
+  bp.bricks_cap = ws.bricks_cap;
+  unsigned long long* d_prof = nullptr;
+  VCHK(frame_prof_slots(h, ws, d_prof));
+  const unsigned long long* mapclose = plan.use_dilated ? h->d_mapclose.p : nullptr;
+  // Lean emission: a production batch reads the voxel records of the candidates' members only - voxels of pure-far bricks -, so
+  // k_frame_lds_far writes (and, built with FR_LEAN_WEIGHTS, counts the points of) those bricks' voxels alone.  The far-only debug
+  // view reads the whole cloud and keeps the full emission; VOFOD_LEAN_EMIT=0 keeps it everywhere.
+  const bool far = plan.clusterer == vplan::Clusterer::FrameFar, packed = plan.in_packed;
+  const auto kern = far ? (packed ? k_frame_lds_far_p : k_frame_lds_far) : (packed ? k_frame_lds_full_p : k_frame_lds_full);
+  const char* label = far ? (packed ? "k_frame_lds_far" : "k_frame_lds_far_strided") : (packed ? "k_frame_lds_full" : "k_frame_lds_full_strided");
+  KLAUNCH_AS(h, label, kern, dim3(n), dim3(FR_THREADS), g, bp, ct->d_lbtab, ws.d_hdrs, ws.sa, ws.pt_cap, ws.va, ws.d_labels, plan.lb_limit, reinterpret_cast<uint32_t*>(ws.d_table.p), ws.fs, h->mg, mapclose,
+             h->d_mapbits, h->d_crows, h->closetab.n_rows, up, ws.d_table, ws.d_cand, plan.write_tables ? 1 : 0, d_prof, ref_lattice, ws.d_args, far ? plan.close_first : 0, plan.lean ? 1 : 0);
+  if (d_prof && !ws.prof_deferred)
+    VCHK(print_frame_prof(h, 0, n, true));
+  HIPCHK(hipGetLastError());
+  return VOFOD_OK;
+}
 
-// K7: Euclidean clustering of the frames in `ws`
-int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridParams& g, uint32_t n, float tol, float cmax, const unsigned long long* mapclose = nullptr,
-                   const UpdateParams* up_tables = nullptr)
+// K7: Euclidean clustering of the voxel records in `ws` by the general kernels - brick level where a 4x4x4 brick is a clique for
+// the tolerance, voxel level otherwise (VOFOD_CCL=voxel forces it: the tests compare both families against the oracle)
+int launch_cluster(vofod_handle* h, Workspace& ws, const vplan::ChainPlan& plan, const GridParams& g, const vofod_handle::ClusterTables* ct)
 {
-  vofod_handle::ClusterTables* ct = nullptr;
-  VCHK(cluster_tables(h, g, tol, cmax, &ct));
   const uint32_t gv = (ws.vox_cap + 255u) / 256u;
-  if (want_bricks(ct, ws))
+  const unsigned long long* mapclose = plan.use_dilated ? h->d_mapclose.p : nullptr;  // k_flatten then answers hasCloseTo through the dilated image
+  if (plan.bricks)
   {
     BrickParams bp = ct->bp;
     bp.bricks_cap = ws.bricks_cap;
-    // Batches of independent frames: the whole brick graph of a frame is clustered inside one workgroup's LDS
-    // (kernels_brick_lds.h).  VOFOD_BRICK_LDS=0 keeps the global-memory kernels.
-    const uint32_t lb_limit = std::getenv("VOFOD_LDS_MAX_BRICKS") ? std::min<uint32_t>(LB_MAX, std::atoi(std::getenv("VOFOD_LDS_MAX_BRICKS"))) : LB_MAX;
-    if (lf.lean_emit)
-    {
-      DevBuf<unsigned long long>& d_prof_all = h->d_prof_ccl;
-      if (!d_prof_all && std::getenv("VOFOD_LDS_PROF"))
-      {
-        HIPCHK(d_prof_all.alloc(32 * 4096));
-        HIPCHK(hipMemset(d_prof_all, 0, sizeof(unsigned long long) * 32 * 4096));
-      }
-      // VOFOD_LDS_PROF=2: a submitted batch keeps the stamps in its ticket's slots and prints them when it is collected - the
-      // phases as they last with the other batches' kernels beside them (=1 synchronises behind every launch)
-      ws.prof_deferred = false;
-      uint32_t prof_slot0 = 0;
-      if (d_prof_all && std::atoi(std::getenv("VOFOD_LDS_PROF") ? std::getenv("VOFOD_LDS_PROF") : "0") == 2 && ws.F <= 256)
-        for (int t = 0; t < vofod_handle::MAX_INFLIGHT; t++)
-          if (&ws == h->slot(t))
-          {
-            ws.prof_deferred = true;
-            prof_slot0 = 256u * static_cast<uint32_t>(t);
-          }
-      ws.prof_slot0 = prof_slot0;
-      unsigned long long* d_prof = d_prof_all ? d_prof_all + 32 * static_cast<size_t>(prof_slot0) : nullptr;
-      if (lf.frame_fused)
-      {
-        lf.far_ran = up_tables && mapclose && ws.close_first;
-        // (four instantiations: close first or not, packed 16-byte column loads or strided ones; the profile names the algorithmic
-        // variant, k_frame_lds_far / k_frame_lds_full, and the strided input pass by the suffix _strided)
-#define VOFOD_FRAME_LAUNCH(label, kern, UP, WT, CF, LEAN)                                                                                                                                         \
-  KLAUNCH_AS(h, label, kern, dim3(n), dim3(FR_THREADS), g, bp, ct->d_lbtab, ws.d_hdrs, ws.sa, ws.pt_cap, ws.va, ws.d_labels, lb_limit, reinterpret_cast<uint32_t*>(ws.d_table.p), ws.fs, h->mg, mapclose, \
-          h->d_mapbits, h->d_crows, h->closetab.n_rows, UP, ws.d_table, ws.d_cand, WT, d_prof, lf.ref_lattice, ws.d_args, CF, LEAN)
-        const UpdateParams up_none{};
-        if (lf.far_ran)  // read-only batches: cluster the far voxels only (the close-first instantiation)
-        {
-          // Lean emission: a production batch reads the voxel records of the candidates' members only - voxels of pure-far bricks -,
-          // so the kernel writes (and, built with FR_LEAN_WEIGHTS, counts the points of) those bricks' voxels alone.  The far-only debug view reads the whole
-          // cloud and keeps the full emission; VOFOD_LEAN_EMIT=0 keeps it everywhere.
-          const int lean = (ws.close_first == 1 && !switch_off("VOFOD_LEAN_EMIT")) ? 1 : 0;
-          if (lf.in_packed)
-            VOFOD_FRAME_LAUNCH("k_frame_lds_far", k_frame_lds_far_p, *up_tables, 1, ws.close_first, lean);
-          else
-            VOFOD_FRAME_LAUNCH("k_frame_lds_far_strided", k_frame_lds_far, *up_tables, 1, ws.close_first, lean);
-        }
-        else
-        {
-          if (lf.in_packed)
-            VOFOD_FRAME_LAUNCH("k_frame_lds_full", k_frame_lds_full_p, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0, 0);
-          else
-            VOFOD_FRAME_LAUNCH("k_frame_lds_full_strided", k_frame_lds_full, up_tables ? *up_tables : up_none, (up_tables && mapclose) ? 1 : 0, 0, 0);
-        }
-#undef VOFOD_FRAME_LAUNCH
-        lf.finalize_fused = up_tables && mapclose;
-        if (d_prof && !ws.prof_deferred)
-          VCHK(print_frame_prof(h, 0, n, true));
-        lf.closefar_fused = mapclose != nullptr;
-        HIPCHK(hipGetLastError());
-        return VOFOD_OK;
-      }
-      // (lean_emit without the frame kernel cannot happen: launch_voxelize clears it when it does not plan the frame path)
-      h->err = "internal: lean emission without the frame kernel";
-      return VOFOD_ERR_DEVICE;
-    }
-    if (!lf.bricks_preset)
-      KLAUNCH(h, k_brick_set, fgrid(g, gv), dim3(256), g, bp, ws.d_hdrs, ws.va, ws.ba);
+    // (Fusing the brick registration into k_emit was measured slower - 194 us vs 96 + 50 us for 32 frames: the returning
+    // atomicOr sits inside the load-balanced emission loop - so it is a kernel of its own.)
+    KLAUNCH(h, k_brick_set, fgrid(g, gv), dim3(256), g, bp, ws.d_hdrs, ws.va, ws.ba);
     // the stencil's pairs as per-brick connectivity masks + transitive reduction; a stencil beyond 64 offsets (or without the
     // pair tables) takes the fused probe + union kernel.  (Round 1 also had "masks + batched hooking" behind VOFOD_BRICK_MODE=2:
     // CAS storms, 470 us against 206 us - removed in round 4.)
-    if (bp.n_off <= 64 && ct->d_pair)
+    if (plan.clusterer == vplan::Clusterer::BrickMasks)
     {
       // ws.d_table is free until k_finalize: it holds the per-brick connectivity masks (list order) in between
       unsigned long long* conn = reinterpret_cast<unsigned long long*>(ws.d_table.p);
@@ -1569,7 +1295,6 @@ int launch_cluster(vofod_handle* h, Workspace& ws, LaunchFlags& lf, const GridPa
     KLAUNCH(h, k_union<2>, fgrid(g, gv), dim3(256), g, ct->cp, ct->d_rows, ws.d_hdrs, ws.d_bitmaps, ws.d_wprefix, ws.va);
     KLAUNCH(h, k_flatten<0>, fgrid(g, gv), dim3(256), g, ws.d_hdrs, ws.va, ws.d_labels, ws.ba, 0u, h->mg, mapclose, h->d_mapbits, h->d_crows, h->closetab.n_rows);
   }
-  lf.closefar_fused = mapclose != nullptr;  // k_flatten answered hasCloseTo through the dilated image
   HIPCHK(hipGetLastError());
   return VOFOD_OK;
 }
