@@ -16,6 +16,9 @@ def reduce(path, frames=256, skip=2):
     out["phases"] = {}
     for ph in rows[0]["phases"]:
         out["phases"][ph] = {q: round(sum(r["phases"][ph][q] for r in rows) / len(rows), 2) for q in ("mean", "median", "p90", "max")}
+    wv = [r for r in rows if "input_waves" in r]
+    if wv:  # the input pass wave by wave: the mean and the last wave's end (us from the frame's start), per cent of the loop spent waiting for loads
+        out["input_waves"] = {k: {q: round(sum(r["input_waves"][k][q] for r in wv) / len(wv), 2) for q in ("mean", "median", "p90", "max")} for k in wv[0]["input_waves"]}
     tl = [r for r in rows if "tail" in r]
     if tl:  # k_tail_far's own stamps for the same frames (one wave per frame)
         out["k_tail_far"] = {ph: {q: round(sum(r["tail"][ph][q] for r in tl) / len(tl), 2) for q in ("mean", "median", "p90", "max")} for ph in tl[0]["tail"]}

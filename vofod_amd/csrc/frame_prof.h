@@ -74,8 +74,8 @@ int frame_prof_slots(vofod_handle* h, Workspace& ws, unsigned long long*& d_prof
   DevBuf<unsigned long long>& d_prof_all = h->d_prof_ccl;
   if (!d_prof_all && std::getenv("VOFOD_LDS_PROF"))
   {
-    HIPCHK(d_prof_all.alloc(32 * 4096));
-    HIPCHK(hipMemset(d_prof_all, 0, sizeof(unsigned long long) * 32 * 4096));
+    HIPCHK(d_prof_all.alloc(FR_PROF_WORDS));  // (the frames' slots, then the per-wave values of the input pass)
+    HIPCHK(hipMemset(d_prof_all, 0, sizeof(unsigned long long) * FR_PROF_WORDS));
   }
   ws.prof_deferred = false;
   uint32_t prof_slot0 = 0;
@@ -101,6 +101,10 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
   if (sync)
     HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(t.data(), d_prof + 32 * static_cast<size_t>(s0), sizeof(unsigned long long) * 32 * cnt, hipMemcpyDeviceToHost));
+  // the input pass per wave: [frame][wave]{clock at which the wave left the loop, ticks it waited for its pieces}
+  unsigned long long* d_wave = d_prof + 32 * static_cast<size_t>(FR_PROF_FRAMES) + 32 * static_cast<size_t>(s0);
+  std::vector<unsigned long long> tw(32 * cnt);
+  HIPCHK(hipMemcpy(tw.data(), d_wave, sizeof(unsigned long long) * 32 * cnt, hipMemcpyDeviceToHost));
   if (const char* rawf = std::getenv("VOFOD_LDS_PROF_RAW"))
   {
     // raw mode: nothing is formatted while the pipeline runs (the JSON table below costs the host ~100 us per launch: 840 k instead
@@ -132,6 +136,7 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
       }
     log.launch++;
     HIPCHK(hipMemsetAsync(d_prof + 32 * static_cast<size_t>(s0), 0, sizeof(unsigned long long) * 32 * cnt, h->stream));
+    HIPCHK(hipMemsetAsync(d_wave, 0, sizeof(unsigned long long) * 32 * cnt, h->stream));
     return VOFOD_OK;
   }
   static const char* names[13] = {"bits", "prefix", "words", "rank-a/b", "rank-c", "emit", "extras", "probe", "adjacent", "far", "exact", "minima+stats", "labels"};  // (rank-a/b includes the counting pass: stamp 14 splits them)
@@ -158,8 +163,8 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
     {
       // a close-first frame: its own phases behind the emission
       auto us = [&](int a, int b) { return (t[32 * f + b] - t[32 * f + a]) * 0.01; };
-      // (stamps 3 -> 15 -> 14: counting pass and closebits, in the order the kernel runs them)
-      const double t_count = FR_LEAN_WEIGHTS ? us(15, 14) : us(3, 15), t_closebits = FR_LEAN_WEIGHTS ? us(3, 15) : us(15, 14);
+      // (stamps 3 -> 15 -> 14: closebits, then the counting pass)
+      const double t_count = us(15, 14), t_closebits = us(3, 15);
       std::fprintf(stderr,
                    "[k_frame_lds_far] frame %u: %.1f us | keys %llu V %llu bricks %llu pure-far bricks %llu far clusters %llu candidate members %llu | input+fragile %.1f prefix %.1f words %.1f count %.1f closebits "
                    "%.1f rank-a/b %.1f rank-c %.1f emit %.1f extras %.1f near+far %.1f open %.1f stats %.1f table %.1f members %.1f\n",
@@ -180,8 +185,7 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
   // frames, us), one JSON object per launch appended to the file - profiles/r05_frame_phases.json is made of these
   if (const char* jf = std::getenv("VOFOD_LDS_PROF_JSON"); jf && !byd.empty() && t[32 * byd[0].second + 31] == ~0ull)
   {
-    // ("count" and "closebits" keep their names whichever runs first: FR_LEAN_WEIGHTS puts closebits in front)
-    static const int cuts[][2] = {{0, 16}, {16, 17}, {17, 18}, {18, 19}, {19, 20}, {20, 1}, {1, 2}, {2, 3}, {FR_LEAN_WEIGHTS ? 15 : 3, FR_LEAN_WEIGHTS ? 14 : 15}, {FR_LEAN_WEIGHTS ? 3 : 15, FR_LEAN_WEIGHTS ? 15 : 14}, {14, 4}, {4, 5}, {5, 6}, {6, 7}, {7, 8}, {8, 9}, {9, 10}, {10, 11}, {11, 13}, {0, 13}};
+    static const int cuts[][2] = {{0, 16}, {16, 17}, {17, 18}, {18, 19}, {19, 20}, {20, 1}, {1, 2}, {2, 3}, {15, 14}, {3, 15}, {14, 4}, {4, 5}, {5, 6}, {6, 7}, {7, 8}, {8, 9}, {9, 10}, {10, 11}, {11, 13}, {0, 13}};
     static const char* cnames[] = {"input", "input_wait", "grid", "grid_wait", "fragile", "fragile_wait", "prefix", "words", "count", "closebits", "rank_ab", "rank_c", "emit", "extras_restore", "cf_edges", "cf_open", "cf_stats", "cf_table", "cf_members", "total"};
     if (FILE* fp = std::fopen(jf, "a"))
     {
@@ -206,7 +210,43 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
       }
       std::sort(st.begin(), st.end());
       std::sort(en.begin(), en.end());
-      std::fprintf(fp, "}, \"start_us\": {\"median\": %.1f, \"max\": %.1f}, \"end_us\": {\"median\": %.1f, \"max\": %.1f}", st[st.size() / 2], st.back(), en[en.size() / 2], en.back());
+      // the input pass wave by wave (us from the frame's start): when the mean wave and the last wave left the loop, and the share
+      // of its time in the loop the mean wave spent waiting for loads
+      std::vector<double> w_mean, w_last, w_share;
+      for (auto& b : byd)
+      {
+        const unsigned long long* w = &tw[32 * b.second];
+        const unsigned long long f0 = t[32 * b.second];
+        double e_sum = 0, e_max = 0, s_sum = 0;
+        int nw = 0;
+        for (int k = 0; k < FR_THREADS / 64; k++)
+          if (w[2 * k] > f0)
+          {
+            const double e = (w[2 * k] - f0) * 0.01;
+            e_sum += e;
+            e_max = std::max(e_max, e);
+            s_sum += w[2 * k + 1] / e;  // (ticks of 10 ns over us: per cent)
+            nw++;
+          }
+        if (nw)
+        {
+          w_mean.push_back(e_sum / nw);
+          w_last.push_back(e_max);
+          w_share.push_back(s_sum / nw);
+        }
+      }
+      std::fprintf(fp, "}");
+      if (!w_mean.empty())
+      {
+        std::fprintf(fp, ", \"input_waves\": {");
+        Quantiles(w_mean).json(fp, "mean_wave_end");
+        std::fprintf(fp, ", ");
+        Quantiles(w_last).json(fp, "last_wave_end");
+        std::fprintf(fp, ", ");
+        Quantiles(w_share).json(fp, "load_wait_pct");
+        std::fprintf(fp, "}");
+      }
+      std::fprintf(fp, ", \"start_us\": {\"median\": %.1f, \"max\": %.1f}, \"end_us\": {\"median\": %.1f, \"max\": %.1f}", st[st.size() / 2], st.back(), en[en.size() / 2], en.back());
       // the classification tail of the same frames (k_tail_far's stamps): boxes + gates, flood fills, records; and how long after
       // the frame's own end its tail started
       std::vector<double> bx, ex, fi, to, lag;
@@ -241,6 +281,7 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
     }
   }
   HIPCHK(hipMemset(d_prof + 32 * static_cast<size_t>(s0), 0, sizeof(unsigned long long) * 32 * cnt));
+  HIPCHK(hipMemset(d_wave, 0, sizeof(unsigned long long) * 32 * cnt));
   return VOFOD_OK;
 }
 

@@ -25,7 +25,7 @@
 // A frame beyond the LDS capacities raises CCL_RETRY_STATUS: the host re-runs that batch on the general kernels.
 // Round 11, lean emission: a production batch (close first, tables written here, no debug output) reads the voxel records of the
 // candidates' members only - voxels of pure-far bricks.  The host then passes `lean`: step 4 stores the records of the pure-far
-// bricks alone (same record, same rank) - with FR_LEAN_WEIGHTS step 3's weights are counted for those bricks alone, too; ranks, V
+// bricks alone (same record, same rank) - and step 3's weights are counted for those bricks alone, too (round 23); ranks, V
 // and the capacity checks stay those of the whole frame.  The far-only debug view reads the whole cloud and keeps the full emission, as does every
 // launch under VOFOD_LEAN_EMIT=0 (read on every call, like the other switches).
 #pragma once
@@ -68,12 +68,12 @@ constexpr int CF_MAX = FR_THREADS;                 // close-first clustering: pu
 #define CF_G_DEF 4
 #endif
 constexpr int CF_G = CF_G_DEF;                     // bricks per thread whose map lookups are in flight together (close-first, first part)
-#ifndef FR_LEAN_WEIGHTS_DEF
-#define FR_LEAN_WEIGHTS_DEF 0
-#endif
-constexpr bool FR_LEAN_WEIGHTS = FR_LEAN_WEIGHTS_DEF != 0;  // 1 (not measured yet, hence off): close-first builds the pure-far list in FRONT of the counting pass 3b, which a lean launch then runs for its bricks only
 constexpr uint16_t FR_VBASE_NONE = 0xffffu;        // lean emission: "not counted" in place of a node's first voxel index
 constexpr uint32_t CF_LABEL_NONE = 0xffffffffu;    // label of a voxel outside the far clusters in the far-only debug view
+// VOFOD_LDS_PROF: the stamp buffer holds 32 slots for each of FR_PROF_FRAMES frames, then - same frame index - two values for each
+// of a frame's 16 waves: the clock at which the wave left the input pass, and the ticks it spent there waiting for its loads
+constexpr uint32_t FR_PROF_FRAMES = 4096;
+constexpr size_t FR_PROF_WORDS = 2 * 32 * static_cast<size_t>(FR_PROF_FRAMES);
 
 // per-frame scratch in global memory (L2-resident: touched sparsely)
 struct FrameScratch
@@ -496,8 +496,10 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     // nothing to do
     const bool zero_dropped = g.ex_min[0] <= 0.0f && g.ex_min[1] <= 0.0f && g.ex_min[2] <= 0.0f && g.ex_max[0] >= 0.0f && g.ex_max[1] >= 0.0f && g.ex_max[2] >= 0.0f;
     const uint32_t cell_lim = 2048u;  // (k0 | k1 | k2 << 3) < 2048: the cell fits the code's fields (9 + 2, 9 + 2, 6 + 2 bits)
+    // (the waves take a round's 512-point pieces in turn: a wave sees every azimuth sector and ring parity - even load)
+    auto piece_pt = [&](uint32_t r) -> uint32_t { return r * IN_ROUND + ((static_cast<uint32_t>(wave) + r) & (FR_THREADS / 64 - 1)) * (64u * IN_PPT); };
     auto load_round = [&](uint32_t r, float (&X)[IN_PPT], float (&Y)[IN_PPT], float (&Z)[IN_PPT]) {
-      const uint32_t i0 = r * IN_ROUND + ((static_cast<uint32_t>(wave) + r) & (FR_THREADS / 64 - 1)) * (64u * IN_PPT) + static_cast<uint32_t>(lane) * IN_PPT;
+      const uint32_t i0 = piece_pt(r) + static_cast<uint32_t>(lane) * IN_PPT;
       if constexpr (PACKED)
       {
 #pragma unroll
@@ -537,6 +539,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     uint16_t* const q_lo = reinterpret_cast<uint16_t*>(q_pl + IN_Q_PLANES * IN_Q_UNITS);                                             // unit index (round << 6 | lane): low half ...
     uint16_t* const q_hi = s_pfpar + static_cast<uint32_t>(wave) * IN_Q_UNITS;                                                       // ... and high half
     uint32_t q_fill = 0;  // units in the queue (wave-uniform)
+    uint32_t w_wait = 0;  // VOFOD_LDS_PROF: ticks of the 100 MHz clock this wave spent waiting for its pieces
     for (uint32_t r = 0;; r++)
     {
       // (No software prefetch of the next round.  Round 4: with the codes' stores between a prefetch and its use every round ended
@@ -544,7 +547,12 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       // iteration, where this round's loads are the youngest operations in flight, then the previous round's stores, held in
       // registers, then the next round's loads, then the work - compiles as intended (one s_waitcnt vmcnt(0) per round, at the
       // top) and measures the same: 274.1 / 277.1 / 278.2 us against 276.1 / 279.3 / 279.1 us per 256 frames, interleaved on one box.
-      // The pass is not waiting for its loads: its instruction stream is what it costs.)
+      // Round 23, on the compacted loop: the per-wave stamps below put the time a wave waits for its pieces at 22 % of its time in
+      // the loop.  The next piece loaded into lx / ly / lz in front of the back - they are dead there - does not fit the
+      // registers: 80 - 128 bytes of scratch per lane in all four instantiations, wherever in the back the loads are issued.  The
+      // next piece requested into L2 instead (one word per 128-byte line, into a token register) fits and LOSES: 1 041 - 1 049 k
+      // against 1 098 - 1 105 k frames/s.  Pieces dealt from a workgroup counter instead of in turn: the kernel alone 207 - 208 us
+      // against 212 - 218 us, the pipelined rate inside its own spread - not kept.  DESIGN.md 5.5.)
       const bool flush = r >= in_rounds;  // behind the last round: the rest of the queue
       if (flush && q_fill == 0u)
         break;
@@ -555,8 +563,13 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       if (!flush)
       {
         load_round(r, lx, ly, lz);
-        // (the waves take the round's 512-point pieces in turn: a wave sees every azimuth sector and ring parity - even load)
-        const uint32_t l0 = r * IN_ROUND + ((static_cast<uint32_t>(wave) + r) & (FR_THREADS / 64 - 1)) * (64u * IN_PPT) + static_cast<uint32_t>(lane) * IN_PPT;
+        if (prof)
+        {
+          const unsigned long long t_req = wall_clock64();
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          w_wait += static_cast<uint32_t>(wall_clock64() - t_req);
+        }
+        const uint32_t l0 = piece_pt(r) + static_cast<uint32_t>(lane) * IN_PPT;
         live = l0 < n_pts;
         if (zero_dropped)
         {
@@ -606,7 +619,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
         }
         const uint32_t id = static_cast<uint32_t>(q_lo[lane]) | (static_cast<uint32_t>(q_hi[lane]) << 16);
         const uint32_t ur = id >> 6;
-        i0 = ur * IN_ROUND + ((static_cast<uint32_t>(wave) + ur) & (FR_THREADS / 64 - 1)) * (64u * IN_PPT) + (id & 63u) * IN_PPT;
+        i0 = piece_pt(ur) + (id & 63u) * IN_PPT;
         if (flush && static_cast<uint32_t>(lane) >= q_fill)
           i0 = n_pts;
       }
@@ -746,6 +759,12 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     }
     // bounding box of the frame (ordered ints: +-inf where a wave kept nothing - the identity of the min / max below)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the wave's codes and fragile points have left (other lanes / waves read them below)
+    if (prof && lane == 0)
+    {
+      unsigned long long* pw = prof + 32 * static_cast<size_t>(FR_PROF_FRAMES) + static_cast<size_t>(FRAME) * 32 + 2 * wave;
+      pw[0] = wall_clock64();
+      pw[1] = w_wait;
+    }
     wave_bbox(fmn, fmx);
     if (lane == 0)
     {
@@ -1068,11 +1087,11 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   // candidates' members only, and those are voxels of pure-far bricks.  `lean` (wave-uniform, set by the host exactly then)
   // restricts pass d - and with it the weights: the counting pass 3b, the extras - to the bricks of the pure-far list: the same
   // records at the same ranks, the others are not written.  Ranks, V and every capacity check stay those of the whole frame.
-  // FR_LEAN_WEIGHTS: the list is built BEFORE the counting pass, which then skips every code of another brick; without it the
-  // counting pass stays as it was and the nodes outside the list are marked behind it, for the extras pass.
+  // The close-first instantiations build the list BEFORE the counting pass, which in a lean launch then skips every code of another
+  // brick at the cost of one s_vbase read (round 23: 226 -> 212 us per launch alone; the full clustering has no list and keeps
+  // its order).
   constexpr bool cf = CFM != 0;
   const bool lean_on = cf && lean != 0;
-  const bool lean_cnt = lean_on && FR_LEAN_WEIGHTS;  // the counting pass is lean too
   auto closebits = [&]() -> bool {
     if constexpr (cf)
     {
@@ -1190,9 +1209,9 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
             if (lean_on)
             {
               // lean emission: a node outside the pure-far list is marked "not counted" where its first voxel's index lives (V <= 65 535:
-              // no index is 0xffff); with the counting pass still ahead (FR_LEAN_WEIGHTS) the listed nodes are marked too - as counted
+              // no index is 0xffff); the counting pass is still ahead, so the listed nodes are marked too - as counted
               const uint32_t i = (g0 + j) * FR_THREADS + tid;
-              if (g0 + j < NPT && i < n && (FR_LEAN_WEIGHTS || !pf))
+              if (g0 + j < NPT && i < n)
                 s_vbase[i] = pf ? static_cast<uint16_t>(0u) : FR_VBASE_NONE;
             }
             const unsigned long long m = __ballot(pf);
@@ -1223,7 +1242,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     }
     return true;
   };
-  if constexpr (cf && FR_LEAN_WEIGHTS)
+  if constexpr (cf)
   {
     if (!closebits())
       return;
@@ -1240,7 +1259,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       bsave[i] = reinterpret_cast<const ulonglong2*>(s_bb)[i];
     constexpr int NPT = LB_MAX / FR_THREADS;  // consecutive nodes per thread
     // (two sums in one scan: all voxels << 16 | voxels that get a counter - a wave holds at most 64 * NPT * 64 < 65 536 of either.  They
-    // differ only in a lean launch behind FR_LEAN_WEIGHTS: V stays the frame's, the counters cover the pure-far bricks.)
+    // differ only in a lean launch: V stays the frame's, the counters cover the pure-far bricks.)
     static_assert(64 * NPT * 64 < 65536, "the packed sums of a wave");
     uint32_t pc[NPT], sum = 0;
 #pragma unroll
@@ -1248,7 +1267,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     {
       const uint32_t i = tid * NPT + r;
       const uint32_t c = i < n ? __popcll(s_word[i]) : 0u;
-      pc[r] = (lean_cnt && i < n && s_vbase[i] == FR_VBASE_NONE) ? 0u : c;
+      pc[r] = (lean_on && i < n && s_vbase[i] == FR_VBASE_NONE) ? 0u : c;
       sum += (c << 16) | pc[r];
     }
     const uint32_t incl = wave_incl_scan(sum);
@@ -1285,7 +1304,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     for (int r = 0; r < NPT; r++)
     {
       const uint32_t i = tid * NPT + r;
-      if (i < n && !(lean_cnt && pc[r] == 0u))  // (a brick has a voxel: only a node marked "not counted" has none to count)
+      if (i < n && !(lean_on && pc[r] == 0u))  // (a brick has a voxel: only a node marked "not counted" has none to count)
         s_vbase[i] = static_cast<uint16_t>(run);
       run += pc[r];
     }
@@ -1297,7 +1316,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     auto count = [&](uint32_t code, uint32_t add) {
       const uint32_t node = code >> 6, bit = code & 63u;
       const uint32_t vb = s_vbase[node];
-      if (lean_cnt && vb == FR_VBASE_NONE)
+      if (lean_on && vb == FR_VBASE_NONE)
         return;  // lean: no record of this brick leaves, nothing reads its weights
       const uint32_t idx = vb + __popcll(s_word[node] & ((1ull << bit) - 1ull));
       const uint32_t sh = 8u * (idx & 3u);
@@ -1357,12 +1376,6 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     }
   }
   __syncthreads();
-  if constexpr (!(cf && FR_LEAN_WEIGHTS))
-  {
-    FR_STAMP(15);
-    if (!closebits())
-      return;
-  }
   FR_STAMP(14);
   // ---- 4: ranks in key order.  Pass a: one segmented scan per 64-node chunk; the per-node channel prefixes go to the
   // frame's scratch in global memory (L2), the sums of the chunk's last brick row to LDS (rows may span chunks).

@@ -1246,9 +1246,11 @@ int launch_frame_kernel(vofod_handle* h, Workspace& ws, const vplan::ChainPlan& 
   bp.bricks_cap = ws.bricks_cap;
   unsigned long long* d_prof = nullptr;
   VCHK(frame_prof_slots(h, ws, d_prof));
+  if (n + ws.prof_slot0 > FR_PROF_FRAMES)
+    d_prof = nullptr;  // (a launch beyond the stamp buffer's frames leaves no stamps)
   const unsigned long long* mapclose = plan.use_dilated ? h->d_mapclose.p : nullptr;
   // Lean emission: a production batch reads the voxel records of the candidates' members only - voxels of pure-far bricks -, so
-  // k_frame_lds_far writes (and, built with FR_LEAN_WEIGHTS, counts the points of) those bricks' voxels alone.  The far-only debug
+  // k_frame_lds_far writes, and counts the points of, those bricks' voxels alone.  The far-only debug
   // view reads the whole cloud and keeps the full emission; VOFOD_LEAN_EMIT=0 keeps it everywhere.
   const bool far = plan.clusterer == vplan::Clusterer::FrameFar, packed = plan.in_packed;
   const auto kern = far ? (packed ? k_frame_lds_far_p : k_frame_lds_far) : (packed ? k_frame_lds_full_p : k_frame_lds_full);
