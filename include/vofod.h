@@ -705,6 +705,70 @@ int vofod_broadcast_map(vofod_comm* comm, vofod_handle* h, int32_t root, int32_t
  * shifts first and then takes a full snapshot. */
 int vofod_map_shift(vofod_handle* h, const int32_t shift_voxels[3], const float new_oparea_offset[3]);
 
+/* ------------------------------------------------- WORLD STORE (product library only)
+ *
+ * vofod_map_shift alone forgets what leaves the box.  With the world store enabled the handle is a WINDOW onto a map larger than
+ * the box: a sparse, tiled store on the device that the shift writes what leaves into and reads what enters from.  Off after
+ * vofod_create; while it is off every call behaves, launch for launch and bit for bit, as it does without this section.
+ *
+ * World indices.  While enabled the handle keeps an integer origin K[3], the world index of the window's voxel (0, 0, 0).  K = 0 at
+ * enable, and every successful vofod_map_shift adds its shift_voxels to K (the value given, also where |s| >= S).  A shift that would
+ * take a component of K outside +-2^30 is VOFOD_ERR_INVALID_ARG with nothing changed (store enabled only).
+ * World box.  Fixed at enable: lo = -margin_lo, hi = S + margin_hi (exclusive), S the map sizes; all in world indices.
+ * Tiles.  VOFOD_WORLD_TILE voxels per edge (2 KiB of uint32), the tile grid anchored at lo.  A dense directory of one word per tile of
+ * the box and a pool of max_tiles tiles are allocated by vofod_world_enable and by nothing else: a shift never allocates.  Tiles are
+ * never freed before vofod_reset or vofod_world_disable.
+ * The store holds the VOXEL MAP only.  Flags and the raycast map are per-pass state: no pass can be pending at a shift, and their rim
+ * enters as init, as without the store.
+ *
+ * The world view W maps a world index g to a 32-bit pattern:
+ *     g inside the window:                            the voxel map's voxel g - K,
+ *     otherwise g inside the box, its tile allocated: the stored pattern,
+ *     otherwise:                                      the bits of score_init.
+ *
+ * vofod_map_shift with the store enabled (every refusal stays and still changes nothing):
+ *   1. write back: every window voxel whose g lies outside the new window.  g in the box and its tile exists: the pattern is stored -
+ *      a pattern equal to init too (the voxel may have been stored as something else on an earlier trip).  g in the box, no tile, the
+ *      pattern differs from init: the tile is WANTED.  If all wanted tiles fit into the free part of the pool, all are allocated,
+ *      filled with init, and take their patterns; if they do not fit NONE is allocated - the shift goes through all the same (the
+ *      vehicle must not lose its box) and shifts_short_of_tiles goes up by one.  voxels_forgotten counts every leaving voxel that
+ *      differs from init and found no place: outside the box, or in a tile that was not allocated.
+ *   2. the maps move as stated at vofod_map_shift;
+ *   3. read in: every voxel of the new window without a source in the old one takes the stored pattern where its tile exists and
+ *      keeps the init value elsewhere;
+ *   4. K += shift_voxels.
+ * Consequence: with enough tiles and inside the box, W is the same function before and after any shift - only the window moves.
+ *
+ * vofod_load_apriori (and vofod_ingest_apriori through it) with the store enabled: the window is stamped as ever.  A point outside
+ * the window goes to g[a] = K[a] + int(floor((p[a] - map_offset[a]) * (1 / voxel_size))) - the window's own float32 expression without
+ * the in-limits cut; points whose floor is not finite or beyond +-2^30 are skipped.  g in the box: W(g) = +inf, allocating tiles.  The
+ * call counts the tiles it needs before it changes anything: if they do not fit it returns VOFOD_ERR_CAPACITY with window, store and
+ * latches untouched (unlike the shift: an a-priori load is init-time work, and the caller can enable a larger pool).  The world
+ * remembers VOXELS, not points: the cell of a far point is decided by the window's geometry at load time.
+ *
+ * vofod_reset: W is init everywhere - the directory is emptied, the pool is free, the counters are zero; K, the box and the switch
+ * are kept (the reference's reset(), which forgets the a-priori map too).  vofod_write_map, vofod_map_apply, vofod_map_export and
+ * vofod_broadcast_map see and change the window only: snapshots do not carry the store, a replica needs its own. */
+#define VOFOD_WORLD_TILE 8
+typedef struct vofod_world_info {
+  int32_t enabled, tile_edge;
+  int32_t origin[3];                /* K */
+  int32_t box_lo[3], box_hi[3];
+  uint64_t tiles_used, tiles_cap;
+  uint64_t shifts_short_of_tiles, voxels_forgotten;   /* cumulative since enable / reset */
+} vofod_world_info;
+/* VOFOD_ERR_INVALID_ARG: a negative margin, max_tiles == 0 (or above 2^32 - 16), a directory of more than 2^31 words, the store
+ * already enabled.  VOFOD_ERR_BUSY, as for the shift: a submitted batch, a raycast pass or a sepclusters pass pending.
+ * VOFOD_ERR_DEVICE: an allocation failed; nothing is kept.  tiles_cap = min(max_tiles, tiles of the box): more can never be used. */
+int vofod_world_enable(vofod_handle* h, const int32_t margin_lo[3], const int32_t margin_hi[3], uint64_t max_tiles);
+/* frees directory and pool; VOFOD_ERR_NOT_PENDING when not enabled; VOFOD_ERR_BUSY while a submitted batch is pending */
+int vofod_world_disable(vofod_handle* h);
+/* enabled = 0 and zeros when off */
+int vofod_world_status(vofod_handle* h, vofod_world_info* out);
+/* W over a box of world indices, x fastest, into host memory; n == size[0] * size[1] * size[2] (VOFOD_ERR_SIZE_MISMATCH otherwise).
+ * VOFOD_ERR_NOT_PENDING when not enabled; VOFOD_ERR_INVALID_ARG: a size below 1, lo or lo + size beyond +-2^31. */
+int vofod_world_read(vofod_handle* h, const int32_t lo[3], const int32_t size[3], float* dst, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,25 @@ sub["R17_MEASURED"] = (P / "r17_raycast_exact.txt").read_text().splitlines()[0].
 sub["R18_MEASURED"] = (P / "r18_raycast_one_walk.txt").read_text().splitlines()[0].removeprefix("measured: ")
 # §5.14: the first line of profiles/r21_point_motion.txt
 sub["R21_MEASURED"] = (P / "r21_point_motion.txt").read_text().splitlines()[0].removeprefix("measured: ")
+# §5.15: the figures of profiles/r23_world_store.json
+r23 = json.loads((P / "r23_world_store.json").read_text())
+parts = []
+for c in r23["configs"]:
+    cs = []
+    for kc in c["cases"]:
+        km = kc["kernels_ms"]
+        par = c.get("parent")
+        vs_parent = ""
+        if par:
+            key = str(kc["shift"])
+            theirs = sorted(r[key]["event_ms_median"] for r in par["runs"])
+            ours = sorted(r[key]["event_ms_median"] for r in par["own_runs"])
+            vs_parent = f"; alone in a process, store off {ours[0]:.4f}-{ours[-1]:.4f} ms against the parent's {theirs[0]:.4f}-{theirs[-1]:.4f} ms"
+        cs.append(f"s = ({', '.join(str(v) for v in kc['shift'])}), rim {kc['rim_voxels'] / 1e6:.2f} M voxels: off {kc['off']['event_ms_median']:.4f} ms, on {kc['on']['event_ms_median']:.4f} ms, "
+                  f"**on - off {kc['on_minus_off_ms']['event']:.4f} ms** (byte model {kc['byte_model']['ms_at_4_TBs']:.4f} ms at 4 TB/s; `k_world_mark` {km['k_world_mark']:.4f} + `k_world_claim` "
+                  f"{km['k_world_claim']:.4f} + `k_world_put` {km['k_world_put']:.4f} + `k_world_get` {km['k_world_get']:.4f} ms){vs_parent}")
+    parts.append(f"at {c['config']} ({c['sensor']}, M = {c['M'] / 1e6:.1f} M, {c['known_voxels'] / 1e6:.2f} M voxels known, {c['cases'][-1]['tiles_used_after']} tiles used at the end) " + "; ".join(cs))
+sub["R23_MEASURED"] = ". ".join(p[0].upper() + p[1:] for p in parts) + "."
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

@@ -197,6 +197,25 @@ class DetectionExtent(C.Structure):
     ]
 
 
+WORLD_TILE = 8
+
+
+class WorldInfo(C.Structure):
+    _fields_ = [
+        ("enabled", C.c_int32),
+        ("tile_edge", C.c_int32),
+        ("origin", C.c_int32 * 3),
+        ("box_lo", C.c_int32 * 3),
+        ("box_hi", C.c_int32 * 3),
+        ("tiles_used", C.c_uint64),
+        ("tiles_cap", C.c_uint64),
+        ("shifts_short_of_tiles", C.c_uint64),
+        ("voxels_forgotten", C.c_uint64),
+    ]
+
+
+assert C.sizeof(WorldInfo) == 80
+
 DETECTION_EXTENT = np.dtype([("id", "<u4"), ("frame", "<u4"), ("first", "<u4"), ("count", "<u4"), ("aabb_min", "<f4", 3), ("aabb_max", "<f4", 3)])
 assert DETECTION_EXTENT.itemsize == C.sizeof(DetectionExtent) == 40
 
@@ -300,13 +319,17 @@ _SIGS = {
     "set_point_motion": (C.c_int, [C.c_void_p, C.c_int]),
     "deskew_points": (C.c_int, [C.c_void_p, _P(Scan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "raycast_units": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_int32)]),
+    "world_enable": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "world_disable": (C.c_int, [C.c_void_p]),
+    "world_status": (C.c_int, [C.c_void_p, _P(WorldInfo)]),
+    "world_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
 }
 
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
                 "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units",
-                "set_point_motion", "deskew_points")
+                "set_point_motion", "deskew_points", "world_enable", "world_disable", "world_status", "world_read")
 
 
 class MsgHeader(C.Structure):

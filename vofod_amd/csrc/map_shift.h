@@ -35,6 +35,8 @@
 //   sepws (cluster list of a pass)     map indices of a sepclusters pass between begin and finish: refused while sep_pending.
 //   d_ray under raycast_pending        the ray lengths of a pass between begin and finish: refused while raycast_pending; outside a
 //                                      pass the map is zero or marked ray_dirty, and both states survive a shift as they are.
+//   vws::Store (world_store.h)         NOT indexed by map voxel but by world index (window origin K + voxel): untouched by the swap; the
+//                                      shift itself writes the leaving rim into it and reads the entering rim from it, and advances K.
 //   Workspace::det_refs                detections vofod_detection_points would answer for belong to the old area: det_valid cleared.
 // The voxel-grid lattices, the reference lattice of the frame kernel, the world crop and the cluster tables are derived from the
 // handle's geometry inside every call (fill_grid_params, frame_plan / fill_ref_lattice, map_cmax): nothing of them is kept.

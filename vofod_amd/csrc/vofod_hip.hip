@@ -38,6 +38,7 @@
 #include "point_deskew.h"
 #include "detection_points.h"
 #include "map_shift.h"
+#include "world_store.h"
 
 using namespace vk;
 
@@ -482,6 +483,7 @@ struct vofod_handle
   vt::Geom hg{};
   DevBuf<float> d_map, d_flags, d_ray;
   DevBuf<float> d_shift_spare;  // vofod_map_shift: destination of the out-of-place shift, swapped with the map it received (allocated on the first shift)
+  vws::Store world;  // vofod_world_enable: the voxel map is a window onto it (world_store.h); indexed by world index, so no shift moves it
   DevBuf<unsigned long long> d_mapbits;
   DevBuf<unsigned long long> d_mapclose;  // d_mapbits dilated by hasCloseTo's stencil (k_dilate), valid while gens match
   uint64_t mapbits_gen = 0, mapclose_gen = ~0ull;

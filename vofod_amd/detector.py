@@ -135,9 +135,9 @@ class VoFOD:
         self._check(self.lib.get_status(self.h, C.byref(s)), "vofod_get_status")
         return s
 
-    def load_apriori(self, xyz: np.ndarray):
+    def load_apriori(self, xyz: np.ndarray, allow: Sequence[int] = ()):
         a = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        self._check(self.lib.load_apriori(self.h, capi.ptr(a), a.shape[0]), "vofod_load_apriori")
+        return self._check(self.lib.load_apriori(self.h, capi.ptr(a), a.shape[0]), "vofod_load_apriori", allow)
 
     def ingest_apriori(self, filename: str, tf_xyz=(0.0, 0.0, 0.0), yaw_deg: float = 0.0, sim_correction=(0.0, 0.0, 0.0)):
         """initialize_apriori_map from a .pts/.xyz file (apriori_map/tf/* of sim.yaml); returns (points loaded, voxels set)"""
@@ -189,6 +189,31 @@ class VoFOD:
                 self.sp.oparea_offset[a] = o[a]
             self.map_offset = tuple(self.status().map_offset)
         return st
+
+    # ---- world store (include/vofod.h, WORLD STORE): the voxel map as a window onto a sparse map of a larger box
+    def world_enable(self, margin_lo, margin_hi, max_tiles: int, allow: Sequence[int] = ()):
+        """The box is [-margin_lo, map_size + margin_hi) in world indices (voxels, the window's origin K = 0 now); the pool holds
+        max_tiles tiles of 8 x 8 x 8 voxels (2 KiB each).  From here on map_shift writes what leaves into the store and reads what
+        enters from it, and load_apriori stamps the points beyond the window."""
+        lo = np.ascontiguousarray(margin_lo, dtype=np.int32).reshape(3)
+        hi = np.ascontiguousarray(margin_hi, dtype=np.int32).reshape(3)
+        return self._check(self.lib.world_enable(self.h, capi.ptr(lo), capi.ptr(hi), int(max_tiles)), "vofod_world_enable", allow)
+
+    def world_disable(self, allow: Sequence[int] = ()):
+        return self._check(self.lib.world_disable(self.h), "vofod_world_disable", allow)
+
+    def world_info(self) -> capi.WorldInfo:
+        out = capi.WorldInfo()
+        self._check(self.lib.world_status(self.h, C.byref(out)), "vofod_world_status")
+        return out
+
+    def world_read(self, lo, size) -> np.ndarray:
+        """W over the box of world indices [lo, lo + size) as float32 [size2, size1, size0] (x fastest)"""
+        lo = np.ascontiguousarray(lo, dtype=np.int32).reshape(3)
+        size = np.ascontiguousarray(size, dtype=np.int32).reshape(3)
+        out = np.empty((int(size[2]), int(size[1]), int(size[0])), dtype=np.float32)
+        self._check(self.lib.world_read(self.h, capi.ptr(lo), capi.ptr(size), capi.ptr(out), out.size), "vofod_world_read")
+        return out
 
     def set_column_shift(self, shift_by_row=None, allow: Sequence[int] = ()):
         """vofod_set_column_shift: pixel (row, col) was measured in column (col + shift_by_row[row]) mod width; None = zeros"""
