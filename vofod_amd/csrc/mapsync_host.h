@@ -1,5 +1,6 @@
 // Host side of the map snapshots (kernels and wire header: mapsync.h; contract: include/vofod.h): vofod_map_export,
-// vofod_map_apply and the RCCL broadcast vofod_broadcast_map.  Included by vofod_hip.hip after driver_aux.h and collective.h.
+// vofod_map_apply and the RCCL broadcast vofod_broadcast_map.  Included by vofod_hip.hip after api_gate.h, driver_aux.h, api_maps.h
+// (pick_map) and collective.h.
 #pragma once
 #include <atomic>
 #include <random>
@@ -247,8 +248,7 @@ int ms_apply_locked(vofod_handle* h, const vms::WireHeader& hd, const uint8_t* d
     h->ray_dirty = true;  // (the next raycast_begin clears the accumulator unless a finish sweeps it)
   }
   h->sep_pending = false;  // a sepclusters pass of this handle belongs to the map it replaced
-  for (int t = 0; t < vofod_handle::MAX_INFLIGHT; t++)
-    h->slot(t)->det_valid = false;  // ... and so do the detections vofod_detection_points would answer for
+  forget_detections(h);  // ... and so do the detections vofod_detection_points would answer for
   h->mapbits_valid = false;  // occupancy image, dilated image and nVoxelsOver are rebuilt on next use (as after write_map)
   HIPCHK(hipStreamSynchronize(h->stream));
   s.applied_gen = hd.new_gen;
@@ -322,8 +322,8 @@ int vofod_map_export(vofod_handle* h, int32_t maps, int32_t kind, void* buf, siz
   const bool size_only = !buf;
   if (memspace == VOFOD_MEM_DEVICE && (reinterpret_cast<uintptr_t>(buf) & 3))
     return VOFOD_ERR_INVALID_ARG;  // records are 32-bit words
-  std::scoped_lock lck(h->mtx);
-  (void)hipSetDevice(h->device);
+  ApiLock lock(h);
+  VCHK(admit(h, NEEDS_NOTHING));  // (a pending exact raycast pass travels as its units: ms_export_locked marks the header)
   if (size_only || memspace == VOFOD_MEM_DEVICE)
     return ms_export_locked(h, maps, kind, static_cast<uint8_t*>(buf), cap, size_only, n_bytes);
   // host buffer: emitted into the staging buffer, then copied out
@@ -338,9 +338,8 @@ int vofod_map_apply(vofod_handle* h, const void* buf, size_t n_bytes, int32_t me
     return VOFOD_ERR_INVALID_ARG;
   if (n_bytes < sizeof(vms::WireHeader) || (memspace == VOFOD_MEM_DEVICE && (reinterpret_cast<uintptr_t>(buf) & 3)))
     return VOFOD_ERR_INVALID_ARG;
-  std::scoped_lock lck(h->mtx);
-  (void)hipSetDevice(h->device);
-  VCHK(busy_check(h, false, true));
+  ApiLock lock(h);
+  VCHK(admit(h, MAP_UNREAD));
   vms::WireHeader hd;
   if (memspace == VOFOD_MEM_HOST)
     std::memcpy(&hd, buf, sizeof(hd));
@@ -430,7 +429,7 @@ int vofod_broadcast_map(vofod_comm* c, vofod_handle* h, int32_t root, int32_t ma
   if (!is_root && local == VOFOD_OK)
     local = ms_ensure_wire(h, bytes);
   if (!is_root && local == VOFOD_OK)
-    local = busy_check(h, false, true);
+    local = admit(h, MAP_UNREAD);  // (a local refusal is every rank's: agreed on below)
   int st = VOFOD_OK;
   VCHK(agree(local, &st));
   if (st != VOFOD_OK)

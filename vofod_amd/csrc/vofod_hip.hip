@@ -1512,6 +1512,10 @@ int host_explore_frame(vofod_handle* h, std::vector<HostCluster>& cl, const vt::
 
 #include "frames_launch.h"
 #include "frames_collect.h"
+#include "api_gate.h"
+#include "api_host.h"
 #include "driver_aux.h"
+#include "api_maps.h"
+#include "api_frames.h"
 #include "collective.h"
 #include "mapsync_host.h"
