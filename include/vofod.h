@@ -748,7 +748,7 @@ int vofod_map_shift(vofod_handle* h, const int32_t shift_voxels[3], const float 
  *
  * vofod_reset: W is init everywhere - the directory is emptied, the pool is free, the counters are zero; K, the box and the switch
  * are kept (the reference's reset(), which forgets the a-priori map too).  vofod_write_map, vofod_map_apply, vofod_map_export and
- * vofod_broadcast_map see and change the window only: snapshots do not carry the store, a replica needs its own. */
+ * vofod_broadcast_map see and change the window only: the map snapshots do not carry the store (WORLD SNAPSHOTS below does). */
 #define VOFOD_WORLD_TILE 8
 typedef struct vofod_world_info {
   int32_t enabled, tile_edge;
@@ -768,6 +768,64 @@ int vofod_world_status(vofod_handle* h, vofod_world_info* out);
 /* W over a box of world indices, x fastest, into host memory; n == size[0] * size[1] * size[2] (VOFOD_ERR_SIZE_MISMATCH otherwise).
  * VOFOD_ERR_NOT_PENDING when not enabled; VOFOD_ERR_INVALID_ARG: a size below 1, lo or lo + size beyond +-2^31. */
 int vofod_world_read(vofod_handle* h, const int32_t lo[3], const int32_t size[3], float* dst, size_t n);
+
+/* ------------------------------------------------- WORLD SNAPSHOTS (product library only)
+ *
+ * The store's counterpart of vofod_map_export / vofod_map_apply: a checkpoint keeps the world outside the box, and a ground station
+ * or a second process holds a copy of it to answer vofod_world_read.  The map snapshots above still carry the window only; a restore is
+ *     vofod_create at the checkpoint's offset, vofod_world_enable with the same margins, vofod_world_apply of the chain in order
+ *     (a full snapshot, then its deltas), vofod_map_apply of a full window snapshot.
+ * vofod_world_apply touches none of the three maps.  Both calls answer VOFOD_ERR_NOT_PENDING while the store is off.
+ *
+ * Wire format (little endian; the same bytes in memory and in a file): a 128-byte header
+ *   0 u32 magic 0x44574656 ("VFWD") | 4 u32 version = 1 | 8 u32 kind (0 delta, 1 full) | 12 u32 tile edge (8) | 16 i32[3] map size |
+ *   28 f32[3] map offset (as vofod_status_info) | 40 f32 voxel size | 44 f32 score_init | 48 u64 base_gen (0 for full) | 56 u64 new_gen |
+ *   64 i32[3] K | 76 i32[3] box_lo | 88 i32[3] box_hi | 100 u32 zero | 104 u64 n tiles | 112 u64 shifts_short_of_tiles |
+ *   120 u64 voxels_forgotten
+ * followed by u32 tile[n4], n4 = n rounded up to a multiple of 4: the carried tiles' directory indices (tz * T1 + ty) * T0 + tx
+ * (T = tiles of the box per axis), strictly ascending, the padding entries 0xFFFFFFFF; then n tiles of 512 u32 words, each as the pool
+ * holds it (x fastest inside the tile; the padding voxels beyond box_hi travel verbatim).  Tile words start 16-byte aligned.
+ * Size = 128 + 4 * n4 + 2048 * n.
+ *
+ * Export.  VOFOD_SNAPSHOT_FULL carries every allocated tile - one whose words all equal init too: allocation is state (tiles_used, and
+ * every later all-or-nothing decision, depend on it) - and starts a chain (new_gen).  VOFOD_SNAPSHOT_DELTA carries every tile allocated
+ * since this handle's last export and every tile with any of its 512 words different from what that export carried; without a chain
+ * it is VOFOD_ERR_DELTA_BASE.  The comparison is against a shadow pool as large as the pool (2 KiB per tile of tiles_cap), allocated
+ * by the first export and freed by vofod_world_disable / vofod_destroy; vofod_map_shift and vofod_load_apriori launch what they
+ * launched before.  The owner's chain survives vofod_map_shift and vofod_load_apriori - those are what it records - and ends with
+ * vofod_reset, vofod_world_disable and a vofod_world_apply on the same handle.  Export only reads the store and is admitted like
+ * vofod_map_export (beside batches in flight too).  buf == NULL && cap == 0: size query (*n_bytes set, nothing changes).  cap too
+ * small: VOFOD_ERR_CAPACITY with *n_bytes = the size, generation and shadow untouched.  memspace: VOFOD_MEM_HOST (staged through a
+ * device buffer of the handle) or VOFOD_MEM_DEVICE on the handle's device, 16-byte aligned (VOFOD_ERR_INVALID_ARG otherwise).
+ * VOFOD_ERR_DEVICE: the shadow pool or the staging buffer could not be allocated (the first export asks for as much memory again as
+ * the pool holds); store, generation and chain are as before, and the call may be repeated.
+ *
+ * Apply checks everything before it writes anything, in this order:
+ *   1. format, VOFOD_ERR_INVALID_ARG: magic, version, kind, tile edge, the zero word; the length against n; on the device: indices
+ *      strictly ascending and below this handle's directory length, padding entries 0xFFFFFFFF;
+ *   2. geometry, VOFOD_ERR_SIZE_MISMATCH: map size, voxel size, score_init, box_lo and box_hi equal this handle's, and the origin
+ *      rule below;
+ *   3. chain, VOFOD_ERR_DELTA_BASE: a delta's base_gen is the generation this handle applied last;
+ *   4. capacity, VOFOD_ERR_CAPACITY, all or nothing: the carried tiles this handle has not allocated fit its pool (which may have
+ *      another max_tiles than the owner's).
+ * The window need not sit where the owner's sat.  With d[a] = round((map_offset_handle[a] - map_offset_header[a]) / voxel_size) in
+ * double, the residual must be below voxel_size / 4 (vofod_map_shift's rule), and the handle's origin becomes K = header.K + d, held
+ * inside +-2^30.  A full snapshot empties the store (as vofod_reset does to it) and then sets K; a delta requires the computed K to
+ * equal the handle's own.  The computed K does not change when the owner shifts, so a handle that never shifts follows an owner that
+ * does.  Then existing tiles are overwritten, new ones take slots and both cumulative counters take the header's values: afterwards
+ * vofod_world_status equals the owner's in every field but tiles_cap, and vofod_world_read outside the window equals the owner's.
+ * VOFOD_ERR_BUSY while a submitted batch is pending, as vofod_map_apply.
+ *
+ * The applied chain holds only while vofod_world_apply is the only writer of this handle's store: vofod_map_shift,
+ * vofod_load_apriori, vofod_reset and vofod_world_disable on the applying handle end it (the next delta is VOFOD_ERR_DELTA_BASE, a
+ * full snapshot repairs it) - every such call that returns VOFOD_OK, a shift by zero voxels and a cloud of zero points included.  Why: the replica's own shift writes its window back into its store, and a window that is stale - it is
+ * fed by vofod_map_apply at another rhythm - would overwrite tiles the owner's deltas no longer carry; the two stores would differ
+ * with every check passing.  A live replica therefore shifts first, then takes a full world snapshot and a full window snapshot.
+ *
+ * There is no collective of its own: with VOFOD_MEM_DEVICE on both sides a caller moves the bytes with the broadcast it already has
+ * (RCCL, MPI) between vofod_world_export and vofod_world_apply. */
+int vofod_world_export(vofod_handle* h, int32_t kind, void* buf, size_t cap, int32_t memspace, size_t* n_bytes);
+int vofod_world_apply(vofod_handle* h, const void* buf, size_t n_bytes, int32_t memspace);
 
 #ifdef __cplusplus
 }

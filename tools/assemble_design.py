@@ -107,6 +107,8 @@ for c in r23["configs"]:
                   f"{km['k_world_claim']:.4f} + `k_world_put` {km['k_world_put']:.4f} + `k_world_get` {km['k_world_get']:.4f} ms){vs_parent}")
     parts.append(f"at {c['config']} ({c['sensor']}, M = {c['M'] / 1e6:.1f} M, {c['known_voxels'] / 1e6:.2f} M voxels known, {c['cases'][-1]['tiles_used_after']} tiles used at the end) " + "; ".join(cs))
 sub["R23_MEASURED"] = ". ".join(p[0].upper() + p[1:] for p in parts) + "."
+# §5.17: the first line of profiles/r25_world_sync.txt
+sub["R25_MEASURED"] = (P / "r25_world_sync.txt").read_text().splitlines()[0].removeprefix("measured: ")
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

@@ -323,13 +323,15 @@ _SIGS = {
     "world_disable": (C.c_int, [C.c_void_p]),
     "world_status": (C.c_int, [C.c_void_p, _P(WorldInfo)]),
     "world_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "world_export": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, _P(C.c_size_t)]),
+    "world_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
 }
 
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
                 "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units",
-                "set_point_motion", "deskew_points", "world_enable", "world_disable", "world_status", "world_read")
+                "set_point_motion", "deskew_points", "world_enable", "world_disable", "world_status", "world_read", "world_export", "world_apply")
 
 
 class MsgHeader(C.Structure):

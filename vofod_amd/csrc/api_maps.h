@@ -124,6 +124,7 @@ int vofod_load_apriori(vofod_handle* h, const float* xyz, size_t n)
     }
     HIPCHK(hipStreamSynchronize(h->stream));
   }
+  h->wsync.applied_gen = 0;  // (world snapshots: a call other than vofod_world_apply that may write the store ends the applied chain - a cloud of zero points too, so that the rule has no exception; the owner's chain records it)
   h->sure_background_sufficient = true;  // vofod_nodelet.cpp:343-344
   h->background_pts_sufficient = true;
   h->mapbits_valid = false;
@@ -277,7 +278,10 @@ int vofod_map_shift(vofod_handle* h, const int32_t shift_voxels[3], const float 
     }
   }
   if (same_offset && shift_voxels[0] == 0 && shift_voxels[1] == 0 && shift_voxels[2] == 0)
+  {
+    h->wsync.applied_gen = 0;  // (world snapshots: every successful shift ends the applied chain, the one that moves nothing too - the rule has no exception)
     return VOFOD_OK;
+  }
   const size_t M = h->mg.n;
   HIPCHK(h->d_shift_spare.reserve(std::max<size_t>(M, 4)));  // (it becomes a map: sized as vofod_create sizes them)
   vsh::ShiftParams p{};
@@ -316,8 +320,11 @@ int vofod_map_shift(vofod_handle* h, const int32_t shift_voxels[3], const float 
   }
   HIPCHK(hipStreamSynchronize(h->stream));  // (the call's only one: the store's counters arrive with it)
   if (w.enabled)
+  {
     for (int a = 0; a < 3; a++)
       w.K[a] = static_cast<int32_t>(K1[a]);
+    h->wsync.applied_gen = 0;  // (world snapshots: this handle's own write-back ends the applied chain; the owner's chain records it)
+  }
   h->sp = nsp;
   set_area_geometry(h);
   h->mapbits_valid = false;  // occupancy image, dilated image and nVoxelsOver are rebuilt on next use (as after write_map)
@@ -398,6 +405,7 @@ int vofod_world_disable(vofod_handle* h)
   VCHK(admit(h, MAP_UNREAD));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->world.drop();
+  h->wsync.drop();  // (the shadow pool, the scratch and both chains of the world snapshots)
   return VOFOD_OK;
 }
 

@@ -640,6 +640,7 @@ int vofod_reset(vofod_handle* h)
   VCHK(admit(h, WS0_FREE | MAP_UNREAD));
   if (h->world.enabled)
     VCHK(world_clear(h));  // W is init everywhere: K, the box and the switch stay (do_reset synchronises)
+  h->wsync.end_chains();  // (world snapshots: the slots are handed out again, and a follower's store is no longer what it applied)
   const int r = do_reset(h);
   h->sure_background_sufficient = false;
   h->background_pts_sufficient = false;

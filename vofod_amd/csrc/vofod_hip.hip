@@ -39,6 +39,7 @@
 #include "detection_points.h"
 #include "map_shift.h"
 #include "world_store.h"
+#include "world_sync.h"
 
 using namespace vk;
 
@@ -484,6 +485,7 @@ struct vofod_handle
   DevBuf<float> d_map, d_flags, d_ray;
   DevBuf<float> d_shift_spare;  // vofod_map_shift: destination of the out-of-place shift, swapped with the map it received (allocated on the first shift)
   vws::Store world;  // vofod_world_enable: the voxel map is a window onto it (world_store.h); indexed by world index, so no shift moves it
+  vwy::State wsync;  // snapshots / deltas of the store (world_sync.h, world_sync_host.h): shadow pool, scratch and the two chains
   DevBuf<unsigned long long> d_mapbits;
   DevBuf<unsigned long long> d_mapclose;  // d_mapbits dilated by hasCloseTo's stencil (k_dilate), valid while gens match
   uint64_t mapbits_gen = 0, mapclose_gen = ~0ull;
@@ -1519,3 +1521,4 @@ int host_explore_frame(vofod_handle* h, std::vector<HostCluster>& cl, const vt::
 #include "api_frames.h"
 #include "collective.h"
 #include "mapsync_host.h"
+#include "world_sync_host.h"

@@ -266,6 +266,36 @@ class VoFOD:
         b = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else buf, dtype=np.uint8).reshape(-1)
         self._check(self.lib.map_apply(self.h, capi.ptr(b), b.size, capi.MEM_HOST), "vofod_map_apply")
 
+    def world_export(self, kind: int = capi.SNAPSHOT_FULL, device=False, allow: Sequence[int] = ()):
+        """A full snapshot (capi.SNAPSHOT_FULL) or a delta (capi.SNAPSHOT_DELTA) of the world store in the wire format of
+        vofod_amd.mapsync.decode_world, as a uint8 array.  `device` = (address, capacity in bytes) on the handle's device, 16-byte
+        aligned: the record is written there - for a collective of the caller's - and its size in bytes comes back.  A delta follows
+        this handle's last export (ERR_DELTA_BASE without one).  A status in `allow` is returned in place of the result.  Without
+        `device` the library is asked twice - the size query, then the export - and each runs the select pass (for a delta: the
+        compare of every allocated tile with the shadow); a caller who minds passes a device buffer large enough."""
+        n = C.c_size_t(0)
+        if device:
+            addr, cap = device
+            st = self.lib.world_export(self.h, int(kind), C.c_void_p(int(addr)), int(cap), capi.MEM_DEVICE, C.byref(n))
+            return n.value if st == capi.OK else self._check(st, "vofod_world_export", allow)
+        st = self.lib.world_export(self.h, int(kind), None, 0, capi.MEM_HOST, C.byref(n))
+        if st != capi.OK:
+            return self._check(st, "vofod_world_export", allow)
+        buf = np.empty(n.value, dtype=np.uint8)
+        st = self.lib.world_export(self.h, int(kind), capi.ptr(buf), buf.size, capi.MEM_HOST, C.byref(n))
+        if st != capi.OK:
+            return self._check(st, "vofod_world_export", allow)
+        return buf[: n.value]
+
+    def world_apply(self, buf, allow: Sequence[int] = ()):
+        """apply a world snapshot or delta: bytes / a uint8 array (world_export, a file, another process), or a pair (address, size in
+        bytes) in the handle's device memory.  Returns the status (one in `allow` leaves the handle as it was)."""
+        if isinstance(buf, tuple):
+            addr, n = buf
+            return self._check(self.lib.world_apply(self.h, C.c_void_p(int(addr)), int(n), capi.MEM_DEVICE), "vofod_world_apply", allow)
+        b = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else buf).view(np.uint8).reshape(-1)
+        return self._check(self.lib.world_apply(self.h, capi.ptr(b), b.size, capi.MEM_HOST), "vofod_world_apply", allow)
+
     def save_map(self, path, maps: int = capi.MAPS_ALL, full: bool = True) -> int:
         """checkpoint: export_map written to `path`; returns its size in bytes"""
         buf = self.export_map(maps, full)

@@ -5,6 +5,9 @@ Independent of the library: `encode` builds the bytes the library writes, `decod
 Byte 112, the first of the header's 16 reserved bytes, holds S + 1 when the snapshot carries a pending EXACT raycast pass with the
 raycast map in its mask (include/vofod.h, EXACT RAYCAST ACCUMULATION: the raycast records are then uint32 units, 2^S per metre) and
 0 otherwise; the other 15 are zero.  `Snapshot.raycast_log2_units` carries it (None: no such pass).
+
+The world store travels in a format of its own (vofod_world_export / vofod_world_apply): `WorldSnapshot`, `encode_world`,
+`decode_world` at the end of this module.
 """
 from __future__ import annotations
 
@@ -156,3 +159,105 @@ def apply_to(s: Snapshot, maps: dict) -> dict:
         cur[idx] = bits
         out[m] = cur.view(np.float32)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# World snapshots (include/vofod.h, WORLD SNAPSHOTS: vofod_world_export / vofod_world_apply): the tiles of the world store.
+# A 128-byte header, u32 tile[n4] (n4 = n rounded up to a multiple of 4; directory indices, strictly ascending, padding 0xFFFFFFFF),
+# then n tiles of 512 u32 words as the pool holds them.
+WORLD_MAGIC = 0x44574656  # "VFWD"
+WORLD_VERSION = 1
+WORLD_TILE = 8
+WORLD_TILE_WORDS = WORLD_TILE ** 3
+WORLD_PAD = 0xFFFFFFFF
+
+WORLD_HEADER = np.dtype(
+    {
+        "names": ["magic", "version", "kind", "tile_edge", "map_size", "map_offset", "voxel_size", "score_init", "base_gen", "new_gen", "origin", "box_lo", "box_hi", "zero", "n_tiles",
+                  "shifts_short_of_tiles", "voxels_forgotten"],
+        "formats": ["<u4", "<u4", "<u4", "<u4", ("<i4", 3), ("<f4", 3), "<f4", "<f4", "<u8", "<u8", ("<i4", 3), ("<i4", 3), ("<i4", 3), "<u4", "<u8", "<u8", "<u8"],
+        "offsets": [0, 4, 8, 12, 16, 28, 40, 44, 48, 56, 64, 76, 88, 100, 104, 112, 120],
+        "itemsize": HEADER_BYTES,
+    }
+)
+
+
+@dataclass
+class WorldSnapshot:
+    kind: int
+    map_size: tuple
+    map_offset: tuple
+    voxel_size: float
+    score_init: float
+    origin: tuple  # K: the world index of the owner's window voxel (0, 0, 0)
+    box_lo: tuple
+    box_hi: tuple
+    base_gen: int = 0
+    new_gen: int = 0
+    shifts_short_of_tiles: int = 0
+    voxels_forgotten: int = 0
+    index: np.ndarray = field(default_factory=lambda: np.zeros(0, np.uint32))  # directory indices (tz * T1 + ty) * T0 + tx, ascending
+    tiles: np.ndarray = field(default_factory=lambda: np.zeros((0, WORLD_TILE_WORDS), np.uint32))  # [n, 512], z / y / x inside a tile
+
+    @property
+    def tiles_per_axis(self) -> tuple:
+        return tuple(-(-(int(h) - int(l)) // WORLD_TILE) for l, h in zip(self.box_lo, self.box_hi))
+
+    def tile_origin(self, k: int) -> tuple:
+        """world index of voxel (0, 0, 0) of carried tile k"""
+        T = self.tiles_per_axis
+        d = int(self.index[k])
+        t = (d % T[0], (d // T[0]) % T[1], d // (T[0] * T[1]))
+        return tuple(int(self.box_lo[a]) + WORLD_TILE * t[a] for a in range(3))
+
+
+def world_nbytes(n: int) -> int:
+    """size of a world snapshot of n tiles"""
+    return HEADER_BYTES + 4 * (-(-int(n) // 4) * 4) + 4 * WORLD_TILE_WORDS * int(n)
+
+
+def encode_world(s: WorldSnapshot) -> np.ndarray:
+    """the bytes of world snapshot `s` (uint8)"""
+    idx = np.ascontiguousarray(s.index, dtype="<u4").reshape(-1)
+    tiles = np.ascontiguousarray(s.tiles, dtype="<u4").reshape(-1, WORLD_TILE_WORDS)
+    if tiles.shape[0] != idx.size:
+        raise ValueError("world snapshot: one tile of 512 words per index")
+    h = np.zeros(1, dtype=WORLD_HEADER)
+    h["magic"], h["version"], h["kind"], h["tile_edge"] = WORLD_MAGIC, WORLD_VERSION, s.kind, WORLD_TILE
+    h["map_size"], h["map_offset"] = np.asarray(s.map_size, dtype=np.int32), np.asarray(s.map_offset, dtype=np.float32)
+    h["voxel_size"], h["score_init"], h["base_gen"], h["new_gen"] = s.voxel_size, s.score_init, s.base_gen, s.new_gen
+    h["origin"], h["box_lo"], h["box_hi"] = np.asarray(s.origin, dtype=np.int32), np.asarray(s.box_lo, dtype=np.int32), np.asarray(s.box_hi, dtype=np.int32)
+    h["n_tiles"], h["shifts_short_of_tiles"], h["voxels_forgotten"] = idx.size, s.shifts_short_of_tiles, s.voxels_forgotten
+    lst = np.full(-(-idx.size // 4) * 4, WORLD_PAD, dtype="<u4")
+    lst[: idx.size] = idx
+    return np.concatenate([h.view(np.uint8).reshape(-1), lst.view(np.uint8), tiles.reshape(-1).view(np.uint8)])
+
+
+def decode_world(buf, check: bool = True) -> WorldSnapshot:
+    """parse a world snapshot; ValueError on a bad magic / version / kind / tile edge / reserved word / length, or (check) indices not
+    strictly ascending, beyond the box's directory, or a padding entry other than 0xFFFFFFFF"""
+    b = np.frombuffer(memoryview(buf), dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    if b.size < HEADER_BYTES:
+        raise ValueError(f"world snapshot: {b.size} bytes, shorter than the {HEADER_BYTES}-byte header")
+    h = b[:HEADER_BYTES].view(WORLD_HEADER)[0]
+    if int(h["magic"]) != WORLD_MAGIC:
+        raise ValueError(f"world snapshot: bad magic {int(h['magic']):#x}")
+    if int(h["version"]) != WORLD_VERSION:
+        raise ValueError(f"world snapshot: unknown version {int(h['version'])}")
+    if int(h["kind"]) not in (KIND_DELTA, KIND_FULL) or int(h["tile_edge"]) != WORLD_TILE or int(h["zero"]) != 0:
+        raise ValueError("world snapshot: bad kind, tile edge or reserved word")
+    n = int(h["n_tiles"])
+    if b.size != world_nbytes(n):
+        raise ValueError(f"world snapshot: {b.size} bytes, the header asks for {world_nbytes(n)}")
+    n4 = -(-n // 4) * 4
+    lst = b[HEADER_BYTES : HEADER_BYTES + 4 * n4].view("<u4")
+    s = WorldSnapshot(kind=int(h["kind"]), map_size=tuple(int(v) for v in h["map_size"]), map_offset=tuple(float(v) for v in h["map_offset"]), voxel_size=float(h["voxel_size"]),
+                      score_init=float(h["score_init"]), origin=tuple(int(v) for v in h["origin"]), box_lo=tuple(int(v) for v in h["box_lo"]), box_hi=tuple(int(v) for v in h["box_hi"]),
+                      base_gen=int(h["base_gen"]), new_gen=int(h["new_gen"]), shifts_short_of_tiles=int(h["shifts_short_of_tiles"]), voxels_forgotten=int(h["voxels_forgotten"]))
+    s.index = lst[:n].copy()
+    s.tiles = b[HEADER_BYTES + 4 * n4 :].view("<u4").reshape(n, WORLD_TILE_WORDS).copy()
+    if check:
+        n_dir = int(np.prod(np.asarray(s.tiles_per_axis, dtype=np.int64)))
+        if np.any(lst[n:] != WORLD_PAD) or (n and (np.any(s.index[1:] <= s.index[:-1]) or int(s.index[-1]) >= n_dir)):
+            raise ValueError("world snapshot: tile indices not strictly ascending, beyond the box, or bad padding")
+    return s
