@@ -73,7 +73,7 @@ struct Cloud
 
 int main(int argc, char** argv)
 {
-  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0;
+  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0;
   float voxel = 0.5f;
   std::string apriori;
   for (int i = 1; i + 1 < argc; i += 2)
@@ -93,6 +93,8 @@ int main(int argc, char** argv)
       period_ms = std::atoi(argv[i + 1]);
     else if (k == "--extents")  // 1: after each scan, the member count and the AABB of every detection (vofod_detection_points)
       extents = std::atoi(argv[i + 1]);
+    else if (k == "--pixels")  // 1: after each scan, the number of raw returns of every detection and their (row, col) rectangle (vofod_detection_pixels)
+      pixels = std::atoi(argv[i + 1]);
   }
   const float vfov = 45.0f * 3.14159265f / 180.0f;
   vofod_static_params sp;
@@ -230,6 +232,30 @@ int main(int argc, char** argv)
                         e.aabb_min[0], e.aabb_min[1], e.aabb_min[2], e.aabb_max[0], e.aabb_max[1], e.aabb_max[2]);
           }
       }
+    }
+    if (pixels && n_det)
+    {
+      // the sensor returns behind every detection: their pixels in the organised scan, for a camera cue or a tracker's re-fit
+      size_t n_span = 0, n_px = 0;
+      if (vofod_detection_pixels(h, VOFOD_POINTS_SYNC, nullptr, 0, &n_span, nullptr, nullptr, nullptr, 0, &n_px, VOFOD_MEM_HOST) == VOFOD_OK)
+      {
+        std::vector<vofod_detection_span> span(n_span);
+        std::vector<uint32_t> px(n_px);
+        if (vofod_detection_pixels(h, VOFOD_POINTS_SYNC, span.data(), n_span, &n_span, px.data(), nullptr, nullptr, n_px, &n_px, VOFOD_MEM_HOST) == VOFOD_OK)
+          for (const vofod_detection_span& sdet : span)
+          {
+            // (the rectangle does not know that column 0 follows column cols - 1: a target across the seam spans the whole width)
+            uint32_t r0 = rows, r1 = 0, c0 = cols, c1 = 0;
+            for (uint32_t i = sdet.first; i < sdet.first + sdet.count; i++)
+            {
+              const uint32_t r = px[i] / static_cast<uint32_t>(cols), cc = px[i] % static_cast<uint32_t>(cols);
+              r0 = std::min(r0, r), r1 = std::max(r1, r), c0 = std::min(c0, cc), c1 = std::max(c1, cc);
+            }
+            std::printf("scan %3d detection id %u pixels: %u returns, rows %u-%u, cols %u-%u\n", k, sdet.id, sdet.count, r0, r1, c0, c1);
+          }
+      }
+      else
+        std::fprintf(stderr, "detection_pixels: %s\n", vofod_last_error_string(h));
     }
     detection_cv.notify_one();  // :951
     if (!raycast_running.exchange(true))  // :953-957

@@ -600,6 +600,51 @@ int vofod_detection_points(vofod_handle* h, int source,
                            vofod_point_xyzr* points, uint32_t* index /* nullable */, size_t points_cap, size_t* n_points,
                            int32_t points_memspace);
 
+/* ------------------------------------------------- raw returns of the detections: their scan pixels (product library only)
+ *
+ * vofod_detection_points stops at voxel centres.  This call hands out the sensor returns themselves: for every detection the
+ * pixels i = row * width + col of its frame's organised scan that fell into its member voxels - for a tracker that re-fits the
+ * target, a camera cue that needs (row, col) in the range image, a logger, a classifier fed the cut-out points.  Answered on the
+ * device (k_det_pixels, vofod_amd/csrc/detection_pixels.h) from what the production call left in the workspace.
+ *
+ * Definition.  Pixel i of frame f belongs to detection d iff (1) the pipeline kept its point: finite, outside the closed exclude
+ * box, inside the closed operation area after the transform with the frame's tf (pcl association, every op rounded), and (2) its
+ * VoxelGridWeighted cell - floor((q - offset) * inv_leaf) per axis in float32 with the FRAME'S OWN lattice offset
+ * (voxel_grid_weighted.cpp:131-136) - is the cell of a member voxel of d.  The point is the one the pipeline consumed: the decoded
+ * point of a range image, the compensated point of a scan with col_tfs.
+ *
+ * source, validity, refusals: exactly as vofod_detection_points (VOFOD_POINTS_SYNC or a collected ticket; VOFOD_ERR_NOT_PENDING
+ * when the source is not valid, never stale data; VOFOD_ERR_INVALID_ARG for a source outside -1..7, a bad memspace or alignment,
+ * NULL count pointers, member or xyz without pixels).
+ * span       one record per detection, in the order of the detections returned; always host memory.
+ * pixels     the pixel indices of detection 0, then those of detection 1, and so on; within a detection they ascend.
+ * member     optional: per pixel, the position of its voxel in that detection's list as vofod_detection_points returns it
+ *            (points[ext.first + member] is the voxel the return fell into).
+ * xyz        optional: per pixel the transformed point q, 3 floats, bit for bit what the voxel grid consumed.
+ * pixels, member and xyz live in memspace: VOFOD_MEM_HOST, or VOFOD_MEM_DEVICE on the handle's device with 4-byte alignment.
+ *
+ * Invariant: span.count is the sum of the weights (vofod_point_xyzr::r bits, the returns per voxel) of the detection's member
+ * voxels, and every member voxel gets exactly its weight in pixels.  The library holds every answer to the first half: a
+ * detection whose returns do not number the sum of its weights makes the call return VOFOD_ERR_DEVICE with nothing written to any
+ * output; vofod_last_error_string names the detection.
+ * One rule of its own: device-resident scan columns (memspace VOFOD_MEM_DEVICE of the scan) are read in place, once more, by
+ * this call - the caller leaves them unchanged from the production call until it has asked.  Host-resident scans, range images
+ * and scans with col_tfs are answered from the library's staging slot and need nothing kept.
+ *
+ * Size query: span == NULL && pixels == NULL sets *n_span and *n_pixels and returns VOFOD_OK; the first query after a production
+ * call launches the small sizing kernel (one workgroup per detection sums the weights), never the pixel walk.  A NULL span or a
+ * NULL pixels alone leaves that output out.  VOFOD_ERR_CAPACITY: span_cap or pixels_cap is too small; both counts are set and
+ * nothing is written.  The call only reads the workspace, runs on the workspace's own chain stream and waits for that stream
+ * only.  With zero detections there is no launch. */
+typedef struct vofod_detection_span {   /* 16 bytes, one per detection, in the order of the detections returned */
+  uint32_t id, frame;                   /* as in the vofod_detection it belongs to */
+  uint32_t first, count;                /* its returns are pixels[first .. first + count) */
+} vofod_detection_span;
+int vofod_detection_pixels(vofod_handle* h, int source,
+                           vofod_detection_span* span, size_t span_cap, size_t* n_span,
+                           uint32_t* pixels, uint32_t* member /* nullable */, float* xyz /* nullable, 3 per pixel */,
+                           size_t pixels_cap, size_t* n_pixels, int32_t memspace);
+
 /* ------------------------------------------------- batched mode: the collective (product library only)
  *
  * one process per GPU runs vofod_process_batch / vofod_batch_submit+collect on its own block of frames; the only

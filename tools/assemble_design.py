@@ -109,6 +109,10 @@ for c in r23["configs"]:
 sub["R23_MEASURED"] = ". ".join(p[0].upper() + p[1:] for p in parts) + "."
 # §5.17: the first line of profiles/r25_world_sync.txt
 sub["R25_MEASURED"] = (P / "r25_world_sync.txt").read_text().splitlines()[0].removeprefix("measured: ")
+# §5.18: the lines of profiles/r26_detection_pixels.txt that begin with "measured: ", "bench: " and "mutations: "
+r26 = (P / "r26_detection_pixels.txt").read_text().splitlines()
+for name, prefix in (("R26_MEASURED", "measured: "), ("R26_BENCH", "bench: "), ("R26_MUTATIONS", "mutations: ")):
+    sub[name] = next(l for l in r26 if l.startswith(prefix)).removeprefix(prefix)
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

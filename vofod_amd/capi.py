@@ -218,6 +218,8 @@ assert C.sizeof(WorldInfo) == 80
 
 DETECTION_EXTENT = np.dtype([("id", "<u4"), ("frame", "<u4"), ("first", "<u4"), ("count", "<u4"), ("aabb_min", "<f4", 3), ("aabb_max", "<f4", 3)])
 assert DETECTION_EXTENT.itemsize == C.sizeof(DetectionExtent) == 40
+DETECTION_SPAN = np.dtype([("id", "<u4"), ("frame", "<u4"), ("first", "<u4"), ("count", "<u4")])  # vofod_detection_span
+assert DETECTION_SPAN.itemsize == 16
 
 POINT_XYZR = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("range", "<u4")])
 DETECTION = np.dtype(
@@ -311,6 +313,7 @@ _SIGS = {
     "broadcast_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_size_t)]),
     "range_to_points": (C.c_int, [C.c_void_p, _P(Scan), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "detection_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_int32]),
+    "detection_pixels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_int32]),
     "map_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "set_column_shift": (C.c_int, [C.c_void_p, C.c_void_p]),
     "column_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -330,7 +333,7 @@ _SIGS = {
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
-                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "map_shift", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units",
+                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "detection_pixels", "map_shift", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units",
                 "set_point_motion", "deskew_points", "world_enable", "world_disable", "world_status", "world_read", "world_export", "world_apply")
 
 

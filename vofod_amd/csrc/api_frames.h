@@ -294,4 +294,119 @@ int vofod_detection_points(vofod_handle* h, int source, vofod_detection_extent* 
   return VOFOD_OK;
 }
 
+int vofod_detection_pixels(vofod_handle* h, int source, vofod_detection_span* span, size_t span_cap, size_t* n_span, uint32_t* pixels, uint32_t* member, float* xyz, size_t pixels_cap,
+                           size_t* n_pixels, int32_t memspace)
+{
+  if (!h || !n_span || !n_pixels || source < VOFOD_POINTS_SYNC || source >= vofod_handle::MAX_INFLIGHT || (memspace != VOFOD_MEM_HOST && memspace != VOFOD_MEM_DEVICE) ||
+      ((member || xyz) && !pixels))
+    return VOFOD_ERR_INVALID_ARG;
+  if (memspace == VOFOD_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(pixels) | reinterpret_cast<uintptr_t>(member) | reinterpret_cast<uintptr_t>(xyz)) & 3))
+    return VOFOD_ERR_INVALID_ARG;
+  ApiLock lock(h);
+  VCHK(admit(h, NEEDS_NOTHING));
+  const int t = source == VOFOD_POINTS_SYNC ? 0 : source;
+  Workspace& ws = *h->slot(t);
+  if (!ws.det_valid || ws.det_submitted != (source != VOFOD_POINTS_SYNC))
+    return VOFOD_ERR_NOT_PENDING;
+  const size_t n = ws.det_refs.size();
+  *n_span = n;
+  *n_pixels = 0;
+  if (n == 0)
+    return VOFOD_OK;  // (no detections: no launch, whatever was asked)
+  // on the workspace's own chain stream (everything that wrote the workspace has been waited for by its collect half)
+  VCHK(ensure_chain_stream(h, t));
+  StreamScope scope(h, h->chain_stream[t]);
+  std::vector<vpx::PixDesc> descs(n);
+  size_t members = 0;
+  for (size_t i = 0; i < n; i++)
+  {
+    const Workspace::DetRef& r = ws.det_refs[i];
+    descs[i] = vpx::PixDesc{r.frame, r.root, r.n_points, static_cast<uint32_t>(members), 0u, 0u, {0u, 0u}};
+    members += r.n_points;
+  }
+  if (members > 0xffffffffull)
+  {
+    h->err = "detection pixels: more than 2^32 member voxels";
+    return VOFOD_ERR_DEVICE;
+  }
+  HIPCHK(ws.d_pxdesc.reserve(n));
+  // ---- the counts: the sizing kernel, once per validity (the record builders clear what it found)
+  if (ws.det_px_sizes.size() != n)
+  {
+    std::vector<vpx::PixSize> sizes(n);
+    HIPCHK(ws.d_pxsize.reserve(n));
+    HIPCHK(hipMemcpyAsync(ws.d_pxdesc, descs.data(), sizeof(vpx::PixDesc) * n, hipMemcpyHostToDevice, h->stream));
+    KLAUNCH(h, vpx::k_det_pixel_sizes, dim3(static_cast<uint32_t>(n)), dim3(vpx::PX_THREADS), ws.d_hdrs, ws.d_cand, ws.va.pts, ws.det_vox_cap, ws.d_pxdesc, ws.d_pxsize);
+    HIPCHK(hipMemcpyAsync(sizes.data(), ws.d_pxsize, sizeof(vpx::PixSize) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; i++)
+      if (sizes[i].members != descs[i].n_points)
+      {
+        h->err = "detection pixels: detection " + std::to_string(ws.det_refs[i].id) + " has " + std::to_string(descs[i].n_points) + " points, its cluster " + std::to_string(sizes[i].members) +
+                 " entries in the frame's member list";
+        return VOFOD_ERR_DEVICE;
+      }
+    ws.det_px_sizes = std::move(sizes);
+  }
+  size_t total = 0;
+  for (size_t i = 0; i < n; i++)
+  {
+    descs[i].first = static_cast<uint32_t>(total);
+    descs[i].count = ws.det_px_sizes[i].count;
+    total += descs[i].count;
+  }
+  *n_pixels = total;
+  if (!span && !pixels)
+    return VOFOD_OK;  // size query
+  if ((span && span_cap < n) || (pixels && pixels_cap < total))
+    return VOFOD_ERR_CAPACITY;
+  if (total > 0xffffffffull)
+  {
+    h->err = "detection pixels: more than 2^32 returns";
+    return VOFOD_ERR_DEVICE;
+  }
+  if (pixels)
+  {
+    // ---- the walk, into the workspace's staging buffers (16-byte aligned; the caller's need not be)
+    HIPCHK(ws.d_pxfound.reserve(n));
+    HIPCHK(ws.d_pxkey.reserve(members));
+    HIPCHK(ws.d_pxrank.reserve(members));
+    HIPCHK(ws.d_pxidx.reserve(total));
+    HIPCHK(ws.d_pxmember.reserve(total));
+    HIPCHK(ws.d_pxxyz.reserve(3 * total));
+    std::vector<vpx::PixFound> found(n);
+    HIPCHK(hipMemcpyAsync(ws.d_pxdesc, descs.data(), sizeof(vpx::PixDesc) * n, hipMemcpyHostToDevice, h->stream));
+    KLAUNCH(h, vpx::k_det_pixels, dim3(static_cast<uint32_t>(n)), dim3(vpx::PX_THREADS), ws.d_args, ws.det_g, ws.d_hdrs, ws.d_cand, ws.va.pts, ws.det_vox_cap, ws.d_pxdesc, ws.d_pxkey, ws.d_pxrank,
+            ws.d_pxidx, ws.d_pxmember, ws.d_pxxyz, ws.d_pxfound);
+    HIPCHK(hipMemcpyAsync(found.data(), ws.d_pxfound, sizeof(vpx::PixFound) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; i++)
+      if (found[i].members != descs[i].n_points || found[i].bad || found[i].pixels != descs[i].count)
+      {
+        const std::string who = "detection pixels: detection " + std::to_string(ws.det_refs[i].id) + " (frame " + std::to_string(ws.det_refs[i].frame) + ")";
+        if (found[i].members != descs[i].n_points)
+          h->err = who + " has " + std::to_string(descs[i].n_points) + " points, its cluster " + std::to_string(found[i].members) + " entries in the frame's member list";
+        else if (found[i].bad)
+          h->err = who + ": " + std::to_string(found[i].bad) + " member centres are no cell centres of the frame's lattice";
+        else
+          h->err = who + ": its member voxels weigh " + std::to_string(descs[i].count) + " returns, the frame's columns hold " + std::to_string(found[i].pixels) +
+                   " (were device-resident columns changed since the scan ran?)";
+        return VOFOD_ERR_DEVICE;
+      }
+    const hipMemcpyKind kind = memspace == VOFOD_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (total)
+    {
+      HIPCHK(hipMemcpyAsync(pixels, ws.d_pxidx, sizeof(uint32_t) * total, kind, h->stream));
+      if (member)
+        HIPCHK(hipMemcpyAsync(member, ws.d_pxmember, sizeof(uint32_t) * total, kind, h->stream));
+      if (xyz)
+        HIPCHK(hipMemcpyAsync(xyz, ws.d_pxxyz, sizeof(float) * 3 * total, kind, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    }
+  }
+  for (size_t i = 0; span && i < n; i++)
+    span[i] = vofod_detection_span{ws.det_refs[i].id, ws.det_refs[i].frame, descs[i].first, descs[i].count};
+  return VOFOD_OK;
+}
+
 }  // extern "C"

@@ -115,8 +115,9 @@ int raycast_begin_locked(vofod_handle* h, const vofod_scan* scan, const float tf
   }
   else
   {
-    const int r = stage_cloud(h, h->ws, 0, scan->x ? scan->x : scan->intensity, scan->y ? scan->y : scan->intensity, scan->z ? scan->z : scan->intensity,
-                              scan->intensity, scan->range, scan->stride_bytes, n, VOFOD_MEM_HOST, 0, nullptr);
+    // (only the two columns the raycast reads are staged: columns 0-2 of the slot stay what the last launch left there, which
+    // vofod_detection_pixels may still be asked about - under VOFOD_SCAN_AUTO_RAYCAST they hold this very scan's points)
+    const int r = stage_cloud(h, h->ws, 0, nullptr, nullptr, nullptr, scan->intensity, scan->range, scan->stride_bytes, n, VOFOD_MEM_HOST, 0, nullptr);
     if (r != VOFOD_OK)
       return r;
     float* base = h->ws.d_stage;

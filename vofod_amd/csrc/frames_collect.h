@@ -68,7 +68,7 @@ struct RecordSink
   RecordSink(vofod_handle* h_, Workspace& ws_, const FrameCall& call_, vofod_detection* out_, size_t cap_, uint32_t* n_out_per_frame_)
       : h(h_), ws(ws_), call(call_), out(out_), cap(cap_), n_out_per_frame(n_out_per_frame_)
   {
-    ws.det_begin(call.submitted, call.g.vox_cap);
+    ws.det_begin(call.submitted, call.g);
   }
   void add(uint32_t f, uint32_t root, const float center[3], uint32_t n_points, double conf_sum)
   {
@@ -477,7 +477,9 @@ int collect_frames(vofod_handle* h, Workspace& ws, FrameCall& call, vofod_detect
   const uint32_t n = call.n;
   if (n == 0)
   {
-    ws.det_begin(call.submitted, ws.vox_cap);
+    GridParams g{};
+    g.vox_cap = ws.vox_cap;
+    ws.det_begin(call.submitted, g);
     ws.det_valid = true;  // (no frames, no detections: vofod_detection_points answers 0 / 0)
     return VOFOD_OK;      // (*n_out is zero already: the entry points clear it)
   }

@@ -37,6 +37,7 @@
 #include "range_decode.h"
 #include "point_deskew.h"
 #include "detection_points.h"
+#include "detection_pixels.h"
 #include "map_shift.h"
 #include "world_store.h"
 #include "world_sync.h"
@@ -307,17 +308,28 @@ struct Workspace
   bool det_valid = false;
   bool det_submitted = false;  // ... by vofod_batch_collect (the ticket's source) rather than a synchronous call (VOFOD_POINTS_SYNC)
   uint32_t det_vox_cap = 0;    // stride of the frame slots the batch ran with
-  void det_begin(bool submitted, uint32_t stride)
+  // vofod_detection_pixels reads the frames' columns as well (detection_pixels.h lists their writers): the GridParams of the launch
+  // (crop boxes, leaf), and the counts of the sizing kernel once a call has asked for them
+  GridParams det_g{};
+  std::vector<vpx::PixSize> det_px_sizes;
+  void det_begin(bool submitted, const GridParams& g)
   {
     det_refs.clear();
+    det_px_sizes.clear();
     det_valid = false;
     det_submitted = submitted;
-    det_vox_cap = stride;
+    det_vox_cap = g.vox_cap;
+    det_g = g;
   }
   DevBuf<vdp::DetDesc> d_detdesc;  // staging of a query, grown on use
   DevBuf<vdp::DetBox> d_detbox;
   DevBuf<float4> d_detpts;
   DevBuf<uint32_t> d_detidx;
+  DevBuf<vpx::PixDesc> d_pxdesc;  // ... and of a vofod_detection_pixels query
+  DevBuf<vpx::PixSize> d_pxsize;
+  DevBuf<vpx::PixFound> d_pxfound;
+  DevBuf<uint32_t> d_pxkey, d_pxrank, d_pxidx, d_pxmember;
+  DevBuf<float> d_pxxyz;
   // state of a submitted, not yet collected batch (vofod_batch_submit / vofod_batch_collect)
   bool pending = false;
   uint32_t job_n = 0;

@@ -478,6 +478,34 @@ class VoFOD:
             return self._check(st, "vofod_detection_points", allow)
         return ext, pts, idx
 
+    def detection_pixels(self, source: int = capi.POINTS_SYNC, device_out=None, allow: Sequence[int] = ()):
+        """The raw returns of the detections returned last from `source` (vofod_detection_pixels): which pixels row * width + col of
+        their frames' scans fell into their member voxels.  Returns (span, pixels, member, xyz): one capi.DETECTION_SPAN record per
+        detection in the order returned, the pixel indices - detection by detection, ascending - per pixel the position of its voxel
+        in the detection's list of detection_points, and the transformed points as an (n, 3) float32 array.  `device_out` = (pixels
+        address, member address or None, xyz address or None, capacity in pixels) on the handle's device: the three go there and
+        (span, None, None, None) comes back.  A status in `allow` is returned in place of the tuple."""
+        n_span, n_px = C.c_size_t(0), C.c_size_t(0)
+        st = self.lib.detection_pixels(self.h, int(source), None, 0, C.byref(n_span), None, None, None, 0, C.byref(n_px), capi.MEM_HOST)
+        if st != capi.OK:
+            return self._check(st, "vofod_detection_pixels", allow)
+        span = np.zeros(n_span.value, dtype=capi.DETECTION_SPAN)
+        if device_out is not None:
+            d_px, d_member, d_xyz, cap = device_out
+            opt = lambda a: None if a is None else C.c_void_p(int(a))
+            st = self.lib.detection_pixels(self.h, int(source), capi.ptr(span), span.size, C.byref(n_span), C.c_void_p(int(d_px)), opt(d_member), opt(d_xyz), int(cap), C.byref(n_px),
+                                           capi.MEM_DEVICE)
+            if st != capi.OK:
+                return self._check(st, "vofod_detection_pixels", allow)
+            return span, None, None, None
+        px = np.zeros(n_px.value, dtype=np.uint32)
+        member = np.zeros(n_px.value, dtype=np.uint32)
+        xyz = np.zeros((n_px.value, 3), dtype=np.float32)
+        st = self.lib.detection_pixels(self.h, int(source), capi.ptr(span), span.size, C.byref(n_span), capi.ptr(px), capi.ptr(member), capi.ptr(xyz), px.size, C.byref(n_px), capi.MEM_HOST)
+        if st != capi.OK:
+            return self._check(st, "vofod_detection_pixels", allow)
+        return span, px, member, xyz
+
     # ------------------------------------------------- stateless L4 helpers
     def voxel_grid_weighted(self, x, y, z, leaf: float, align_center=None):
         return voxel_grid_weighted(self.lib, x, y, z, leaf, align_center, handle=self.h)
