@@ -10,6 +10,7 @@
 // the nodelet receives from the Ouster driver: organised h x w xyz + range in mm, zeros for no return.
 //
 //   vofod_replay [--scans N] [--rows H] [--cols W] [--voxel S] [--apriori file.xyz] [--period-ms P]
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -73,7 +74,7 @@ struct Cloud
 
 int main(int argc, char** argv)
 {
-  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0;
+  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0, render = 0;
   float voxel = 0.5f;
   std::string apriori;
   for (int i = 1; i + 1 < argc; i += 2)
@@ -95,6 +96,8 @@ int main(int argc, char** argv)
       extents = std::atoi(argv[i + 1]);
     else if (k == "--pixels")  // 1: after each scan, the number of raw returns of every detection and their (row, col) rectangle (vofod_detection_pixels)
       pixels = std::atoi(argv[i + 1]);
+    else if (k == "--render")  // 1: after the run, the map as the sensor sees it from the last pose (vofod_map_render): the counts of the four kinds of pixel
+      render = std::atoi(argv[i + 1]);
   }
   const float vfov = 45.0f * 3.14159265f / 180.0f;
   vofod_static_params sp;
@@ -174,6 +177,7 @@ int main(int argc, char** argv)
 
   // ---- main role: one cloud per iteration
   size_t total_det = 0, det_on_target = 0, det_off_target = 0, msg_bytes = 0;
+  float last_tf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 4};
   std::vector<uint8_t> msg_buf;
   const auto t0 = std::chrono::steady_clock::now();
   for (int k = 0; k < n_scans; k++)
@@ -204,6 +208,7 @@ int main(int argc, char** argv)
       const float rm = static_cast<float>(c->range[i]) * 0.001f;
       c->x[i] = ds[0] * rm, c->y[i] = ds[1] * rm, c->z[i] = ds[2] * rm;
     }
+    std::copy(c->tf, c->tf + 12, last_tf);
     vofod_scan scan{c->x.data(), c->y.data(), c->z.data(), c->intensity.data(), c->range.data(), 4, cols, rows, VOFOD_MEM_HOST, 0.1 * k};
     vofod_detection dets[64];
     size_t n_det = 0;
@@ -294,6 +299,25 @@ int main(int argc, char** argv)
   std::printf("done: %d scans in %.3f s (%.1f scans/s incl. synthesis), detections %zu, detection_its %d, raycasts %d (timeouts %d), sepclusters passes %d\n", n_scans, secs, n_scans / secs,
               total_det, si.detection_its, n_raycasts.load(), n_raycast_timeouts.load(), n_sep.load());
   std::printf("check: %zu detections on the flying target, %zu elsewhere; %zu message bytes serialised\n", det_on_target, det_off_target, msg_bytes);
+  if (render)
+  {
+    // the expected range image of the last pose: what the map, as the run left it, says the sensor should see (background above
+    // thresholds/new_obstacles); `range` is a range image for vofod_process_scan / vofod_raycast_begin as it stands
+    const size_t n = static_cast<size_t>(rows) * cols;
+    std::vector<uint32_t> range(n);
+    std::vector<uint8_t> what(n);
+    if (vofod_map_render(h, last_tf, 1, static_cast<float>(dp.voxel_map__thresholds__new_obstacles), static_cast<float>(dp.raycast__max_distance), range.data(), nullptr, what.data(), nullptr,
+                         VOFOD_MEM_HOST) == VOFOD_OK)
+    {
+      size_t count[4] = {0, 0, 0, 0};
+      for (size_t i = 0; i < n; i++)
+        count[what[i] & 3]++;
+      std::printf("render of the last pose: %zu hits, %zu rays ended inside the map, %zu left it, %zu not cast\n", count[VOFOD_RENDER_HIT], count[VOFOD_RENDER_END], count[VOFOD_RENDER_LEFT],
+                  count[VOFOD_RENDER_NOT_CAST]);
+    }
+    else
+      std::fprintf(stderr, "map_render: %s\n", vofod_last_error_string(h));
+  }
   vofod_destroy(h);
   return det_off_target > det_on_target ? 3 : 0;  // (the target is found in most scans once the map has settled; strays are rare)
 }

@@ -750,6 +750,66 @@ int vofod_broadcast_map(vofod_comm* comm, vofod_handle* h, int32_t root, int32_t
  * shifts first and then takes a full snapshot. */
 int vofod_map_shift(vofod_handle* h, const int32_t shift_voxels[3], const float new_oparea_offset[3]);
 
+/* ------------------------------------------------- MAP RENDER (product library only)
+ *
+ * MAP RENDER.  The expected range image: the voxel map rendered through the handle's own LUT from a pose - standing here, looking
+ * there, what does the map say I should see?  One uint32 millimetre value per pixel, in the sensor's own format: it compares
+ * pixel by pixel with a measured scan, it goes back into vofod_process_scan / vofod_raycast_begin as a range image, it answers
+ * line-of-sight queries for many poses in one call, and it turns any map into a scan generator.  Answered on the device
+ * (k_map_render, vofod_amd/csrc/map_render.h); the CPU oracle does not have it.
+ *
+ * Pixel and ray.  For view v and pixel i = row * width + col the ray is the rigid ray of the raycast role:
+ *     d = lut_directions[3i..], o = lut_offsets[3i..] (zeros when the handle has none), [R | t] = tfs[12v .. 12v + 12) row-major
+ *     dir[k]   = ((R[k][0]*d[0]) + (R[k][1]*d[1])) + (R[k][2]*d[2])
+ *     start[k] = (((R[k][0]*o[0]) + (R[k][1]*o[1])) + (R[k][2]*o[2])) + t[k]
+ * IEEE float32, each operation rounded once, nothing fused.  No mask, no intensity gate, no exclude box and no col_tfs apply:
+ * every pixel is cast.  The map read is VOFOD_MAP_VOXELS as it stands when the call is serialised.
+ *
+ * Walk.  VoxelMap::forEachRay (voxel_map.cpp:229-263) with length = max_distance, vs the voxel size, off the map's origin:
+ *     cur[a]    = (int) floorf((start[a] - off[a]) * (1.0f / vs))                  the start's voxel
+ *     step[a]   = sign(dir[a]) (0 for a zero),  last[a] = step[a] > 0 ? size[a] - 1 : 0
+ *     tdelta[a] = (1.0f / |dir[a]|) * vs
+ *     ctr[a]    = (((float) cur[a] + 0.5f) * vs) + off[a]
+ *     tmax[a]   = ((vs / 2.0f) + ((float) step[a] * (ctr[a] - start[a]))) / |dir[a]|
+ *     if cur is outside the map                    -> what = NOT_CAST
+ *     prev = 0
+ *     loop:
+ *         a = the axis of the smallest tmax, the first one on ties;  dist = tmax[a]
+ *         if map[cur] > threshold                  -> what = HIT,  t_in = prev, t_out = min(dist, length); stop
+ *         if !(dist < length)                      -> what = END;  stop      (the length ran out inside cur)
+ *         if cur[a] == last[a]                     -> what = LEFT; stop      (the next step would leave the map)
+ *         cur[a] += step[a]; tmax[a] = tmax[a] + tdelta[a]; prev = dist
+ * `>` is the float compare: a NaN voxel is never a hit, +inf (an a-priori voxel) is, a voxel equal to the threshold is not.
+ *
+ * Outputs, each n_views * width * height values indexed (v * height + row) * width + col, each nullable:
+ *     what      one of VOFOD_RENDER_*
+ *     voxel     HIT: the linear index (z * sy + y) * sx + x of the hit voxel (the order of vofod_read_map); otherwise 0xffffffff
+ *     t_in_out  two floats per pixel.  HIT: (t_in, t_out), the piece of the ray inside the hit voxel in metres from start;
+ *               END, LEFT: (prev, min(dist, length)) of the last voxel looked at; NOT_CAST: (0, 0)
+ *     range     HIT: max(1, (uint32) rintf(((t_in + t_out) * 0.5f) * 1000.0f)) - the middle of that piece in the sensor's
+ *               millimetres, ties to even, never the 0 that means "no return" (the float is clamped to 2^32 - 256 before the
+ *               conversion); otherwise 0
+ * They live in out_memspace: VOFOD_MEM_HOST, or VOFOD_MEM_DEVICE on the handle's device, written in place - range and voxel
+ * 4-byte aligned, t_in_out 8-byte aligned.
+ *
+ * Refusals.  VOFOD_ERR_INVALID_ARG: n_views == 0 or above 65535, tfs == NULL, all four outputs NULL, !(max_distance > 0), a NaN
+ * threshold, an unknown memspace, a misaligned device output.  VOFOD_ERR_SENSOR_OUTSIDE_MAP, with nothing written, when the origin
+ * t of any view lies outside the map - the rule vofod_raycast_begin applies to its one tf.  VOFOD_ERR_DEVICE as everywhere.
+ *
+ * The call reads the voxel map only and uses a workspace of its own: it is admitted with tickets in flight and with a raycast
+ * pass (float or exact) or a sepclusters pass pending, runs on the handle's stream behind what was enqueued, returns after one
+ * synchronisation and changes nothing another call can observe - maps, latches, ids, detections, tickets, snapshot chains.
+ * World store: the window is rendered; a ray that reaches the window's face is LEFT.  Rendering through the store's tiles is out
+ * of scope, and so are a pose per column (col_tfs) and the occupancy image as a shortcut for its own threshold. */
+enum { VOFOD_RENDER_NOT_CAST = 0, VOFOD_RENDER_HIT = 1, VOFOD_RENDER_END = 2, VOFOD_RENDER_LEFT = 3 };
+int vofod_map_render(vofod_handle* h, const float* tfs /* n_views * 12, host */, size_t n_views,
+                     float threshold, float max_distance,
+                     uint32_t* range /* n_views * w * h, nullable */,
+                     uint32_t* voxel /* same, nullable */,
+                     uint8_t* what   /* same, nullable */,
+                     float* t_in_out /* n_views * w * h * 2, nullable */,
+                     int32_t out_memspace);
+
 /* ------------------------------------------------- WORLD STORE (product library only)
  *
  * vofod_map_shift alone forgets what leaves the box.  With the world store enabled the handle is a WINDOW onto a map larger than

@@ -113,6 +113,10 @@ sub["R25_MEASURED"] = (P / "r25_world_sync.txt").read_text().splitlines()[0].rem
 r26 = (P / "r26_detection_pixels.txt").read_text().splitlines()
 for name, prefix in (("R26_MEASURED", "measured: "), ("R26_BENCH", "bench: "), ("R26_MUTATIONS", "mutations: ")):
     sub[name] = next(l for l in r26 if l.startswith(prefix)).removeprefix(prefix)
+# §5.19: the lines of profiles/r27_map_render.txt that begin with "measured: ", "resources: ", "bench: " and "mutations: "
+r27 = (P / "r27_map_render.txt").read_text().splitlines()
+for name, prefix in (("R27_MEASURED", "measured: "), ("R27_RESOURCES", "resources: "), ("R27_BENCH", "bench: "), ("R27_MUTATIONS", "mutations: ")):
+    sub[name] = next(l for l in r27 if l.startswith(prefix)).removeprefix(prefix)
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

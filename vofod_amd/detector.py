@@ -190,6 +190,26 @@ class VoFOD:
             self.map_offset = tuple(self.status().map_offset)
         return st
 
+    def map_render(self, tfs, threshold: float, max_distance: float, out=None, allow: Sequence[int] = ()):
+        """The voxel map as the sensor would see it from each pose of `tfs` ([views, 3, 4] or one [3, 4]; vofod_map_render): returns
+        (range, voxel, what, t_in_out) - uint32 millimetres (0: no hit), the hit voxel's linear index (capi.RENDER_NO_VOXEL: none),
+        capi.RENDER_* as uint8, each [views, h, w], and the ray's piece inside the last voxel looked at as float32 [views, h, w, 2].
+        `out` = (range, voxel, what, t_in_out) device addresses on the handle's device, None for an output left out: they are
+        written in place and None comes back.  A status in `allow` is returned in place of the result."""
+        t = np.ascontiguousarray(tfs, dtype=np.float32).reshape(-1, 12)
+        nv, hh, ww = t.shape[0], int(self.sp.sensor_vrays), int(self.sp.sensor_hrays)
+        if out is not None:
+            ptrs = [None if a is None else C.c_void_p(int(a)) for a in out]
+            st = self._check(self.lib.map_render(self.h, capi.ptr(t), nv, float(threshold), float(max_distance), *ptrs, capi.MEM_DEVICE), "vofod_map_render", allow)
+            return None if st == capi.OK else st
+        rng = np.zeros((nv, hh, ww), dtype=np.uint32)
+        vox = np.zeros((nv, hh, ww), dtype=np.uint32)
+        what = np.zeros((nv, hh, ww), dtype=np.uint8)
+        tio = np.zeros((nv, hh, ww, 2), dtype=np.float32)
+        st = self._check(self.lib.map_render(self.h, capi.ptr(t), nv, float(threshold), float(max_distance), capi.ptr(rng), capi.ptr(vox), capi.ptr(what), capi.ptr(tio), capi.MEM_HOST),
+                         "vofod_map_render", allow)
+        return (rng, vox, what, tio) if st == capi.OK else st
+
     # ---- world store (include/vofod.h, WORLD STORE): the voxel map as a window onto a sparse map of a larger box
     def world_enable(self, margin_lo, margin_hi, max_tiles: int, allow: Sequence[int] = ()):
         """The box is [-margin_lo, map_size + margin_hi) in world indices (voxels, the window's origin K = 0 now); the pool holds

@@ -182,6 +182,16 @@ def make_moving_scan(scene: Scene, tf_ref: np.ndarray, col_tfs: np.ndarray, sens
     return SynthScan(scan=scan, tf=np.asarray(tf_ref, dtype=np.float32), x=x, y=y, z=z, intensity=intensity, range=range_mm)
 
 
+def scan_from_render(range_mm, intensity: float = 1000.0, stamp: float = 0.0) -> ScanData:
+    """A rendered view (one [h, w] slice of VoFOD.map_render's `range`) as the range image a sensor would have delivered: the
+    uint32 millimetres as they are (0: no return) and a constant `intensity` (above raycast__min_intensity by default), ready for
+    process_scan / raycast_begin of a handle with the same LUT."""
+    r = np.ascontiguousarray(range_mm, dtype=np.uint32)
+    assert r.ndim == 2, "one view: [h, w]"
+    h, w = r.shape
+    return ScanData.range_image(r.reshape(-1), width=w, height=h, intensity=np.full(h * w, intensity, dtype=np.float32), stamp=stamp)
+
+
 def apriori_points(scene: Scene, voxel_size: float, n_voxels: int | None = None, seed: int = 0, solid_ground_to: float | None = None) -> np.ndarray:
     """World-frame points on the ground sheet and on the static boxes' shells, one per
     voxel-sized cell (stand-in for the downsampled static cloud of vofod_nodelet.cpp:332-341).
