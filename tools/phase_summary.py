@@ -19,6 +19,10 @@ def reduce(path, frames=256, skip=2):
     wv = [r for r in rows if "input_waves" in r]
     if wv:  # the input pass wave by wave: the mean and the last wave's end (us from the frame's start), per cent of the loop spent waiting for loads
         out["input_waves"] = {k: {q: round(sum(r["input_waves"][k][q] for r in wv) / len(wv), 2) for q in ("mean", "median", "p90", "max")} for k in wv[0]["input_waves"]}
+    pf = [r["pure_far"] for r in rows if "pure_far" in r]
+    if pf:  # lengths of the frames' pure-far lists, and frames per launch whose list is beyond the lean ranks' threshold
+        out["pure_far"] = {"bricks": {q: round(sum(r["bricks"][q] for r in pf) / len(pf), 1) for q in ("mean", "median", "p90", "max")},
+                           **{k: round(sum(r[k] for r in pf) / len(pf), 1) for k in ("min", "p10", "over_lean_ranks_max")}}
     tl = [r for r in rows if "tail" in r]
     if tl:  # k_tail_far's own stamps for the same frames (one wave per frame)
         out["k_tail_far"] = {ph: {q: round(sum(r["tail"][ph][q] for r in tl) / len(tl), 2) for q in ("mean", "median", "p90", "max")} for ph in tl[0]["tail"]}

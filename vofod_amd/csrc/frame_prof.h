@@ -236,6 +236,19 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
         }
       }
       std::fprintf(fp, "}");
+      // the pure-far lists' lengths (slot 24), and how many of the frames keep the frame-wide rank passes for a long list
+      {
+        std::vector<double> npf;
+        size_t over = 0;
+        for (auto& b : byd)
+        {
+          npf.push_back(static_cast<double>(t[32 * b.second + 24]));
+          over += t[32 * b.second + 24] > FR_LEAN_RANKS_MAX ? 1 : 0;
+        }
+        std::fprintf(fp, ", \"pure_far\": {");
+        Quantiles(npf).json(fp, "bricks");  // (sorts)
+        std::fprintf(fp, ", \"min\": %.0f, \"p10\": %.0f, \"over_lean_ranks_max\": %zu}", npf.front(), npf[npf.size() / 10], over);
+      }
       if (!w_mean.empty())
       {
         std::fprintf(fp, ", \"input_waves\": {");

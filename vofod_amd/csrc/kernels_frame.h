@@ -28,6 +28,8 @@
 // bricks alone (same record, same rank) - and step 3's weights are counted for those bricks alone, too (round 23); ranks, V
 // and the capacity checks stay those of the whole frame.  The far-only debug view reads the whole cloud and keeps the full emission, as does every
 // launch under VOFOD_LEAN_EMIT=0 (read on every call, like the other switches).
+// Round 28, lean ranks: in a lean launch step 4 builds its rank tables for the pure-far bricks alone, too - a walk over the brick row
+// of every list entry instead of the segmented scans over all nodes; VOFOD_LEAN_RANKS=0, or a list beyond FR_LEAN_RANKS_MAX, keeps those.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -68,6 +70,10 @@ constexpr int CF_MAX = FR_THREADS;                 // close-first clustering: pu
 #define CF_G_DEF 4
 #endif
 constexpr int CF_G = CF_G_DEF;                     // bricks per thread whose map lookups are in flight together (close-first, first part)
+#ifndef FR_LEAN_RANKS_MAX_DEF
+#define FR_LEAN_RANKS_MAX_DEF 512
+#endif
+constexpr uint32_t FR_LEAN_RANKS_MAX = FR_LEAN_RANKS_MAX_DEF;  // lean ranks: pure-far bricks per frame up to which the rank tables are built per list entry (beyond: the frame-wide passes a / b)
 constexpr uint16_t FR_VBASE_NONE = 0xffffu;        // lean emission: "not counted" in place of a node's first voxel index
 constexpr uint32_t CF_LABEL_NONE = 0xffffffffu;    // label of a voxel outside the far clusters in the far-only debug view
 // VOFOD_LDS_PROF: the stamp buffer holds 32 slots for each of FR_PROF_FRAMES frames, then - same frame index - two values for each
@@ -1384,89 +1390,182 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   uint32_t* bmin_g = fs.bmin + static_cast<size_t>(FRAME) * LB_MAX;
   ulonglong2* nodeA = reinterpret_cast<ulonglong2*>(fs.nodeA + static_cast<size_t>(FRAME) * LB_MAX * 4);
   constexpr unsigned long long FR_BEGAN = 1ull << 63;
-  for (uint32_t ch = wave; ch < n_chunks; ch += FR_THREADS / 64)
+  // Lean ranks (round 28): in a lean launch nodeA and rowT are read for the nodes of the pure-far list only (pass d, the extras,
+  // rank_ctx), so the passes a and b shrink to a walk over the brick rows of those few nodes, and pass c takes every node's own
+  // layer counts instead of the rows' totals.  Bit 1 of `lean` (VOFOD_LEAN_RANKS=0 clears it); a frame with a long list keeps the
+  // frame-wide passes: the walk costs work per entry, they cost work per node.
+  const bool lean_ranks = lean_on && (lean & 2) != 0 && s_npf <= FR_LEAN_RANKS_MAX;
+  if (lean_ranks)
   {
-    const uint32_t i = ch * 64u + lane;
-    const FrNodes nd = fr_load_nodes(s_word, s_xyz, i, n, nby, lane, s_cin, ch, false);
-    if (nd.live)
-    {
-      s_xyz[i] = nd.xyz | (lb_oct8(nd.W) << 24);  // the word is final: its octant occupancy rides along for phase D
-      nodeA[2 * i] = make_ulonglong2(nd.A[0] - nd.P[0], nd.A[1] - nd.P[1]);
-      nodeA[2 * i + 1] = make_ulonglong2(nd.A[2] - nd.P[2], (nd.A[3] - nd.P[3]) | (nd.began_here ? FR_BEGAN : 0ull));
-    }
-    if (lane == 63)
-    {
+    for (uint32_t i = tid; i < n; i += FR_THREADS)
+      s_xyz[i] |= lb_oct8(s_word[i]) << 24;  // the word is final: its octant occupancy rides along for phase D (the row bits stay)
+    // One list entry per group of 16 lanes (a DPP row).  The nodes are in brick-linear order, so a brick row is a contiguous range
+    // of nodes: the group walks it from the entry's node, 16 nodes a step, backwards (A: the bricks in front) and forwards (the
+    // entry's own brick and those behind), until a step meets another row.  Several entries of one row store the same totals.
+    // The 16 channel counts of a lane's nodes ride in byte fields (a row holds at most 512 bricks: 32 nodes per lane and walk, 4
+    // voxels each); they are spread to the tables' 16-bit fields once, before the group's sum.
+    const int gl = lane & 15;
+    const uint32_t npf = s_npf;
+    // nibble q of the result: voxels in nibble q of x - the lattice rows yy + 4 zz of half a brick word
+    auto nib_counts = [](uint32_t x) -> uint32_t {
+      x = x - ((x >> 1) & 0x55555555u);
+      return (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
+    };
+    // acc: [0] / [1] the even / odd yy of the layers zz = 0, 1 (a byte each), [2] / [3] of zz = 2, 3
+    auto add_node = [&](uint32_t (&acc)[4], uint32_t j) {
+      const unsigned long long W = s_word[j];
+      const uint32_t lo = nib_counts(static_cast<uint32_t>(W)), hi = nib_counts(static_cast<uint32_t>(W >> 32));
+      acc[0] += lo & 0x0f0f0f0fu;
+      acc[1] += (lo >> 4) & 0x0f0f0f0fu;
+      acc[2] += hi & 0x0f0f0f0fu;
+      acc[3] += (hi >> 4) & 0x0f0f0f0fu;
+    };
+    // out[2 zz], out[2 zz + 1]: the halves of layer zz's table word - yy 0 | yy 1 << 16, yy 2 | yy 3 << 16
+    auto spread = [](const uint32_t (&acc)[4], uint32_t (&out)[8]) {
 #pragma unroll
       for (int zz = 0; zz < 4; zz++)
-        s_cin[ch + 1][zz] = nd.A[zz];  // staged one slot up: slot k + 1 becomes the carry into chunk k + 1
-      s_cflag[ch + 1] = nd.began_here ? 1u : 0u;
+      {
+        const uint32_t e = acc[(zz >> 1) * 2] >> (16 * (zz & 1)), o = acc[(zz >> 1) * 2 + 1] >> (16 * (zz & 1));
+        out[2 * zz] = (e & 0xffu) | ((o & 0xffu) << 16);
+        out[2 * zz + 1] = ((e >> 8) & 0xffu) | (((o >> 8) & 0xffu) << 16);
+      }
+    };
+    for (uint32_t k = static_cast<uint32_t>(tid) >> 4; k < npf; k += FR_THREADS / 16)
+    {
+      const uint32_t i = s_pf[k];
+      const uint32_t xyz_i = s_xyz[i];
+      const uint32_t rkey = (xyz_i >> 9) & 0x7fffu;  // (by, bz): the brick row
+      uint32_t accA[4] = {0u, 0u, 0u, 0u}, accT[4] = {0u, 0u, 0u, 0u};
+      for (int j = static_cast<int>(i) - 1 - gl;; j -= 16)
+      {
+        const bool in = j >= 0 && ((s_xyz[j] >> 9) & 0x7fffu) == rkey;
+        if (in)
+          add_node(accA, static_cast<uint32_t>(j));
+        if ((static_cast<uint32_t>(__ballot(in) >> (lane & 48)) & 0xffffu) != 0xffffu)
+          break;  // (the same for the 16 lanes of the group)
+      }
+      for (uint32_t j = i + static_cast<uint32_t>(gl);; j += 16u)
+      {
+        const bool in = j < n && ((s_xyz[j] >> 9) & 0x7fffu) == rkey;
+        if (in)
+          add_node(accT, j);
+        if ((static_cast<uint32_t>(__ballot(in) >> (lane & 48)) & 0xffffu) != 0xffffu)
+          break;
+      }
+      uint32_t A[8], T[8];
+      spread(accA, A);
+      spread(accT, T);
+#pragma unroll
+      for (int q = 0; q < 8; q++)
+      {
+        // (no field passes 16 bits - a row's channel holds at most 2 048 voxels -, so the halves add on their own)
+        T[q] += A[q];
+        A[q] += dpp_mov0<0x111, 0xf>(A[q]);
+        T[q] += dpp_mov0<0x111, 0xf>(T[q]);
+        A[q] += dpp_mov0<0x112, 0xf>(A[q]);
+        T[q] += dpp_mov0<0x112, 0xf>(T[q]);
+        A[q] += dpp_mov0<0x114, 0xf>(A[q]);
+        T[q] += dpp_mov0<0x114, 0xf>(T[q]);
+        A[q] += dpp_mov0<0x118, 0xf>(A[q]);
+        T[q] += dpp_mov0<0x118, 0xf>(T[q]);
+      }
+      if (gl == 15)  // the row's last lane holds the sums
+      {
+        auto w64 = [](uint32_t lo, uint32_t hi) -> unsigned long long { return static_cast<unsigned long long>(lo) | (static_cast<unsigned long long>(hi) << 32); };
+        nodeA[2 * i] = make_ulonglong2(w64(A[0], A[1]), w64(A[2], A[3]));
+        nodeA[2 * i + 1] = make_ulonglong2(w64(A[4], A[5]), w64(A[6], A[7]) | FR_BEGAN);  // (complete: no reader adds a chunk's carry)
+        ulonglong2* dst = reinterpret_cast<ulonglong2*>(rowT + static_cast<size_t>(fr_row(xyz_i, nby)) * 4);
+        dst[0] = make_ulonglong2(w64(T[0], T[1]), w64(T[2], T[3]));
+        dst[1] = make_ulonglong2(w64(T[4], T[5]), w64(T[6], T[7]));
+      }
     }
   }
-  __syncthreads();
-  if (wave == 0)
+  else
   {
-    // carry into chunk k + 1 = S(k) = tail(k) + (the tail row began inside chunk k ? 0 : S(k - 1)): a segmented scan again
-    unsigned long long carry[4] = {0ull, 0ull, 0ull, 0ull};
-    for (uint32_t k0 = 0; k0 < n_chunks; k0 += 64)
+    for (uint32_t ch = wave; ch < n_chunks; ch += FR_THREADS / 64)
     {
-      const uint32_t k = k0 + lane;
-      unsigned long long v[4];
-      bool hd = true;
-      if (k < n_chunks)
+      const uint32_t i = ch * 64u + lane;
+      const FrNodes nd = fr_load_nodes(s_word, s_xyz, i, n, nby, lane, s_cin, ch, false);
+      if (nd.live)
+      {
+        s_xyz[i] = nd.xyz | (lb_oct8(nd.W) << 24);  // the word is final: its octant occupancy rides along for phase D
+        nodeA[2 * i] = make_ulonglong2(nd.A[0] - nd.P[0], nd.A[1] - nd.P[1]);
+        nodeA[2 * i + 1] = make_ulonglong2(nd.A[2] - nd.P[2], (nd.A[3] - nd.P[3]) | (nd.began_here ? FR_BEGAN : 0ull));
+      }
+      if (lane == 63)
       {
 #pragma unroll
         for (int zz = 0; zz < 4; zz++)
-          v[zz] = s_cin[k + 1][zz];
-        hd = s_cflag[k + 1] != 0u;
+          s_cin[ch + 1][zz] = nd.A[zz];  // staged one slot up: slot k + 1 becomes the carry into chunk k + 1
+        s_cflag[ch + 1] = nd.began_here ? 1u : 0u;
       }
-      else
-      {
-#pragma unroll
-        for (int zz = 0; zz < 4; zz++)
-          v[zz] = 0ull;
-      }
-      fr_segscan(v, hd);
-      if (!hd)
-      {
-#pragma unroll
-        for (int zz = 0; zz < 4; zz++)
-          v[zz] += carry[zz];
-      }
-      if (k < n_chunks)
-      {
-#pragma unroll
-        for (int zz = 0; zz < 4; zz++)
-          s_cin[k + 1][zz] = v[zz];
-      }
-#pragma unroll
-      for (int zz = 0; zz < 4; zz++)
-        carry[zz] = fr_shfl64(v[zz], 63);
     }
-    if (lane < 4)
-      s_cin[0][lane] = 0ull;
-  }
-  __syncthreads();
-  // Pass b: the last node of every brick row writes the row's channel totals (dense index brick row = bz * nby + by; only
-  // occupied rows are written / read)
-  for (uint32_t i = tid; i < n; i += FR_THREADS)
-  {
-    const uint32_t row = fr_row(s_xyz[i], nby);
-    const bool tail = i + 1 == n || fr_row(s_xyz[i + 1], nby) != row;
-    if (tail)
+    __syncthreads();
+    if (wave == 0)
     {
-      const ulonglong2 a0 = nodeA[2 * i], a1 = nodeA[2 * i + 1];
-      const unsigned long long W = s_word[i];
-      const bool began = (a1.y & FR_BEGAN) != 0ull;
-      unsigned long long T[4] = {a0.x + fr_chan(W, 0), a0.y + fr_chan(W, 1), a1.x + fr_chan(W, 2), (a1.y & ~FR_BEGAN) + fr_chan(W, 3)};
-      if (!began)
+      // carry into chunk k + 1 = S(k) = tail(k) + (the tail row began inside chunk k ? 0 : S(k - 1)): a segmented scan again
+      unsigned long long carry[4] = {0ull, 0ull, 0ull, 0ull};
+      for (uint32_t k0 = 0; k0 < n_chunks; k0 += 64)
       {
+        const uint32_t k = k0 + lane;
+        unsigned long long v[4];
+        bool hd = true;
+        if (k < n_chunks)
+        {
+#pragma unroll
+          for (int zz = 0; zz < 4; zz++)
+            v[zz] = s_cin[k + 1][zz];
+          hd = s_cflag[k + 1] != 0u;
+        }
+        else
+        {
+#pragma unroll
+          for (int zz = 0; zz < 4; zz++)
+            v[zz] = 0ull;
+        }
+        fr_segscan(v, hd);
+        if (!hd)
+        {
+#pragma unroll
+          for (int zz = 0; zz < 4; zz++)
+            v[zz] += carry[zz];
+        }
+        if (k < n_chunks)
+        {
+#pragma unroll
+          for (int zz = 0; zz < 4; zz++)
+            s_cin[k + 1][zz] = v[zz];
+        }
 #pragma unroll
         for (int zz = 0; zz < 4; zz++)
-          T[zz] += s_cin[i >> 6][zz];
+          carry[zz] = fr_shfl64(v[zz], 63);
       }
-      ulonglong2* dst = reinterpret_cast<ulonglong2*>(rowT + static_cast<size_t>(row) * 4);
-      dst[0] = make_ulonglong2(T[0], T[1]);
-      dst[1] = make_ulonglong2(T[2], T[3]);
+      if (lane < 4)
+        s_cin[0][lane] = 0ull;
+    }
+    __syncthreads();
+    // Pass b: the last node of every brick row writes the row's channel totals (dense index brick row = bz * nby + by; only
+    // occupied rows are written / read)
+    for (uint32_t i = tid; i < n; i += FR_THREADS)
+    {
+      const uint32_t row = fr_row(s_xyz[i], nby);
+      const bool tail = i + 1 == n || fr_row(s_xyz[i + 1], nby) != row;
+      if (tail)
+      {
+        const ulonglong2 a0 = nodeA[2 * i], a1 = nodeA[2 * i + 1];
+        const unsigned long long W = s_word[i];
+        const bool began = (a1.y & FR_BEGAN) != 0ull;
+        unsigned long long T[4] = {a0.x + fr_chan(W, 0), a0.y + fr_chan(W, 1), a1.x + fr_chan(W, 2), (a1.y & ~FR_BEGAN) + fr_chan(W, 3)};
+        if (!began)
+        {
+#pragma unroll
+          for (int zz = 0; zz < 4; zz++)
+            T[zz] += s_cin[i >> 6][zz];
+        }
+        ulonglong2* dst = reinterpret_cast<ulonglong2*>(rowT + static_cast<size_t>(row) * 4);
+        dst[0] = make_ulonglong2(T[0], T[1]);
+        dst[1] = make_ulonglong2(T[2], T[3]);
+      }
     }
   }
   __syncthreads();
@@ -1484,35 +1583,63 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     const uint32_t i0 = static_cast<uint32_t>(tid) * NPT;
     for (int s = tid; s < FR_MAX_NBZ + 1; s += FR_THREADS)
       s_gs[s] = ~0ull;
-    uint32_t rows[NPT];  // the brick row a node is the last one of, or ~0
+    uint32_t rows[NPT];  // the brick row a node is the last one of (lean ranks: the first one), or ~0
     unsigned long long tz[NPT];
     unsigned long long sum = 0ull;
-    uint32_t xyz_next = i0 < n ? s_xyz[i0] : 0u;
-#pragma unroll
-    for (int r = 0; r < NPT; r++)
+    if (lean_ranks)
     {
-      const uint32_t i = i0 + r;
-      rows[r] = 0xffffffffu;
-      if (i < n)
+      // Lean ranks: no row totals to read - every node adds the voxels of its own four layers, and a brick row's G is taken at its
+      // FIRST node: the exclusive sum there is the same sum over the rows in front.  Nothing of the passes a / b is read.
+      uint32_t row_prev = (i0 > 0 && i0 < n) ? fr_row(s_xyz[i0 - 1], nby) : 0xffffffffu;
+#pragma unroll
+      for (int r = 0; r < NPT; r++)
       {
-        const uint32_t xyz = xyz_next;
-        xyz_next = i + 1 < n ? s_xyz[i + 1] : 0u;
-        const uint32_t row = fr_row(xyz, nby);
-        if (i + 1 == n || fr_row(xyz_next, nby) != row)
-          rows[r] = row;
+        const uint32_t i = i0 + r;
+        rows[r] = 0xffffffffu;
+        tz[r] = 0ull;
+        if (i < n)
+        {
+          const uint32_t row = fr_row(s_xyz[i], nby);
+          if (row != row_prev)
+            rows[r] = row;
+          row_prev = row;
+          const unsigned long long W = s_word[i];
+          const uint32_t lo = static_cast<uint32_t>(W), hi = static_cast<uint32_t>(W >> 32);
+          tz[r] = static_cast<unsigned long long>(__popc(lo & 0xffffu)) | (static_cast<unsigned long long>(__popc(lo >> 16)) << 16) | (static_cast<unsigned long long>(__popc(hi & 0xffffu)) << 32) |
+                  (static_cast<unsigned long long>(__popc(hi >> 16)) << 48);
+          sum += tz[r];
+        }
       }
     }
-#pragma unroll
-    for (int r = 0; r < NPT; r++)
+    else
     {
-      tz[r] = 0ull;
-      if (rows[r] != 0xffffffffu)
+      uint32_t xyz_next = i0 < n ? s_xyz[i0] : 0u;
+#pragma unroll
+      for (int r = 0; r < NPT; r++)
       {
-        const ulonglong2* src = reinterpret_cast<const ulonglong2*>(rowT + static_cast<size_t>(rows[r]) * 4);
-        const ulonglong2 t0 = src[0], t1 = src[1];
-        tz[r] = static_cast<unsigned long long>(fr_hsum16(t0.x)) | (static_cast<unsigned long long>(fr_hsum16(t0.y)) << 16) | (static_cast<unsigned long long>(fr_hsum16(t1.x)) << 32) |
-                (static_cast<unsigned long long>(fr_hsum16(t1.y)) << 48);
-        sum += tz[r];
+        const uint32_t i = i0 + r;
+        rows[r] = 0xffffffffu;
+        if (i < n)
+        {
+          const uint32_t xyz = xyz_next;
+          xyz_next = i + 1 < n ? s_xyz[i + 1] : 0u;
+          const uint32_t row = fr_row(xyz, nby);
+          if (i + 1 == n || fr_row(xyz_next, nby) != row)
+            rows[r] = row;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < NPT; r++)
+      {
+        tz[r] = 0ull;
+        if (rows[r] != 0xffffffffu)
+        {
+          const ulonglong2* src = reinterpret_cast<const ulonglong2*>(rowT + static_cast<size_t>(rows[r]) * 4);
+          const ulonglong2 t0 = src[0], t1 = src[1];
+          tz[r] = static_cast<unsigned long long>(fr_hsum16(t0.x)) | (static_cast<unsigned long long>(fr_hsum16(t0.y)) << 16) | (static_cast<unsigned long long>(fr_hsum16(t1.x)) << 32) |
+                  (static_cast<unsigned long long>(fr_hsum16(t1.y)) << 48);
+          sum += tz[r];
+        }
       }
     }
     unsigned long long incl = sum;
@@ -1550,8 +1677,8 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
         // G of the row: the slab's constant is added where it is read
         *reinterpret_cast<uint4*>(rowQ + static_cast<size_t>(rows[r]) * 4) =
             make_uint4(static_cast<uint32_t>(G) & 0xffffu, static_cast<uint32_t>(G >> 16) & 0xffffu, static_cast<uint32_t>(G >> 32) & 0xffffu, static_cast<uint32_t>(G >> 48));
-        G += tz[r];
       }
+      G += tz[r];  // (zero at a node that is not its row's last one - lean ranks: the node's own counts)
     }
     __syncthreads();
     if (tid < nbz && s_gs[tid] != ~0ull)
