@@ -23,6 +23,12 @@ def reduce(path, frames=256, skip=2):
     if pf:  # lengths of the frames' pure-far lists, and frames per launch whose list is beyond the lean ranks' threshold
         out["pure_far"] = {"bricks": {q: round(sum(r["bricks"][q] for r in pf) / len(pf), 1) for q in ("mean", "median", "p90", "max")},
                            **{k: round(sum(r[k] for r in pf) / len(pf), 1) for k in ("min", "p10", "over_lean_ranks_max")}}
+    lc = [r["lean_count"] for r in rows if "lean_count" in r]
+    if lc:  # lean count: entries of the frames' code lists and voxels with a counter (mean over launches; the maxima over all launches size the
+        # caps), and frames per launch that counted from the list / walked every code / had a list beyond the cap
+        out["lean_count"] = {**{k: {**{q: round(sum(r[k][q] for r in lc) / len(lc), 1) for q in ("mean", "median", "p90", "max")}, "max_of_launches": max(r[k]["max"] for r in lc)}
+                                for k in ("entries", "counters")},
+                             **{k: round(sum(r[k] for r in lc) / len(lc), 1) for k in ("from_list", "walked", "over_lean_count_max")}}
     tl = [r for r in rows if "tail" in r]
     if tl:  # k_tail_far's own stamps for the same frames (one wave per frame)
         out["k_tail_far"] = {ph: {q: round(sum(r["tail"][ph][q] for r in tl) / len(tl), 2) for q in ("mean", "median", "p90", "max")} for ph in tl[0]["tail"]}

@@ -28,6 +28,7 @@ struct Switches
   bool close_first = true;   // VOFOD_CLOSE_FIRST=0: the full clustering everywhere
   bool lean_emit = true;     // VOFOD_LEAN_EMIT=0: the close-first frame kernel emits every voxel record
   bool lean_ranks = true;    // VOFOD_LEAN_RANKS=0: a lean launch still builds its rank tables for every brick
+  bool lean_count = true;    // VOFOD_LEAN_COUNT=0: a lean launch still counts its weights by walking every code
   bool device_tail = true;   // VOFOD_DEVICE_TAIL=0: the full tables come back for the host tail
   bool brick_lds = true;     // VOFOD_BRICK_LDS=0: the global-memory clustering kernels
   bool brick_ccl = true;     // VOFOD_CCL=voxel: the voxel-level clustering kernels
@@ -43,6 +44,7 @@ inline Switches read_switches()
   s.close_first = !switch_off("VOFOD_CLOSE_FIRST");
   s.lean_emit = !switch_off("VOFOD_LEAN_EMIT");
   s.lean_ranks = !switch_off("VOFOD_LEAN_RANKS");
+  s.lean_count = !switch_off("VOFOD_LEAN_COUNT");
   s.device_tail = !switch_off("VOFOD_DEVICE_TAIL");
   s.brick_lds = !switch_off("VOFOD_BRICK_LDS");
   const char* ccl = std::getenv("VOFOD_CCL");
@@ -131,6 +133,7 @@ struct ChainPlan
   bool far_ran = false;         // cluster table and member list are in the order k_tail_far reads
   bool lean = false;            // k_frame_lds_far writes the voxel records of pure-far bricks only
   bool lean_ranks = false;      // ... and ranks through tables built for those bricks only (kernels_frame.h, pass 4)
+  bool lean_count = false;      // ... and counts the weights from a filtered list of those bricks' codes (kernels_frame.h, pass 3b)
   bool write_tables = false;    // the frame kernel writes cluster table and candidate list itself
   bool mapbits_patched = false; // k_finalize_far keeps the map's occupancy image and counters up to date with the scan's update
   bool bitmap_clean_after = false;  // Workspace::bitmap_clean once the chain is enqueued
@@ -181,6 +184,7 @@ inline ChainPlan plan_chain(const PlanInputs& in)
   p.far_ran = p.frame() && up_tables && p.use_dilated && p.close_first != 0;
   p.lean = p.far_ran && p.close_first == 1 && sw.lean_emit;
   p.lean_ranks = p.lean && sw.lean_ranks;
+  p.lean_count = p.lean && sw.lean_count;
   p.write_tables = p.frame() && up_tables && p.use_dilated;
   if (p.far_single)
     p.clusterer = Clusterer::FarSingle;

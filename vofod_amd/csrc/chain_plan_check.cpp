@@ -54,7 +54,7 @@ int main(int argc, char** argv)
   in.lb_max = 7168;        // kernels_brick_lds.h LB_MAX
   in.slab_words64 = 16384; // kernels_slab.h SLAB_WORDS64
   const std::map<std::string, bool*> flags = {
-      {"close_first", &in.sw.close_first}, {"lean_emit", &in.sw.lean_emit}, {"lean_ranks", &in.sw.lean_ranks}, {"device_tail", &in.sw.device_tail}, {"brick_lds", &in.sw.brick_lds}, {"brick_ccl", &in.sw.brick_ccl},
+      {"close_first", &in.sw.close_first}, {"lean_emit", &in.sw.lean_emit}, {"lean_ranks", &in.sw.lean_ranks}, {"lean_count", &in.sw.lean_count}, {"device_tail", &in.sw.device_tail}, {"brick_lds", &in.sw.brick_lds}, {"brick_ccl", &in.sw.brick_ccl},
       {"dilate", &in.sw.dilate}, {"slabs", &in.sw.slabs}, {"slab_emit", &in.sw.slab_emit}, {"no_update", &in.no_update}, {"submitted", &in.submitted}, {"dbg", &in.dbg},
       {"dbg_far_only", &in.dbg_far_only}, {"auto_raycast", &in.auto_raycast}, {"bitmap_clean", &in.bitmap_clean}, {"brick_ok", &in.brick_ok}, {"lds_ok", &in.lds_ok},
       {"pair_table", &in.pair_table}, {"cf_off", &in.cf_off}, {"lds_ccl_off", &in.lds_ccl_off}, {"ref_lattice_on", &in.ref_lattice_on}, {"layout_packed", &in.layout_packed},

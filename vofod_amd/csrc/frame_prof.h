@@ -249,6 +249,25 @@ int print_frame_prof(vofod_handle* h, uint32_t s0, uint32_t cnt, bool sync)
         Quantiles(npf).json(fp, "bricks");  // (sorts)
         std::fprintf(fp, ", \"min\": %.0f, \"p10\": %.0f, \"over_lean_ranks_max\": %zu}", npf.front(), npf[npf.size() / 10], over);
       }
+      // the lean count (slot 28 above the extras' 24 bits: the list's length, 20 bits; Vc, 16 bits; bit 63: counted from the list): the
+      // lists' lengths and the voxels with a counter, and how many of the frames walked every code instead
+      {
+        std::vector<double> nlc, vc;
+        size_t from_list = 0, over = 0;
+        for (auto& b : byd)
+        {
+          const unsigned long long x = t[32 * b.second + 28];
+          nlc.push_back(static_cast<double>((x >> 24) & 0xfffffull));
+          vc.push_back(static_cast<double>((x >> 44) & 0xffffull));
+          from_list += x >> 63;
+          over += ((x >> 24) & 0xfffffull) > FR_LEAN_COUNT_MAX ? 1 : 0;
+        }
+        std::fprintf(fp, ", \"lean_count\": {");
+        Quantiles(nlc).json(fp, "entries");
+        std::fprintf(fp, ", ");
+        Quantiles(vc).json(fp, "counters");
+        std::fprintf(fp, ", \"from_list\": %zu, \"walked\": %zu, \"over_lean_count_max\": %zu}", from_list, byd.size() - from_list, over);
+      }
       if (!w_mean.empty())
       {
         std::fprintf(fp, ", \"input_waves\": {");

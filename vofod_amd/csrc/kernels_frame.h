@@ -30,6 +30,9 @@
 // launch under VOFOD_LEAN_EMIT=0 (read on every call, like the other switches).
 // Round 28, lean ranks: in a lean launch step 4 builds its rank tables for the pure-far bricks alone, too - a walk over the brick row
 // of every list entry instead of the segmented scans over all nodes; VOFOD_LEAN_RANKS=0, or a list beyond FR_LEAN_RANKS_MAX, keeps those.
+// Round 29, lean count: in a lean launch pass 3b first filters the codes of the pure-far bricks into a list (a round's look-ups in flight
+// together, one reservation per wave and round) and counts the weights from that list; VOFOD_LEAN_COUNT=0, or a list beyond
+// FR_LEAN_COUNT_MAX, keeps the walk over every code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,6 +77,10 @@ constexpr int CF_G = CF_G_DEF;                     // bricks per thread whose ma
 #define FR_LEAN_RANKS_MAX_DEF 512
 #endif
 constexpr uint32_t FR_LEAN_RANKS_MAX = FR_LEAN_RANKS_MAX_DEF;  // lean ranks: pure-far bricks per frame up to which the rank tables are built per list entry (beyond: the frame-wide passes a / b)
+#ifndef FR_LEAN_COUNT_MAX_DEF
+#define FR_LEAN_COUNT_MAX_DEF 8192
+#endif
+constexpr uint32_t FR_LEAN_COUNT_MAX = FR_LEAN_COUNT_MAX_DEF;  // lean count: entries of a frame's list of listed codes up to which pass 3b counts from the list (beyond: the walk over every code)
 constexpr uint16_t FR_VBASE_NONE = 0xffffu;        // lean emission: "not counted" in place of a node's first voxel index
 constexpr uint32_t CF_LABEL_NONE = 0xffffffffu;    // label of a voxel outside the far clusters in the far-only debug view
 // VOFOD_LDS_PROF: the stamp buffer holds 32 slots for each of FR_PROF_FRAMES frames, then - same frame index - two values for each
@@ -386,6 +393,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   __shared__ __attribute__((aligned(16))) uint16_t s_pfpar[CF_MAX];  // union-find over the list's indices (set up behind the emission; the rank pass c borrows the storage)
   __shared__ uint32_t s_taint[CF_MAX / 32], s_troot[CF_MAX / 32];  // bit k: list entry k has an edge to a brick with a close voxel / the component rooted at k holds such an entry
   __shared__ uint32_t s_npf, s_nc, s_no2, s_ncand;
+  __shared__ uint32_t s_nlc;  // lean count: entries of the frame's list of listed codes (may pass FR_LEAN_COUNT_MAX: the list then is not used)
   __shared__ __attribute__((aligned(16))) uint32_t s_cfd[32][4];  // (stencil row, direction) descriptors of the close-first edge passes
   __shared__ uint8_t s_cfl[2][32];
   __shared__ uint32_t s_cfn[2];
@@ -1258,7 +1266,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   // counter per voxel, indexed in brick order: first voxel of the node + set bits below.  Consecutive equal codes of a
   // thread add once.  Points that would take a counter past 255 go to the frame's record list instead
   // (node * 64 + bit | (points - 1) << 25), added to the stored weights after the emission.
-  uint32_t V = 0;
+  uint32_t V = 0, Vc = 0;  // Vc: voxels with a counter
   {
     ulonglong2* bsave = reinterpret_cast<ulonglong2*>(fs.bbsave + static_cast<size_t>(FRAME) * FR_BB64);
     for (int i = tid; i < FR_BB64 / 2; i += FR_THREADS)
@@ -1279,8 +1287,10 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     const uint32_t incl = wave_incl_scan(sum);
     if (lane == 63)
       s_wsum[wave] = incl;
+    if (tid == 0)
+      s_nlc = 0;
     __syncthreads();  // (also: every thread has parked its part of the bitmap)
-    uint32_t run = (incl - sum) & 0xffffu, Vc = 0;  // Vc: voxels with a counter
+    uint32_t run = (incl - sum) & 0xffffu;
     for (int w = 0; w < FR_THREADS / 64; w++)
     {
       const uint32_t x = s_wsum[w];
@@ -1364,21 +1374,110 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       if (last != FR_CODE_NONE)
         count(last, cntl);
     };
+    // Lean count (round 29; bit 2 of `lean`, VOFOD_LEAN_COUNT=0 clears it).  A lean frame lists a few hundred of its ~7 000 bricks: of the
+    // ~45 000 codes the walk below visits, a few per cent reach a counter - but at every one of its 16 positions some lane of the wave has
+    // a run boundary, so the wave pays the position's dependent s_vbase read, its wait and its branch every time.  Instead: a filter
+    // pass reads s_vbase for all 16 codes of a lane and round before the first answer is used, merges the lane's runs of a listed code
+    // into entries code | (points - 1) << 25 (the extras-record format), reserves the wave's room in the frame's list with one wave
+    // scan and one LDS atomic per round, and the threads then stride over the list with the same count().  Integer adds commute: the
+    // weights (byte + extras) are those of the walk.  The list lives behind the counters in the parked bitmap's LDS (Vc bytes of
+    // FR_CNT_CAP are counters), which the restore behind the extras pass overwrites; a frame whose counters leave no room for
+    // FR_LEAN_COUNT_MAX entries, or whose list would be longer, takes the walk - on counters that nobody has touched yet.
+    const uint32_t lc_off = (Vc + 15u) & ~15u;  // bytes: the zeroed counters end here
+    bool counted = false;
+    if (lean_on && (lean & 4) != 0 && lc_off + 4u * FR_LEAN_COUNT_MAX <= FR_CNT_CAP)  // (wave-uniform)
+    {
+      uint32_t* s_lc = s_cnt32 + (lc_off >> 2);
+      auto filter_round = [&](const uint32_t (&c)[KPT]) {
+        uint32_t vb[KPT];
 #pragma unroll
-    for (int r = 0; r < RR; r++)
-      if (static_cast<uint32_t>(r) * 64u * KPT < wcnt)
-        count_round(creg[r]);
-    for (uint32_t rb = static_cast<uint32_t>(RR) * 64u * KPT; rb < wcnt; rb += 64u * KPT)
-    {
-      uint32_t c[KPT];
-      load_codes(rb + lane * KPT, c);
-      count_round(c);
+        for (int u = 0; u < KPT; u++)
+          vb[u] = s_vbase[min(c[u] >> 6, static_cast<uint32_t>(LB_MAX - 1))];  // (FR_CODE_NONE: some node's answer, not used)
+        uint32_t ends = 0;  // bit u: a run of a listed code ends at position u
+#pragma unroll
+        for (int u = 0; u < KPT; u++)
+        {
+          const bool end = u == KPT - 1 || c[u + (u < KPT - 1 ? 1 : 0)] != c[u];
+          ends |= (end && vb[u] != FR_VBASE_NONE && c[u] != FR_CODE_NONE) ? 1u << u : 0u;
+        }
+        if (!__any(ends != 0u))
+          return;
+        const uint32_t k = __popc(ends), incl = wave_incl_scan(k);
+        uint32_t pos = 0;
+        if (lane == 63)
+          pos = atomicAdd(&s_nlc, incl);
+        pos = __builtin_amdgcn_readlane(pos, 63) + incl - k;
+        uint32_t more = 0;  // points of the run so far, less one
+#pragma unroll
+        for (int u = 0; u < KPT; u++)
+        {
+          more = (u > 0 && c[u] == c[u > 0 ? u - 1 : 0]) ? more + 1u : 0u;
+          if ((ends >> u) & 1u)
+          {
+            if (pos < FR_LEAN_COUNT_MAX)
+              s_lc[pos] = c[u] | (more << 25);
+            pos++;
+          }
+        }
+      };
+#pragma unroll
+      for (int r = 0; r < RR; r++)
+        if (static_cast<uint32_t>(r) * 64u * KPT < wcnt)
+          filter_round(creg[r]);
+      for (uint32_t rb = static_cast<uint32_t>(RR) * 64u * KPT; rb < wcnt; rb += 64u * KPT)
+      {
+        uint32_t c[KPT];
+        load_codes(rb + lane * KPT, c);
+        filter_round(c);
+      }
+      for (uint32_t i0 = 0; i0 < n_frag; i0 += FR_THREADS)  // (wave-uniform trip count: the reservation below ballots the wave)
+      {
+        const uint32_t i = i0 + tid;
+        const uint32_t cd = i < n_frag ? reinterpret_cast<const uint32_t*>(fragl + i)[3] : FR_CODE_NONE;
+        const bool hit = cd != FR_CODE_NONE && s_vbase[min(cd >> 6, static_cast<uint32_t>(LB_MAX - 1))] != FR_VBASE_NONE;
+        const unsigned long long m = __ballot(hit);
+        if (!m)
+          continue;
+        uint32_t pos = 0;
+        if (lane == 0)
+          pos = atomicAdd(&s_nlc, static_cast<uint32_t>(__popcll(m)));
+        pos = __builtin_amdgcn_readlane(pos, 0) + __popcll(m & ((1ull << lane) - 1ull));
+        if (hit && pos < FR_LEAN_COUNT_MAX)
+          s_lc[pos] = cd;
+      }
+      __syncthreads();
+      const uint32_t n_lc = s_nlc;
+      if (n_lc <= FR_LEAN_COUNT_MAX)  // (wave-uniform, behind the barrier: every entry is in the list)
+      {
+        for (uint32_t e = tid; e < n_lc; e += FR_THREADS)
+        {
+          const uint32_t rec = s_lc[e];
+          count(rec & 0x1ffffffu, (rec >> 25) + 1u);
+        }
+        counted = true;
+      }
     }
-    for (uint32_t i = tid; i < n_frag; i += FR_THREADS)
+    // (diagnostics, slot 28 above the extras' 24 bits: the list's length, Vc, and bit 63: the weights were counted from the list)
+    if (cf && prof && tid == 0)
+      prof[static_cast<size_t>(FRAME) * 32 + 28] = (static_cast<unsigned long long>(min(s_nlc, 0xfffffu)) << 24) | (static_cast<unsigned long long>(Vc) << 44) | (counted ? 1ull << 63 : 0ull);
+    if (!counted)
     {
-      const uint32_t cd = reinterpret_cast<const uint32_t*>(fragl + i)[3];
-      if (cd != FR_CODE_NONE)
-        count(cd, 1u);
+#pragma unroll
+      for (int r = 0; r < RR; r++)
+        if (static_cast<uint32_t>(r) * 64u * KPT < wcnt)
+          count_round(creg[r]);
+      for (uint32_t rb = static_cast<uint32_t>(RR) * 64u * KPT; rb < wcnt; rb += 64u * KPT)
+      {
+        uint32_t c[KPT];
+        load_codes(rb + lane * KPT, c);
+        count_round(c);
+      }
+      for (uint32_t i = tid; i < n_frag; i += FR_THREADS)
+      {
+        const uint32_t cd = reinterpret_cast<const uint32_t*>(fragl + i)[3];
+        if (cd != FR_CODE_NONE)
+          count(cd, 1u);
+      }
     }
   }
   __syncthreads();
@@ -2275,7 +2374,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       prof[static_cast<size_t>(FRAME) * 32 + 25] = s_nc + s_no2;
       prof[static_cast<size_t>(FRAME) * 32 + 26] = n;
       prof[static_cast<size_t>(FRAME) * 32 + 27] = n_keys;
-      prof[static_cast<size_t>(FRAME) * 32 + 28] = s_ne;
+      prof[static_cast<size_t>(FRAME) * 32 + 28] |= min(s_ne, 0xffffffu);  // (pass 3b left the lean count's figures in the upper bits)
       prof[static_cast<size_t>(FRAME) * 32 + 29] = V;
       prof[static_cast<size_t>(FRAME) * 32 + 30] = s_ncand;
       prof[static_cast<size_t>(FRAME) * 32 + 31] = ~0ull;  // (marks a close-first frame for print_prof)

@@ -1275,7 +1275,7 @@ int launch_frame_kernel(vofod_handle* h, Workspace& ws, const vplan::ChainPlan& 
   const auto kern = far ? (packed ? k_frame_lds_far_p : k_frame_lds_far) : (packed ? k_frame_lds_full_p : k_frame_lds_full);
   const char* label = far ? (packed ? "k_frame_lds_far" : "k_frame_lds_far_strided") : (packed ? "k_frame_lds_full" : "k_frame_lds_full_strided");
   KLAUNCH_AS(h, label, kern, dim3(n), dim3(FR_THREADS), g, bp, ct->d_lbtab, ws.d_hdrs, ws.sa, ws.pt_cap, ws.va, ws.d_labels, plan.lb_limit, reinterpret_cast<uint32_t*>(ws.d_table.p), ws.fs, h->mg, mapclose,
-             h->d_mapbits, h->d_crows, h->closetab.n_rows, up, ws.d_table, ws.d_cand, plan.write_tables ? 1 : 0, d_prof, ref_lattice, ws.d_args, far ? plan.close_first : 0, plan.lean ? (plan.lean_ranks ? 3 : 1) : 0);
+             h->d_mapbits, h->d_crows, h->closetab.n_rows, up, ws.d_table, ws.d_cand, plan.write_tables ? 1 : 0, d_prof, ref_lattice, ws.d_args, far ? plan.close_first : 0, plan.lean ? 1 | (plan.lean_ranks ? 2 : 0) | (plan.lean_count ? 4 : 0) : 0);
   if (d_prof && !ws.prof_deferred)
     VCHK(print_frame_prof(h, 0, n, true));
   HIPCHK(hipGetLastError());
