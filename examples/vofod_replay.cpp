@@ -74,7 +74,7 @@ struct Cloud
 
 int main(int argc, char** argv)
 {
-  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0, render = 0;
+  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0, render = 0, agree = 0;
   float voxel = 0.5f;
   std::string apriori;
   for (int i = 1; i + 1 < argc; i += 2)
@@ -98,6 +98,8 @@ int main(int argc, char** argv)
       pixels = std::atoi(argv[i + 1]);
     else if (k == "--render")  // 1: after the run, the map as the sensor sees it from the last pose (vofod_map_render): the counts of the four kinds of pixel
       render = std::atoi(argv[i + 1]);
+    else if (k == "--agree")  // 1: before each scan's update, the scan against the map as it stands (vofod_map_render_scans): the counts of the seven verdicts
+      agree = std::atoi(argv[i + 1]);
   }
   const float vfov = 45.0f * 3.14159265f / 180.0f;
   vofod_static_params sp;
@@ -210,6 +212,18 @@ int main(int argc, char** argv)
     }
     std::copy(c->tf, c->tf + 12, last_tf);
     vofod_scan scan{c->x.data(), c->y.data(), c->z.data(), c->intensity.data(), c->range.data(), 4, cols, rows, VOFOD_MEM_HOST, 0.1 * k};
+    if (agree)
+    {
+      // which share of this scan agrees with the map under this pose, and how many returns lie in space the map holds free -
+      // asked BEFORE the scan updates the map; a voxel of tolerance, the counts alone (no image is read back)
+      uint32_t counts[8];
+      if (vofod_map_render_scans(h, &scan, c->tf, 1, static_cast<float>(dp.voxel_map__thresholds__new_obstacles), static_cast<float>(dp.raycast__max_distance), voxel, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, counts, VOFOD_MEM_HOST) == VOFOD_OK)
+        std::printf("scan %3d against the map: %u none, %u agree, %u empty, %u nearer, %u through, %u missing, %u beyond\n", k, counts[VOFOD_VERDICT_NONE], counts[VOFOD_VERDICT_AGREES],
+                    counts[VOFOD_VERDICT_EMPTY], counts[VOFOD_VERDICT_NEARER], counts[VOFOD_VERDICT_THROUGH], counts[VOFOD_VERDICT_MISSING], counts[VOFOD_VERDICT_BEYOND]);
+      else
+        std::fprintf(stderr, "map_render_scans: %s\n", vofod_last_error_string(h));
+    }
     vofod_detection dets[64];
     size_t n_det = 0;
     const int st = vofod_process_scan(h, &scan, c->tf, VOFOD_SCAN_DEFAULT, dets, 64, &n_det, nullptr);

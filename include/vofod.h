@@ -800,7 +800,7 @@ int vofod_map_shift(vofod_handle* h, const int32_t shift_voxels[3], const float 
  * pass (float or exact) or a sepclusters pass pending, runs on the handle's stream behind what was enqueued, returns after one
  * synchronisation and changes nothing another call can observe - maps, latches, ids, detections, tickets, snapshot chains.
  * World store: the window is rendered; a ray that reaches the window's face is LEFT.  Rendering through the store's tiles is out
- * of scope, and so are a pose per column (col_tfs) and the occupancy image as a shortcut for its own threshold. */
+ * of scope, and so is the occupancy image as a shortcut for its own threshold.  A pose per column (col_tfs): SCANS AGAINST THE MAP. */
 enum { VOFOD_RENDER_NOT_CAST = 0, VOFOD_RENDER_HIT = 1, VOFOD_RENDER_END = 2, VOFOD_RENDER_LEFT = 3 };
 int vofod_map_render(vofod_handle* h, const float* tfs /* n_views * 12, host */, size_t n_views,
                      float threshold, float max_distance,
@@ -809,6 +809,67 @@ int vofod_map_render(vofod_handle* h, const float* tfs /* n_views * 12, host */,
                      uint8_t* what   /* same, nullable */,
                      float* t_in_out /* n_views * w * h * 2, nullable */,
                      int32_t out_memspace);
+
+/* ------------------------------------------------- SCANS AGAINST THE MAP (product library only)
+ *
+ * SCANS AGAINST THE MAP.  MAP RENDER with SCANS as its views: every ray is cast the way the scan measured it - from the pose of its
+ * measurement column where the scan carries col_tfs - and every measured return is compared with what the map says the ray should
+ * have met: a verdict per pixel, and the number of pixels of each verdict per scan.  Which returns lie in space the map holds
+ * free?  Which share of this scan agrees with the map under this pose?  Answered on the device by the walk of MAP RENDER
+ * (k_map_render_scans, vofod_amd/csrc/map_render.h: the same kernel template); the CPU oracle does not have it.
+ *
+ * Views.  View v is scans[v] under [R | t] = tfs[12v .. 12v + 12).  Of a scan the call reads width, height, memspace, col_tfs, and
+ * range with stride_bytes - range only when verdict or counts is asked for; x, y, z and intensity are never read.  Device-resident
+ * range columns and pose tables are read in place, host-resident ones are staged in the call's own workspace; the caller may
+ * overwrite every input when the call returns.
+ *
+ * Ray of pixel i = row * width + col of view v.
+ *     col_tfs == NULL   the rigid ray of MAP RENDER: every output is bit for bit what vofod_map_render gives for tfs[v].
+ *     col_tfs != NULL   d', o' exactly as MOTION-COMPENSATED RAYS defines them: m = (col + shift_by_row[row]) mod width with the
+ *                       handle's column shifts (vofod_set_column_shift), T = col_tfs[m], in that section's association, nothing
+ *                       fused; then dir = R d' and start = (R o') + t in MAP RENDER's association.  This holds whatever
+ *                       vofod_set_raycast_motion says: that switch belongs to the raycast role.
+ * The two matrices are never multiplied together.  A ray whose own start lies outside the map is NOT_CAST.
+ *
+ * Walk and outputs.  The walk and the outputs range, voxel, what and t_in_out are MAP RENDER's, word for word, with
+ * length = max_distance.
+ *
+ * Verdict.  With r = range[i] of the scan (uint32 millimetres), rm = (float) r * 0.001f (the decode's expression),
+ * tol = tolerance, (what, t_in, t_out) the render of the same pixel and mask the handle's mask - every operation float32, rounded
+ * once, the comparisons the float compares (a NaN makes them false):
+ *     what == NOT_CAST                          -> NONE
+ *     r == 0 && mask[i] == 0                    -> NONE      (the reference casts no ray there either: vofod_nodelet.cpp:1449)
+ *     r == 0:   what == HIT -> MISSING          else -> EMPTY
+ *     r  > 0, what == HIT:  (rm + tol) < t_in   -> NEARER    (a return in space the map holds free, in front of its surface)
+ *                           rm > (t_out + tol)  -> THROUGH   (a return behind the surface the map expects)
+ *                           otherwise           -> AGREES
+ *     r  > 0, what == END or LEFT:
+ *                           (rm + tol) < t_out  -> NEARER
+ *                           otherwise           -> BEYOND    (beyond the rendered length or the map's face: nothing to compare)
+ * verdict holds n_scans * width * height of them, indexed as the render outputs, in out_memspace (no alignment asked).
+ *
+ * Counts.  counts[8v + c] is the number of pixels of view v with verdict c; slot 7 is 0; the eight slots of a view sum to
+ * width * height.  Integers: exact, whatever the order they were counted in.  counts is ALWAYS host memory.
+ *
+ * Refusals, with nothing written to any output.  VOFOD_ERR_INVALID_ARG: n_scans == 0 or above 65535, scans or tfs NULL, all six
+ * outputs NULL, !(max_distance > 0), a NaN threshold, a tolerance that is NaN or negative, an unknown memspace of the outputs or of
+ * any scan, a misaligned device output (MAP RENDER's rule), verdict or counts asked for with a scan whose range is NULL, a
+ * device-resident range whose base or stride is no multiple of 4, a device-resident col_tfs that is not 4-byte aligned.
+ * VOFOD_ERR_SIZE_MISMATCH: a scan whose width or height is not the handle's.  VOFOD_ERR_SENSOR_OUTSIDE_MAP: the origin t of any
+ * tfs[v] lies outside the map.  VOFOD_ERR_DEVICE as everywhere.
+ *
+ * Admission is MAP RENDER's: the call reads the voxel map only, uses its own workspace, makes one launch on the handle's stream
+ * and one synchronisation, is admitted with tickets in flight and with a raycast or sepclusters pass pending, and changes nothing
+ * another call can observe.  Out of scope: shortening a walk by the measured range, rendering through the world store's tiles,
+ * a signed residual output (range gives it). */
+enum { VOFOD_VERDICT_NONE = 0, VOFOD_VERDICT_AGREES = 1, VOFOD_VERDICT_EMPTY = 2, VOFOD_VERDICT_NEARER = 3,
+       VOFOD_VERDICT_THROUGH = 4, VOFOD_VERDICT_MISSING = 5, VOFOD_VERDICT_BEYOND = 6 };
+int vofod_map_render_scans(vofod_handle* h, const vofod_scan* scans, const float* tfs /* n_scans * 12, host */, size_t n_scans,
+                           float threshold, float max_distance, float tolerance,
+                           uint32_t* range, uint32_t* voxel, uint8_t* what, float* t_in_out,   /* as vofod_map_render, nullable */
+                           uint8_t* verdict /* n_scans * w * h, nullable, out_memspace */,
+                           uint32_t* counts /* n_scans * 8, nullable, ALWAYS host */,
+                           int32_t out_memspace);
 
 /* ------------------------------------------------- WORLD STORE (product library only)
  *

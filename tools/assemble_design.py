@@ -117,6 +117,10 @@ for name, prefix in (("R26_MEASURED", "measured: "), ("R26_BENCH", "bench: "), (
 r27 = (P / "r27_map_render.txt").read_text().splitlines()
 for name, prefix in (("R27_MEASURED", "measured: "), ("R27_RESOURCES", "resources: "), ("R27_BENCH", "bench: "), ("R27_MUTATIONS", "mutations: ")):
     sub[name] = next(l for l in r27 if l.startswith(prefix)).removeprefix(prefix)
+# §5.20: the same four lines of profiles/r30_map_render_scans.txt
+r30 = (P / "r30_map_render_scans.txt").read_text().splitlines()
+for name, prefix in (("R30_MEASURED", "measured: "), ("R30_RESOURCES", "resources: "), ("R30_BENCH", "bench: "), ("R30_MUTATIONS", "mutations: ")):
+    sub[name] = next(l for l in r30 if l.startswith(prefix)).removeprefix(prefix)
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

@@ -210,6 +210,32 @@ class VoFOD:
                          "vofod_map_render", allow)
         return (rng, vox, what, tio) if st == capi.OK else st
 
+    def map_render_scans(self, scans, tfs, threshold: float, max_distance: float, tolerance: float = 0.0, out=None, allow: Sequence[int] = ()):
+        """Scans against the map (vofod_map_render_scans): view v is `scans[v]` (ScanData; one with `col_tfs` is cast from a pose per
+        measurement column) under `tfs[v]`.  Returns a namespace of range, voxel, what, t_in_out - shaped like map_render's - and
+        verdict (capi.VERDICT_* as uint8 [views, h, w]) and counts (uint32 [views, 8]: the pixels of each verdict).  `out` =
+        (range, voxel, what, t_in_out, verdict) device addresses on the handle's device, None for an output left out: they are
+        written in place and come back as None; counts is host memory always.  Where a scan has no `range`, verdict and counts are None.  A status in `allow` is returned in place of the result."""
+        from types import SimpleNamespace
+
+        scans = [scans] if isinstance(scans, ScanData) else list(scans)
+        t = np.ascontiguousarray(tfs, dtype=np.float32).reshape(-1, 12)
+        nv, hh, ww = len(scans), int(self.sp.sensor_vrays), int(self.sp.sensor_hrays)
+        assert t.shape[0] == nv, "one tf per scan"
+        arr = (capi.Scan * nv)(*[s.as_c() for s in scans])
+        compare = all(s.range is not None for s in scans)  # (scans without a range: the render alone, verdict and counts None)
+        counts = np.zeros((nv, 8), dtype=np.uint32) if compare else None
+        if out is not None:
+            ptrs = [None if a is None else C.c_void_p(int(a)) for a in out]
+            st = self._check(self.lib.map_render_scans(self.h, arr, capi.ptr(t), nv, float(threshold), float(max_distance), float(tolerance), *ptrs, capi.ptr(counts), capi.MEM_DEVICE),
+                             "vofod_map_render_scans", allow)
+            return SimpleNamespace(range=None, voxel=None, what=None, t_in_out=None, verdict=None, counts=counts) if st == capi.OK else st
+        r = SimpleNamespace(range=np.zeros((nv, hh, ww), dtype=np.uint32), voxel=np.zeros((nv, hh, ww), dtype=np.uint32), what=np.zeros((nv, hh, ww), dtype=np.uint8),
+                            t_in_out=np.zeros((nv, hh, ww, 2), dtype=np.float32), verdict=np.zeros((nv, hh, ww), dtype=np.uint8) if compare else None, counts=counts)
+        st = self._check(self.lib.map_render_scans(self.h, arr, capi.ptr(t), nv, float(threshold), float(max_distance), float(tolerance), capi.ptr(r.range), capi.ptr(r.voxel),
+                                                   capi.ptr(r.what), capi.ptr(r.t_in_out), capi.ptr(r.verdict), capi.ptr(r.counts), capi.MEM_HOST), "vofod_map_render_scans", allow)
+        return r if st == capi.OK else st
+
     # ---- world store (include/vofod.h, WORLD STORE): the voxel map as a window onto a sparse map of a larger box
     def world_enable(self, margin_lo, margin_hi, max_tiles: int, allow: Sequence[int] = ()):
         """The box is [-margin_lo, map_size + margin_hi) in world indices (voxels, the window's origin K = 0 now); the pool holds
