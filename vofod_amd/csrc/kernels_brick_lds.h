@@ -190,6 +190,25 @@ __device__ __forceinline__ uint32_t lb_cas16(uint16_t* par, uint32_t i, uint32_t
   }
 }
 
+// union of two roots: the larger is hooked under the smaller (labels: smallest member); a root that lost its place meanwhile
+// is followed to its new parent
+__device__ __forceinline__ void lb_link(uint16_t* par, uint32_t ra, uint32_t rb)
+{
+  while (ra != rb)
+  {
+    if (ra < rb)
+    {
+      const uint32_t tmp = ra;
+      ra = rb;
+      rb = tmp;
+    }
+    const uint32_t old = lb_cas16(par, ra, ra, rb);
+    if (old == ra)
+      break;
+    ra = old;
+  }
+}
+
 __device__ __forceinline__ uint32_t lb_node(const uint32_t* bits, const uint16_t* pre, uint32_t b)
 {
   return pre[b >> 5] + __popc(bits[b >> 5] & ((1u << (b & 31u)) - 1u));

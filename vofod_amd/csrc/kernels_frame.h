@@ -44,10 +44,6 @@ namespace vk
 {
 
 constexpr int FR_THREADS = 1024;
-#ifndef FR_WRITE_BACK_DEF
-#define FR_WRITE_BACK_DEF 1
-#endif
-constexpr bool FR_WRITE_BACK = FR_WRITE_BACK_DEF != 0;  // pass 1 writes the converted codes back (0: pass 3a converts again)
 constexpr int FR_BW64 = LB_BITWORDS / 2;  // 64-bit words of the brick-lattice bitmap
 #ifndef FR_WAVE_PRIO
 #define FR_WAVE_PRIO 3
@@ -212,6 +208,22 @@ __device__ __forceinline__ void wave_bbox(float (&mn)[3], float (&mx)[3])
   }
 }
 
+// Append through a ballot: the lanes with `pred` take consecutive places behind *counter.  The first of them does one atomic add for
+// the wave (none at all when no lane has anything); a lane's place is the wave's base + the lanes with `pred` below it.  Returns the
+// place - of use where `pred` holds; the capacity check is the caller's.
+__device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool pred, int lane)
+{
+  const unsigned long long m = __ballot(pred);
+  if (!m)
+    return 0u;
+  const int leader = __ffsll(static_cast<long long>(m)) - 1;
+  uint32_t base = 0;
+  if (lane == leader)
+    base = atomicAdd(counter, static_cast<uint32_t>(__popcll(m)));
+  base = __builtin_amdgcn_readlane(base, leader);
+  return base + __popcll(m & ((1ull << lane) - 1ull));
+}
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Packed f32 operation of a wave-uniform scalar with a pair of points: op_sel_hi:[0,1] makes the upper lane read the LOW dword
@@ -263,6 +275,31 @@ __device__ __forceinline__ uint32_t fr_hsum16(unsigned long long x)
   return static_cast<uint32_t>(x & 0xffffu) + static_cast<uint32_t>((x >> 16) & 0xffffu) + static_cast<uint32_t>((x >> 32) & 0xffffu) + static_cast<uint32_t>(x >> 48);
 }
 
+// rank of the voxel at bit p of brick word W: Qz = base rank of its lattice row group (layer zz = p >> 4), Mz = that layer's four yy
+// channel offsets of the brick inside its rows (16 bits each), then the brick's own voxels of the row below the bit
+__device__ __forceinline__ uint32_t fr_rank(uint32_t Qz, unsigned long long Mz, unsigned long long W, uint32_t p)
+{
+  const uint32_t yy = (p >> 2) & 3u, xx = p & 3u;
+  const uint32_t nib = static_cast<uint32_t>(W >> (p & ~3u)) & 0xfu;
+  return Qz + (static_cast<uint32_t>(Mz >> (16 * yy)) & 0xffffu) + __popc(nib & ((1u << xx) - 1u));
+}
+
+// four counts as the 16-bit fields of one word (one per lattice layer zz)
+__device__ __forceinline__ unsigned long long fr_pack4x16(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3)
+{
+  return static_cast<unsigned long long>(c0) | (static_cast<unsigned long long>(c1) << 16) | (static_cast<unsigned long long>(c2) << 32) | (static_cast<unsigned long long>(c3) << 48);
+}
+
+// the window slots of a stencil row (slot s: dx = s - R) as the brick at the other end of the pair sees them: that neighbour is the
+// pair's base brick and sees this brick at (-dx, ddy, ddz), i.e. slot 2R - s
+__device__ __forceinline__ uint32_t fr_reverse_slots(uint32_t mask, int R)
+{
+  uint32_t rev = 0;
+  for (int sl = 0; sl <= 2 * R; sl++)
+    rev |= ((mask >> (2 * R - sl)) & 1u) << sl;
+  return rev;
+}
+
 __device__ __forceinline__ unsigned long long fr_shfl64(unsigned long long v, int src)
 {
   const uint32_t lo = __shfl(static_cast<uint32_t>(v), src), hi = __shfl(static_cast<uint32_t>(v >> 32), src);
@@ -273,6 +310,38 @@ template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ unsigned long long dpp_mov0_64(unsigned long long v)
 {
   return static_cast<unsigned long long>(dpp_mov0<CTRL, ROW_MASK>(static_cast<uint32_t>(v))) | (static_cast<unsigned long long>(dpp_mov0<CTRL, ROW_MASK>(static_cast<uint32_t>(v >> 32))) << 32);
+}
+
+// wave_incl_scan (kernels_voxelize.h) for 64-bit values: four 16-bit fields ride in one scan
+__device__ __forceinline__ unsigned long long wave_incl_scan(unsigned long long v)
+{
+  v += dpp_mov0_64<0x111, 0xf>(v);
+  v += dpp_mov0_64<0x112, 0xf>(v);
+  v += dpp_mov0_64<0x114, 0xf>(v);
+  v += dpp_mov0_64<0x118, 0xf>(v);
+  v += dpp_mov0_64<0x142, 0xa>(v);
+  v += dpp_mov0_64<0x143, 0xc>(v);
+  return v;
+}
+
+// Exclusive scan of `v` over the block's 16 waves: a wave scan, the waves' sums through s_w behind ONE barrier (stores the caller
+// made before the call pass it, too), then the sums of the waves in front.  each(x) sees every wave's sum: the caller adds up the
+// totals it needs there - packed fields that fit a wave's sum may not fit the block's.
+template <typename T, typename F>
+__device__ __forceinline__ T fr_block_excl_scan(T v, T* s_w, int lane, int wave, F&& each)
+{
+  const T incl = wave_incl_scan(v);
+  if (lane == 63)
+    s_w[wave] = incl;
+  __syncthreads();
+  T excl = incl - v;
+  for (int w = 0; w < FR_THREADS / 64; w++)
+  {
+    const T x = s_w[w];
+    excl += w < wave ? x : static_cast<T>(0);
+    each(x);
+  }
+  return excl;
 }
 
 // Segmented inclusive scan over the wave's lanes: four 64-bit values per lane, a segment starts at every lane whose
@@ -459,6 +528,16 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   if (tid < CF_MAX / 32)
     s_taint[tid] = s_troot[tid] = 0u;
   __syncthreads();
+  // the frame leaves the kernel: its status for the host (a retry status: the batch runs again on the next kernels of the chain),
+  // the count of bricks where the host reports it, no voxels.  The caller returns.
+  auto fail = [&](int32_t status, auto... n_bricks) {
+    if (tid == 0)
+    {
+      h.status = status;
+      ((h.n_bricks = n_bricks), ...);
+      h.V = 0;
+    }
+  };
   // bit of a packed brick in the brick bitmap
   auto brick_lin = [&](uint32_t p) -> uint32_t { return (((p >> 18) & 63u) * static_cast<uint32_t>(nby) + ((p >> 9) & 511u)) * static_cast<uint32_t>(nbx) + (p & 511u); };
   // brick code of a reference cell: packed brick coordinates (fr_pack), then the bit inside the brick
@@ -481,11 +560,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     const uint32_t in_rounds = (n_pts + IN_ROUND - 1u) / IN_ROUND;
     if (static_cast<uint64_t>(in_rounds) * 64u * IN_PPT > seg_cap)
     {
-      if (tid == 0)
-      {
-        h.status = VOFOD_ERR_CAPACITY;  // (a cloud beyond the workspace's code list: the host sizes it for the sensor)
-        h.V = 0;
-      }
+      fail(VOFOD_ERR_CAPACITY);  // (a cloud beyond the workspace's code list: the host sizes it for the sensor)
       return;
     }
     float fmn[3] = {INFINITY, INFINITY, INFINITY}, fmx[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -955,30 +1030,15 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     for (int r = 0; r < WPT; r++)
       if (tid * WPT + r < FR_BW64)
         cnt += __popcll(s_bits64[tid * WPT + r]);
-    const uint32_t incl = wave_incl_scan(cnt);
-    if (lane == 63)
-      s_wsum[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, total = 0;
-    for (int w = 0; w < FR_THREADS / 64; w++)
-    {
-      const uint32_t x = s_wsum[w];
-      base += w < wave ? x : 0u;
-      total += x;
-    }
+    uint32_t total = 0;
+    uint32_t run = fr_block_excl_scan(cnt, s_wsum, lane, wave, [&](uint32_t x) { total += x; });
     if (tid == 0)
       s_n = total;
     if (total > lb_limit)  // <= LB_MAX (lower only in the tests of the fallback)
     {
-      if (tid == 0)
-      {
-        h.status = CCL_RETRY_STATUS;
-        h.n_bricks = total;
-        h.V = 0;
-      }
+      fail(CCL_RETRY_STATUS, total);
       return;
     }
-    uint32_t run = base + incl - cnt;
 #pragma unroll
     for (int r = 0; r < WPT; r++)
       if (tid * WPT + r < FR_BW64)
@@ -1013,6 +1073,23 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
         creg[r][u] = FR_CODE_NONE;
     }
   }
+  // a wave's walk over its codes: round(c) for the rounds held in creg, then for the rest of the segment, fetched through load_codes;
+  // listed(base, c) follows every round that came from the list (3a stores the rewritten codes there again)
+  auto walk_codes = [&](auto&& round, auto&& listed) {
+#pragma unroll
+    for (int r = 0; r < RR; r++)
+      if (static_cast<uint32_t>(r) * 64u * KPT < wcnt)
+        round(creg[r]);
+    for (uint32_t rb = static_cast<uint32_t>(RR) * 64u * KPT; rb < wcnt; rb += 64u * KPT)
+    {
+      const uint32_t base = rb + lane * KPT;
+      uint32_t c[KPT];
+      load_codes(base, c);
+      round(c);
+      listed(base, c);
+    }
+  };
+  auto read_only = [](uint32_t, const uint32_t (&)[KPT]) {};
   {
     auto or_word = [&](uint32_t node, unsigned long long acc) {
       uint32_t* w32 = reinterpret_cast<uint32_t*>(&s_word[node]);
@@ -1046,16 +1123,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       if (cur != FR_CODE_NONE)
         or_word(cur_node, acc);
     };
-#pragma unroll
-    for (int r = 0; r < RR; r++)
-      if (static_cast<uint32_t>(r) * 64u * KPT < wcnt)
-        words_round(creg[r]);
-    for (uint32_t rb = static_cast<uint32_t>(RR) * 64u * KPT; rb < wcnt; rb += 64u * KPT)
-    {
-      const uint32_t base = rb + lane * KPT;
-      uint32_t c[KPT];
-      load_codes(base, c);
-      words_round(c);
+    auto store_codes = [&](uint32_t base, const uint32_t (&c)[KPT]) {
       if (base + KPT <= wcnt)
       {
 #pragma unroll
@@ -1069,7 +1137,8 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
           if (base + u < wcnt)
             seg[base + u] = c[u];
       }
-    }
+    };
+    walk_codes(words_round, store_codes);
     // the fragile points' codes (the side list: a fraction of a percent of the frame), one per thread and round
     for (uint32_t i = tid; i < n_frag; i += FR_THREADS)
     {
@@ -1228,15 +1297,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
               if (g0 + j < NPT && i < n)
                 s_vbase[i] = pf ? static_cast<uint16_t>(0u) : FR_VBASE_NONE;
             }
-            const unsigned long long m = __ballot(pf);
-            if (!m)
-              continue;
-            const int leader = __ffsll(static_cast<long long>(m)) - 1;
-            uint32_t base = 0;
-            if (lane == leader)
-              base = atomicAdd(&s_npf, static_cast<uint32_t>(__popcll(m)));
-            base = __builtin_amdgcn_readlane(base, leader);
-            const uint32_t pos = base + __popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t pos = wave_append(&s_npf, pf, lane);
             if (pf && pos < static_cast<uint32_t>(CF_MAX))
               s_pf[pos] = static_cast<uint16_t>((g0 + j) * FR_THREADS + tid);
           }
@@ -1244,12 +1305,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
         __syncthreads();
         if (s_npf > static_cast<uint32_t>(CF_MAX))
         {
-          if (tid == 0)
-          {
-            h.status = CF_RETRY_STATUS;  // (a cold map: nearly every brick is pure far) the batch takes the full clustering
-            h.n_bricks = s_npf;
-            h.V = 0;
-          }
+          fail(CF_RETRY_STATUS, s_npf);  // (a cold map: nearly every brick is pure far) the batch takes the full clustering
           return false;
         }
       }
@@ -1284,36 +1340,23 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       pc[r] = (lean_on && i < n && s_vbase[i] == FR_VBASE_NONE) ? 0u : c;
       sum += (c << 16) | pc[r];
     }
-    const uint32_t incl = wave_incl_scan(sum);
-    if (lane == 63)
-      s_wsum[wave] = incl;
     if (tid == 0)
       s_nlc = 0;
-    __syncthreads();  // (also: every thread has parked its part of the bitmap)
-    uint32_t run = (incl - sum) & 0xffffu;
-    for (int w = 0; w < FR_THREADS / 64; w++)
-    {
-      const uint32_t x = s_wsum[w];
-      run += w < wave ? x & 0xffffu : 0u;
+    // (the scan's barrier also: every thread has parked its part of the bitmap.  The block's totals are added up field by field: V
+    // may pass 16 bits, which the checks below catch; the packed prefix is used only behind them)
+    uint32_t run = fr_block_excl_scan(sum, s_wsum, lane, wave, [&](uint32_t x) {
       V += x >> 16;
       Vc += x & 0xffffu;
-    }
+    });
+    run &= 0xffffu;
     if (V > g.vox_cap)
     {
-      if (tid == 0)
-      {
-        h.status = VOFOD_ERR_CAPACITY;  // as k_scan_b
-        h.V = 0;
-      }
+      fail(VOFOD_ERR_CAPACITY);  // as k_scan_b
       return;
     }
     if (V > FR_CNT_CAP || V > 65535u)
     {
-      if (tid == 0)
-      {
-        h.status = CCL_RETRY_STATUS;  // more voxels than byte counters: the batch takes the general kernels
-        h.V = 0;
-      }
+      fail(CCL_RETRY_STATUS);  // more voxels than byte counters: the batch takes the general kernels
       return;
     }
 #pragma unroll
@@ -1420,28 +1463,13 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
           }
         }
       };
-#pragma unroll
-      for (int r = 0; r < RR; r++)
-        if (static_cast<uint32_t>(r) * 64u * KPT < wcnt)
-          filter_round(creg[r]);
-      for (uint32_t rb = static_cast<uint32_t>(RR) * 64u * KPT; rb < wcnt; rb += 64u * KPT)
-      {
-        uint32_t c[KPT];
-        load_codes(rb + lane * KPT, c);
-        filter_round(c);
-      }
+      walk_codes(filter_round, read_only);
       for (uint32_t i0 = 0; i0 < n_frag; i0 += FR_THREADS)  // (wave-uniform trip count: the reservation below ballots the wave)
       {
         const uint32_t i = i0 + tid;
         const uint32_t cd = i < n_frag ? reinterpret_cast<const uint32_t*>(fragl + i)[3] : FR_CODE_NONE;
         const bool hit = cd != FR_CODE_NONE && s_vbase[min(cd >> 6, static_cast<uint32_t>(LB_MAX - 1))] != FR_VBASE_NONE;
-        const unsigned long long m = __ballot(hit);
-        if (!m)
-          continue;
-        uint32_t pos = 0;
-        if (lane == 0)
-          pos = atomicAdd(&s_nlc, static_cast<uint32_t>(__popcll(m)));
-        pos = __builtin_amdgcn_readlane(pos, 0) + __popcll(m & ((1ull << lane) - 1ull));
+        const uint32_t pos = wave_append(&s_nlc, hit, lane);
         if (hit && pos < FR_LEAN_COUNT_MAX)
           s_lc[pos] = cd;
       }
@@ -1462,16 +1490,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       prof[static_cast<size_t>(FRAME) * 32 + 28] = (static_cast<unsigned long long>(min(s_nlc, 0xfffffu)) << 24) | (static_cast<unsigned long long>(Vc) << 44) | (counted ? 1ull << 63 : 0ull);
     if (!counted)
     {
-#pragma unroll
-      for (int r = 0; r < RR; r++)
-        if (static_cast<uint32_t>(r) * 64u * KPT < wcnt)
-          count_round(creg[r]);
-      for (uint32_t rb = static_cast<uint32_t>(RR) * 64u * KPT; rb < wcnt; rb += 64u * KPT)
-      {
-        uint32_t c[KPT];
-        load_codes(rb + lane * KPT, c);
-        count_round(c);
-      }
+      walk_codes(count_round, read_only);
       for (uint32_t i = tid; i < n_frag; i += FR_THREADS)
       {
         const uint32_t cd = reinterpret_cast<const uint32_t*>(fragl + i)[3];
@@ -1704,8 +1723,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
           row_prev = row;
           const unsigned long long W = s_word[i];
           const uint32_t lo = static_cast<uint32_t>(W), hi = static_cast<uint32_t>(W >> 32);
-          tz[r] = static_cast<unsigned long long>(__popc(lo & 0xffffu)) | (static_cast<unsigned long long>(__popc(lo >> 16)) << 16) | (static_cast<unsigned long long>(__popc(hi & 0xffffu)) << 32) |
-                  (static_cast<unsigned long long>(__popc(hi >> 16)) << 48);
+          tz[r] = fr_pack4x16(__popc(lo & 0xffffu), __popc(lo >> 16), __popc(hi & 0xffffu), __popc(hi >> 16));
           sum += tz[r];
         }
       }
@@ -1735,29 +1753,13 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
         {
           const ulonglong2* src = reinterpret_cast<const ulonglong2*>(rowT + static_cast<size_t>(rows[r]) * 4);
           const ulonglong2 t0 = src[0], t1 = src[1];
-          tz[r] = static_cast<unsigned long long>(fr_hsum16(t0.x)) | (static_cast<unsigned long long>(fr_hsum16(t0.y)) << 16) | (static_cast<unsigned long long>(fr_hsum16(t1.x)) << 32) |
-                  (static_cast<unsigned long long>(fr_hsum16(t1.y)) << 48);
+          tz[r] = fr_pack4x16(fr_hsum16(t0.x), fr_hsum16(t0.y), fr_hsum16(t1.x), fr_hsum16(t1.y));
           sum += tz[r];
         }
       }
     }
-    unsigned long long incl = sum;
-    incl += dpp_mov0_64<0x111, 0xf>(incl);
-    incl += dpp_mov0_64<0x112, 0xf>(incl);
-    incl += dpp_mov0_64<0x114, 0xf>(incl);
-    incl += dpp_mov0_64<0x118, 0xf>(incl);
-    incl += dpp_mov0_64<0x142, 0xa>(incl);
-    incl += dpp_mov0_64<0x143, 0xc>(incl);
-    if (lane == 63)
-      s_w4[wave] = incl;
-    __syncthreads();
-    unsigned long long G = incl - sum, tot = 0ull;
-    for (int w = 0; w < FR_THREADS / 64; w++)
-    {
-      const unsigned long long x = s_w4[w];
-      G += w < wave ? x : 0ull;
-      tot += x;
-    }
+    unsigned long long tot = 0ull;
+    unsigned long long G = fr_block_excl_scan(sum, s_w4, lane, wave, [&](unsigned long long x) { tot += x; });
     if (tid == 0)
       s_gs[FR_MAX_NBZ] = tot;  // the sentinel behind the last slab
     uint32_t bz_prev = (i0 > 0 && i0 < n) ? static_cast<uint32_t>(fr_bz(s_xyz[i0 - 1])) : 0xffffffffu;
@@ -1796,7 +1798,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   }
   __syncthreads();
   FR_STAMP(5);
-  // (the rank of a voxel, as pass d below computes it - for the close-first path, which comes back to its few far bricks later)
+  // (the rank of a voxel: for pass d below, and for the close-first path, which comes back to its few far bricks later)
   auto rank_ctx = [&](uint32_t i, uint32_t xyz, unsigned long long (&M)[4], uint32_t (&Q)[4]) {
     const uint32_t row = fr_row(xyz, nby);
     const ulonglong2 a0 = nodeA[2 * i], a1 = nodeA[2 * i + 1];
@@ -1817,11 +1819,10 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     Q[0] = qq.x + qc.x, Q[1] = qq.y + qc.y, Q[2] = qq.z + qc.z, Q[3] = qq.w + qc.w;
   };
   auto rank_of = [&](unsigned long long W, int p, const unsigned long long (&M)[4], const uint32_t (&Q)[4]) -> uint32_t {
-    const int zz = p >> 4, yy = (p >> 2) & 3, xx = p & 3;
+    const int zz = p >> 4;
     const unsigned long long Mz = zz == 0 ? M[0] : zz == 1 ? M[1] : zz == 2 ? M[2] : M[3];
     const uint32_t Qz = zz == 0 ? Q[0] : zz == 1 ? Q[1] : zz == 2 ? Q[2] : Q[3];
-    const uint32_t nib = static_cast<uint32_t>(W >> (p & ~3)) & 0xfu;
-    return Qz + (static_cast<uint32_t>(Mz >> (16 * yy)) & 0xffffu) + __popc(nib & ((1u << xx) - 1u));
+    return fr_rank(Qz, Mz, W, static_cast<uint32_t>(p));
   };
   // Pass d: the voxel records leave at their ranks (voxel_grid_weighted.cpp:171-188): centre, weight 1 (+ extras below),
   // node of the brick (for the label pass); the lattice key only for the general kernels that may follow (!write_tables).
@@ -1831,29 +1832,10 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   {
     const uint32_t i = lean_on ? static_cast<uint32_t>(s_pf[e]) : e;
     const uint32_t xyz = s_xyz[i];
-    const uint32_t row = fr_row(xyz, nby);
     const unsigned long long W = s_word[i];
     unsigned long long M[4];
     uint32_t Q[4];
-    {
-      const ulonglong2 a0 = nodeA[2 * i], a1 = nodeA[2 * i + 1];
-      const ulonglong2* src = reinterpret_cast<const ulonglong2*>(rowT + static_cast<size_t>(row) * 4);
-      const ulonglong2 t0 = src[0], t1 = src[1];
-      const uint4 qq = *reinterpret_cast<const uint4*>(rowQ + static_cast<size_t>(row) * 4);
-      const bool began = (a1.y & FR_BEGAN) != 0ull;
-      M[0] = fr_excl16(t0.x) + a0.x;
-      M[1] = fr_excl16(t0.y) + a0.y;
-      M[2] = fr_excl16(t1.x) + a1.x;
-      M[3] = fr_excl16(t1.y) + (a1.y & ~FR_BEGAN);
-      if (!began)
-      {
-#pragma unroll
-        for (int zz = 0; zz < 4; zz++)
-          M[zz] += s_cin[i >> 6][zz];
-      }
-      const uint4 qc = *reinterpret_cast<const uint4*>(&s_qc[fr_bz(xyz)][0]);
-      Q[0] = qq.x + qc.x, Q[1] = qq.y + qc.y, Q[2] = qq.z + qc.z, Q[3] = qq.w + qc.w;
-    }
+    rank_ctx(i, xyz, M, Q);
     const int bx = fr_bx(xyz), by = fr_by(xyz), bz = fr_bz(xyz);
     unsigned long long w = W;
     bool first = true;
@@ -1863,10 +1845,10 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       const int p = __ffsll(static_cast<long long>(w)) - 1;
       w &= w - 1;
       const int zz = p >> 4, yy = (p >> 2) & 3, xx = p & 3;
+      // (the selects stand here in line: through rank_of the compiler turned them into a ladder of divergent branches inside this loop)
       const unsigned long long Mz = zz == 0 ? M[0] : zz == 1 ? M[1] : zz == 2 ? M[2] : M[3];
       const uint32_t Qz = zz == 0 ? Q[0] : zz == 1 ? Q[1] : zz == 2 ? Q[2] : Q[3];
-      const uint32_t nib = static_cast<uint32_t>(W >> (p & ~3)) & 0xfu;
-      const uint32_t rank = Qz + (static_cast<uint32_t>(Mz >> (16 * yy)) & 0xffffu) + __popc(nib & ((1u << xx) - 1u));
+      const uint32_t rank = fr_rank(Qz, Mz, W, static_cast<uint32_t>(p));
       const int k0 = 4 * bx + xx + o0, k1 = 4 * by + yy + o1, k2 = 4 * bz + zz + o2;  // the frame's own cell
       float4 pt;
       pt.x = __fadd_rn(__fmul_rn(__fadd_rn(static_cast<float>(k0), 0.5f), g.leaf[0]), hoff0);
@@ -1923,12 +1905,10 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
         if (lean_on && s_vbase[node[u]] == FR_VBASE_NONE)
           continue;  // lean: the record of this voxel was not written
         const uint32_t add = (rec[u] >> 25) + 1u, p = rec[u] & 63u;
-        const uint32_t zz = p >> 4, yy = (p >> 2) & 3u, xx = p & 3u;
         unsigned long long Mz = fr_excl16(tz[u]) + (az[u] & ~FR_BEGAN);
         if (!(a3[u] & FR_BEGAN))
-          Mz += s_cin[node[u] >> 6][zz];
-        const uint32_t nib = static_cast<uint32_t>(wv[u] >> (p & ~3u)) & 0xfu;
-        const uint32_t rank = qz[u] + (static_cast<uint32_t>(Mz >> (16 * yy)) & 0xffffu) + __popc(nib & ((1u << xx) - 1u));
+          Mz += s_cin[node[u] >> 6][p >> 4];
+        const uint32_t rank = fr_rank(qz[u], Mz, wv[u], p);
         atomicAdd(reinterpret_cast<uint32_t*>(&va.pts[rank].w), add);
       }
     }
@@ -1971,11 +1951,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   const uint32_t cap_axis = 3u * n, cap_near = 10u * n;
   if (!cf && hcap < 14u * n)
   {
-    if (tid == 0)
-    {
-      h.status = CCL_RETRY_STATUS;
-      h.V = 0;
-    }
+    fail(CCL_RETRY_STATUS);
     return;
   }
   const uint32_t cap_far = hcap - cap_axis - cap_near;
@@ -2026,6 +2002,24 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       ext_ok &= (static_cast<float>(box[3 + a] - box[a]) * g.leaf[a] <= up.cand_max_extent);
     return !close && static_cast<int>(size) >= up.min_points && ext_ok;
   };
+  // (diagnostics: a frame's counts behind its stamps, slots 24-31; each clustering brings the four that are its own)
+  auto diag = [&](unsigned long long d24, unsigned long long d25, unsigned long long d30, unsigned long long d31) {
+    if (prof && tid == 0)
+    {
+      unsigned long long* slot = prof + static_cast<size_t>(FRAME) * 32;
+      slot[24] = d24;
+      slot[25] = d25;
+      slot[26] = n;
+      slot[27] = n_keys;
+      if (cf)
+        slot[28] |= min(s_ne, 0xffffffu);  // (pass 3b left the lean count's figures in the upper bits)
+      else
+        slot[28] = s_ne;
+      slot[29] = V;
+      slot[30] = d30;
+      slot[31] = d31;
+    }
+  };
   if constexpr (cf)
   {
     // ---- close first, continued: edges and unions around the pure-far bricks (list entry k <-> thread k from F-b on).
@@ -2040,20 +2034,8 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     const uint32_t n_pf = s_npf;
     auto tainted = [&](uint32_t k) -> bool { return ((*reinterpret_cast<volatile uint32_t*>(&s_taint[k >> 5]) >> (k & 31u)) & 1u) != 0u; };
     auto join = [&](uint32_t ka, uint32_t kb) {
-      uint32_t ra = lb_find(s_pfpar, ka), rb = lb_find(s_pfpar, kb);
-      while (ra != rb)  // hook the larger root under the smaller
-      {
-        if (ra < rb)
-        {
-          const uint32_t tmp = ra;
-          ra = rb;
-          rb = tmp;
-        }
-        const uint32_t old = lb_cas16(s_pfpar, ra, ra, rb);
-        if (old == ra)
-          break;
-        ra = old;
-      }
+      const uint32_t ra = lb_find(s_pfpar, ka), rb = lb_find(s_pfpar, kb);
+      lb_link(s_pfpar, ra, rb);
     };
     constexpr uint32_t CF_OPEN_UNION = 1u << 23;  // open pair: k | t2 << 10 | kind
     // (row, direction) combinations and their slots: 32 descriptors in LDS, and the lists of those that have adjacent / far slots
@@ -2069,14 +2051,8 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       uint32_t slots_near = valid & near, slots_far = valid & ~near;
       if (back)
       {
-        uint32_t rn = 0, rf = 0;  // the neighbour is the pair's base brick: it sees this brick at (-dx, ddy, ddz), i.e. slot 2R - s
-        for (int sl = 0; sl <= 2 * R; sl++)
-        {
-          rn |= ((slots_near >> (2 * R - sl)) & 1u) << sl;
-          rf |= ((slots_far >> (2 * R - sl)) & 1u) << sl;
-        }
-        slots_near = rn;
-        slots_far = rf;
+        slots_near = fr_reverse_slots(slots_near, R);
+        slots_far = fr_reverse_slots(slots_far, R);
         ddy = -ddy;
         ddz = -ddz;
       }
@@ -2154,11 +2130,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     {
       // more open pairs than the scratch list holds (a tiny workspace: the list has five words per voxel slot): nothing may
       // be dropped - the batch takes the full clustering
-      if (tid == 0)
-      {
-        h.status = CF_RETRY_STATUS;
-        h.V = 0;
-      }
+      fail(CF_RETRY_STATUS);
       return;
     }
     {
@@ -2368,17 +2340,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     }
     FR_STAMP(12);
     FR_STAMP(13);
-    if (prof && tid == 0)
-    {
-      prof[static_cast<size_t>(FRAME) * 32 + 24] = n_pf;
-      prof[static_cast<size_t>(FRAME) * 32 + 25] = s_nc + s_no2;
-      prof[static_cast<size_t>(FRAME) * 32 + 26] = n;
-      prof[static_cast<size_t>(FRAME) * 32 + 27] = n_keys;
-      prof[static_cast<size_t>(FRAME) * 32 + 28] |= min(s_ne, 0xffffffu);  // (pass 3b left the lean count's figures in the upper bits)
-      prof[static_cast<size_t>(FRAME) * 32 + 29] = V;
-      prof[static_cast<size_t>(FRAME) * 32 + 30] = s_ncand;
-      prof[static_cast<size_t>(FRAME) * 32 + 31] = ~0ull;  // (marks a close-first frame for print_prof)
-    }
+    diag(n_pf, s_nc + s_no2, s_ncand, ~0ull);  // (slot 31 all ones: marks a close-first frame for print_prof)
     return;
   }
   {
@@ -2470,21 +2432,6 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   __syncthreads();
   const uint32_t nh_axis = s_nhn >> 17, nh_near = s_nhn & 0x1ffffu;
   FR_STAMP(8);
-  auto link = [&](uint32_t ra, uint32_t rb) {  // hook the larger root under the smaller (labels: smallest member)
-    while (ra != rb)
-    {
-      if (ra < rb)
-      {
-        const uint32_t tmp = ra;
-        ra = rb;
-        rb = tmp;
-      }
-      const uint32_t old = lb_cas16(s_par, ra, ra, rb);
-      if (old == ra)
-        break;
-      ra = old;
-    }
-  };
   auto flatten = [&]() {
     uint32_t roots[LB_MAX / FR_THREADS];
 #pragma unroll
@@ -2545,17 +2492,9 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
 #pragma unroll
       for (int u = 0; u < HU; u++)
       {
-        const unsigned long long m = __ballot(kind[u] == 2u);
-        if (m)
-        {
-          const int leader = __ffsll(static_cast<long long>(m)) - 1;
-          uint32_t base = 0;
-          if (lane == leader)
-            base = atomicAdd(&s_no, static_cast<uint32_t>(__popcll(m)));
-          base = __builtin_amdgcn_readlane(base, leader);
-          if (kind[u] == 2u)
-            opens[base + __popcll(m & ((1ull << lane) - 1ull))] = hv[u];
-        }
+        const uint32_t pos = wave_append(&s_no, kind[u] == 2u, lane);
+        if (kind[u] == 2u)
+          opens[pos] = hv[u];
       }
       uint32_t cur_t = 0xffffffffu, cur_root = 0;
 #pragma unroll
@@ -2570,7 +2509,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
         if (ra == rb)
           continue;
         cur_root = min(ra, rb);
-        link(ra, rb);
+        lb_link(s_par, ra, rb);
       }
     }
   };
@@ -2608,17 +2547,9 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     for (uint32_t i = tid; i < n_r; i += FR_THREADS)
     {
       const bool out = i < n && lb_ld16(s_par, i) != G;
-      const unsigned long long m = __ballot(out);
-      if (m)
-      {
-        const int leader = __ffsll(static_cast<long long>(m)) - 1;
-        uint32_t base = 0;
-        if (lane == leader)
-          base = atomicAdd(&s_nn, static_cast<uint32_t>(__popcll(m)));
-        base = __builtin_amdgcn_readlane(base, leader);
-        if (out)
-          small[base + __popcll(m & ((1ull << lane) - 1ull))] = i;
-      }
+      const uint32_t pos = wave_append(&s_nn, out, lane);
+      if (out)
+        small[pos] = i;
     }
   }
   __syncthreads();
@@ -2634,13 +2565,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
     load_row(row, ddy, ddz, valid, axis, near, ov);
     uint32_t far = valid & ~near;  // slots of the half stencil two bricks away (forward view)
     if (back)
-    {
-      // the neighbour is the pair's base brick: it sees this brick at (-dx, ddy, ddz), i.e. slot 2R - s
-      uint32_t rev = 0;
-      for (int sl = 0; sl <= 2 * R; sl++)
-        rev |= ((far >> (2 * R - sl)) & 1u) << sl;
-      far = rev;
-    }
+      far = fr_reverse_slots(far, R);
     static_assert(FR_THREADS % 32 == 0, "items of a thread share row and direction");
     if (far)
       for (uint32_t it = tid; it < items; it += FR_THREADS)
@@ -2672,11 +2597,7 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   const uint32_t nh_far = s_nf;
   if (nh_far > cap_far)
   {
-    if (tid == 0)
-    {
-      h.status = CCL_RETRY_STATUS;
-      h.V = 0;
-    }
+    fail(CCL_RETRY_STATUS);
     return;
   }
   hits_pass(hits_far, nh_far);
@@ -2697,17 +2618,9 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       bool keep = false;
       if (hv != 0xffffffffu)
         keep = lb_ld16(s_par, hv & 8191u) != lb_ld16(s_par, (hv >> 13) & 8191u);
-      const unsigned long long m = __ballot(keep);
-      if (m)
-      {
-        const int leader = __ffsll(static_cast<long long>(m)) - 1;
-        uint32_t base = 0;
-        if (lane == leader)
-          base = atomicAdd(&s_nh, static_cast<uint32_t>(__popcll(m)));
-        base = __builtin_amdgcn_readlane(base, leader);
-        if (keep)
-          hits[base + __popcll(m & ((1ull << lane) - 1ull))] = hv;  // the hit list is dead: it holds the survivors
-      }
+      const uint32_t pos = wave_append(&s_nh, keep, lane);
+      if (keep)
+        hits[pos] = hv;  // the hit list is dead: it holds the survivors
     }
   }
   __syncthreads();
@@ -2727,21 +2640,11 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       continue;
     ra = lb_find(s_par, ra);
     rb = lb_find(s_par, rb);
-    link(ra, rb);
+    lb_link(s_par, ra, rb);
   }
   __syncthreads();
   FR_STAMP(11);
-  if (prof && tid == 0)
-  {
-    prof[static_cast<size_t>(FRAME) * 32 + 24] = nh;
-    prof[static_cast<size_t>(FRAME) * 32 + 25] = no;
-    prof[static_cast<size_t>(FRAME) * 32 + 26] = n;
-    prof[static_cast<size_t>(FRAME) * 32 + 27] = n_keys;
-    prof[static_cast<size_t>(FRAME) * 32 + 28] = s_ne;
-    prof[static_cast<size_t>(FRAME) * 32 + 29] = V;
-    prof[static_cast<size_t>(FRAME) * 32 + 30] = n_surv;
-    prof[static_cast<size_t>(FRAME) * 32 + 31] = n_small | (static_cast<unsigned long long>(nh_far) << 32);
-  }
+  diag(nh, no, n_surv, n_small | (static_cast<unsigned long long>(nh_far) << 32));
   // ---- E: component minima: the smallest voxel rank of a component is the first voxel of one of its bricks
   uint32_t my_root[LB_MAX / FR_THREADS], my_min[LB_MAX / FR_THREADS];
   unsigned long long my_w[LB_MAX / FR_THREADS];
@@ -2792,17 +2695,9 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
   for (int r = 0; r < LB_MAX / FR_THREADS; r++)
   {
     const bool is_root = my_root[r] == static_cast<uint32_t>(r * FR_THREADS + tid);
-    const unsigned long long m = __ballot(is_root);
-    if (!m)
-      continue;
-    const int leader = __ffsll(static_cast<long long>(m)) - 1;
-    uint32_t base = 0;
-    if (lane == leader)
-      base = atomicAdd(&s_nh, static_cast<uint32_t>(__popcll(m)));
-    base = __builtin_amdgcn_readlane(base, leader);
+    const uint32_t c = wave_append(&s_nh, is_root, lane);
     if (is_root)
     {
-      const uint32_t c = base + __popcll(m & ((1ull << lane) - 1ull));
       const uint32_t label = s_cmin[my_root[r]];
       s_cidx[my_root[r]] = static_cast<uint16_t>(min(c, static_cast<uint32_t>(LB_ST_ROWS)));
       if (c < LB_ST_ROWS)
@@ -3052,21 +2947,13 @@ __global__ FR_VGPR_ATTR __launch_bounds__(FR_THREADS) void k_frame_lds(const Gri
       }
       if (write_tables)
       {
-        const unsigned long long m = __ballot(cand);
-        if (m)
+        const uint32_t pos = wave_append(&h.n_cand, cand, lane);
+        if (cand)
         {
-          const int leader = __ffsll(static_cast<long long>(m)) - 1;
-          uint32_t base = 0;
-          if (lane == leader)
-            base = atomicAdd(&h.n_cand, static_cast<uint32_t>(__popcll(m)));
-          base = __builtin_amdgcn_readlane(base, leader);
-          if (cand)
-          {
-            CandMember cm;
-            cm.root = label;
-            cm.v = v;
-            cands[base + __popcll(m & ((1ull << lane) - 1ull))] = cm;
-          }
+          CandMember cm;
+          cm.root = label;
+          cm.v = v;
+          cands[pos] = cm;
         }
       }
     }
