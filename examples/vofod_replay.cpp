@@ -74,7 +74,7 @@ struct Cloud
 
 int main(int argc, char** argv)
 {
-  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0, render = 0, agree = 0;
+  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0, render = 0, agree = 0, match = 0;
   float voxel = 0.5f;
   std::string apriori;
   for (int i = 1; i + 1 < argc; i += 2)
@@ -100,6 +100,8 @@ int main(int argc, char** argv)
       render = std::atoi(argv[i + 1]);
     else if (k == "--agree")  // 1: before each scan's update, the scan against the map as it stands (vofod_map_render_scans): the counts of the seven verdicts
       agree = std::atoi(argv[i + 1]);
+    else if (k == "--match")  // 1: before each scan's update, a 5 x 5 x 1 lattice of poses one voxel apart with 3 yaws around the scan's pose, scored against the map (vofod_map_match)
+      match = std::atoi(argv[i + 1]);
   }
   const float vfov = 45.0f * 3.14159265f / 180.0f;
   vofod_static_params sp;
@@ -223,6 +225,23 @@ int main(int argc, char** argv)
                     counts[VOFOD_VERDICT_EMPTY], counts[VOFOD_VERDICT_NEARER], counts[VOFOD_VERDICT_THROUGH], counts[VOFOD_VERDICT_MISSING], counts[VOFOD_VERDICT_BEYOND]);
       else
         std::fprintf(stderr, "map_render_scans: %s\n", vofod_last_error_string(h));
+    }
+    if (match)
+    {
+      // where do this scan's returns land under 75 poses around the one it came with - asked BEFORE the scan updates the map.  The
+      // centre of the lattice (candidate 37) is the scan's own pose: best == 37 says that no neighbour explains the scan better.
+      const float step[3] = {voxel, voxel, voxel};
+      const int32_t cnt[3] = {5, 5, 1};
+      float tfs[75 * 12];
+      uint32_t counts[75 * 4];
+      int32_t best = -1;
+      if (vofod_pose_lattice(c->tf, step, cnt, 0.01f, 3, tfs) == VOFOD_OK &&
+          vofod_map_match(h, &scan, tfs, 75, static_cast<float>(dp.voxel_map__thresholds__new_obstacles), counts, &best) == VOFOD_OK)
+        std::printf("scan %3d matched under 75 poses: best %d (%u occupied, %u free, %u outside), the scan's own pose %u occupied; %u pixels skipped\n", k, best,
+                    counts[4 * best + VOFOD_MATCH_OCCUPIED], counts[4 * best + VOFOD_MATCH_FREE], counts[4 * best + VOFOD_MATCH_OUTSIDE], counts[4 * 37 + VOFOD_MATCH_OCCUPIED],
+                    counts[VOFOD_MATCH_SKIPPED]);
+      else
+        std::fprintf(stderr, "map_match: %s\n", vofod_last_error_string(h));
     }
     vofod_detection dets[64];
     size_t n_det = 0;

@@ -559,6 +559,16 @@ int vofod_raycast_units(vofod_handle* h, uint32_t* units, size_t n, int32_t* log
  * VOFOD_ERR_INVALID_ARG. */
 int vofod_column_poses(const float tf_begin[12], const float tf_end[12], const float tf_ref[12],
                        const double* frac /* n, NULL = m / (n - 1) */, int32_t n, float* col_tfs);
+/* Host helper (no handle, no device): a lattice of candidate poses around `tf` for vofod_map_match.  Candidate
+ *     k = ((iyaw * n[2] + iz) * n[1] + iy) * n[0] + ix,       i_a in [0, n[a]), iyaw in [0, n_yaw)
+ * with d[a] = (i_a - (n[a] - 1) / 2.0) * step[a] and psi = (iyaw - (n_yaw - 1) / 2.0) * yaw_step (radians) is [R_k | t_k]:
+ *     t_k = t + d;      rows of R_k:  cos(psi) R0 - sin(psi) R1,   sin(psi) R0 + cos(psi) R1,   R2
+ * - a shift along the world's axes and a yaw about the vertical through the sensor's own origin.  Evaluated in double, each entry
+ * rounded to float once; the centre candidate of odd counts is `tf` itself.  tfs_out holds n[0] * n[1] * n[2] * n_yaw poses of 12
+ * floats.  VOFOD_ERR_INVALID_ARG, with nothing written: a NULL pointer, any count below 1, a product of the counts above 65535, a
+ * step or yaw_step that is not finite. */
+int vofod_pose_lattice(const float tf[12], const float step[3], const int32_t n[3], float yaw_step, int32_t n_yaw,
+                       float* tfs_out /* n[0]*n[1]*n[2]*n_yaw * 12 */);
 
 /* ------------------------------------------------- member voxels and AABB of the detections (product library only)
  *
@@ -870,6 +880,58 @@ int vofod_map_render_scans(vofod_handle* h, const vofod_scan* scans, const float
                            uint8_t* verdict /* n_scans * w * h, nullable, out_memspace */,
                            uint32_t* counts /* n_scans * 8, nullable, ALWAYS host */,
                            int32_t out_memspace);
+
+/* ------------------------------------------------- MAP MATCH (product library only)
+ *
+ * MAP MATCH.  Candidate poses scored against the map: where do this scan's returns land under pose k?  One map look-up per return
+ * and candidate - not a ray walk - for up to 65535 candidates of one scan in one call: the tool a caller needs when the counts of
+ * SCANS AGAINST THE MAP say that the pose has drifted.  Answered on the device (k_match_bits, k_match_points, k_match_score,
+ * vofod_amd/csrc/map_match.h); the CPU oracle does not have it.  Every operation is IEEE float32, rounded once, nothing fused.
+ *
+ * The scan's point.  For pixel i = row * width + col, p is
+ *     range image (x == y == z == NULL, range given)   the p of RANGE IMAGES
+ *     range image with col_tfs                         the p of MOTION COMPENSATION, with the handle's column shifts and that
+ *                                                      section's NaN rule for q inside the exclude box
+ *     point scan (x, y, z given, no col_tfs)           p = (x[i], y[i], z[i]) as given; range and intensity are not read
+ *
+ * SKIPPED.  A pixel is SKIPPED when any of these holds, and live otherwise; it does not depend on the candidate:
+ *     range[i] == 0 on a range image;  all three coordinates zero, of either sign, on a point scan;
+ *     any p[a] is not finite;
+ *     lo[a] <= p[a] <= hi[a] on all three axes - the closed exclude box as the first crop uses it (vofod_nodelet.cpp:626-629).
+ *
+ * Candidate k.  [R | t] = tfs[12k .. 12k + 12) row-major, and for a live pixel
+ *     w[a] = R[a][0]*p[0] + (R[a][1]*p[1] + (R[a][2]*p[2] + t[a]))         (PCL's association, the pipeline's own transform)
+ *     f[a] = floorf((w[a] - off[a]) * (1.0f / vs))                          (the voxel coordinate, before any conversion)
+ * with off the map's origin, vs the voxel size and size the map's size in voxels.
+ *
+ * Class of a live pixel.  OUTSIDE unless f[a] >= 0.0f && f[a] < (float) size[a] on all three axes - compared as floats before the
+ * conversion, so a NaN or infinite w is OUTSIDE and no out-of-range float is ever converted.  Inside, with (x, y, z) = (int) f and
+ * v = (z * sy + y) * sx + x: OCCUPIED when map[v] > threshold, FREE otherwise - the float compare of MAP RENDER: a NaN voxel is
+ * FREE, a +inf voxel is OCCUPIED, a voxel equal to the threshold is FREE.  The map is VOFOD_MAP_VOXELS as it stands when the call
+ * is serialised.
+ *
+ * Outputs.  counts[4k + c] is the number of pixels of class c under candidate k (host memory); the four slots of a candidate sum to
+ * width * height, and slot 0 (SKIPPED) is the same for every k.  Integers: exact, whatever the order they were counted in.
+ * *best (nullable) is the smallest k with the largest counts[4k + 3].
+ *
+ * Refusals, decided before the lock, with nothing written.  VOFOD_ERR_INVALID_ARG: h, scan, tfs or counts NULL; n_poses == 0 or
+ * above 65535; a NaN threshold; an unknown memspace; exactly one or two of x, y, z NULL; all three NULL without range; a point scan
+ * that carries col_tfs (whatever vofod_set_point_motion says); a device-resident column or range whose base or stride is no
+ * multiple of 4; a device-resident col_tfs that is not 4-byte aligned.  VOFOD_ERR_SIZE_MISMATCH: the scan's width or height is not
+ * the handle's.  There is no SENSOR_OUTSIDE_MAP rule: a candidate may lie anywhere, and its points are then OUTSIDE.
+ * VOFOD_ERR_DEVICE as everywhere.
+ *
+ * Admission is MAP RENDER's: the call reads the voxel map only, stages host inputs in a workspace of its own, runs on the handle's
+ * stream, returns after one synchronisation, is admitted beside tickets in flight and beside a pending raycast (float or exact) or
+ * sepclusters pass, and changes nothing another call can observe.  World store: the window is matched.  What the score says: how
+ * many returns fall into voxels the map holds occupied - a correlation, high where the scan's surfaces lie on the map's.  What it
+ * does not say: a likelihood, or anything about free space the rays crossed (SCANS AGAINST THE MAP answers that).  Out of scope: a
+ * NEAR class, several scans per call, a search loop (the caller owns coarse-to-fine; vofod_pose_lattice builds the candidates),
+ * matching through the world store's tiles. */
+enum { VOFOD_MATCH_SKIPPED = 0, VOFOD_MATCH_OUTSIDE = 1, VOFOD_MATCH_FREE = 2, VOFOD_MATCH_OCCUPIED = 3 };
+int vofod_map_match(vofod_handle* h, const vofod_scan* scan,
+                    const float* tfs /* n_poses * 12, host */, size_t n_poses, float threshold,
+                    uint32_t* counts /* n_poses * 4, host */, int32_t* best /* one value, host, nullable */);
 
 /* ------------------------------------------------- WORLD STORE (product library only)
  *

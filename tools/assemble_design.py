@@ -121,6 +121,10 @@ for name, prefix in (("R27_MEASURED", "measured: "), ("R27_RESOURCES", "resource
 r30 = (P / "r30_map_render_scans.txt").read_text().splitlines()
 for name, prefix in (("R30_MEASURED", "measured: "), ("R30_RESOURCES", "resources: "), ("R30_BENCH", "bench: "), ("R30_MUTATIONS", "mutations: ")):
     sub[name] = next(l for l in r30 if l.startswith(prefix)).removeprefix(prefix)
+# §5.21: the same four lines of profiles/r31_map_match.txt
+r31 = (P / "r31_map_match.txt").read_text().splitlines()
+for name, prefix in (("R31_MEASURED", "measured: "), ("R31_RESOURCES", "resources: "), ("R31_BENCH", "bench: "), ("R31_MUTATIONS", "mutations: ")):
+    sub[name] = next(l for l in r31 if l.startswith(prefix)).removeprefix(prefix)
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

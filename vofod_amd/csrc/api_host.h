@@ -395,6 +395,45 @@ int vofod_column_poses(const float tf_begin[12], const float tf_end[12], const f
   return VOFOD_OK;
 }
 
+// ---- vofod_pose_lattice: host only, double throughout, each entry rounded to float once
+int vofod_pose_lattice(const float tf[12], const float step[3], const int32_t n[3], float yaw_step, int32_t n_yaw, float* tfs_out)
+{
+  if (!tf || !step || !n || !tfs_out || n_yaw < 1 || !std::isfinite(yaw_step))
+    return VOFOD_ERR_INVALID_ARG;
+  uint64_t total = static_cast<uint64_t>(n_yaw);
+  for (int a = 0; a < 3; a++)
+  {
+    if (n[a] < 1 || !std::isfinite(step[a]))
+      return VOFOD_ERR_INVALID_ARG;
+    total *= static_cast<uint64_t>(n[a]);  // (four factors below 2^31, checked after each: no overflow of 64 bits)
+    if (total > 65535)
+      return VOFOD_ERR_INVALID_ARG;
+  }
+  if (total > 65535)
+    return VOFOD_ERR_INVALID_ARG;
+  float* out = tfs_out;
+  for (int32_t iyaw = 0; iyaw < n_yaw; iyaw++)
+  {
+    const double psi = (iyaw - (n_yaw - 1) / 2.0) * static_cast<double>(yaw_step);
+    const double c = std::cos(psi), s = std::sin(psi);
+    for (int32_t iz = 0; iz < n[2]; iz++)
+      for (int32_t iy = 0; iy < n[1]; iy++)
+        for (int32_t ix = 0; ix < n[0]; ix++, out += 12)
+        {
+          const int32_t i[3] = {ix, iy, iz};
+          for (int j = 0; j < 3; j++)
+          {
+            out[j] = static_cast<float>(c * static_cast<double>(tf[j]) - s * static_cast<double>(tf[4 + j]));
+            out[4 + j] = static_cast<float>(s * static_cast<double>(tf[j]) + c * static_cast<double>(tf[4 + j]));
+            out[8 + j] = tf[8 + j];
+          }
+          for (int a = 0; a < 3; a++)
+            out[4 * a + 3] = static_cast<float>(static_cast<double>(tf[4 * a + 3]) + (i[a] - (n[a] - 1) / 2.0) * static_cast<double>(step[a]));
+        }
+  }
+  return VOFOD_OK;
+}
+
 // ---- row N3: the nodelet's outgoing messages in the ROS 1 wire format (little endian, strings and arrays prefixed with a
 // uint32 length; std_msgs/Header = seq, stamp.sec, stamp.nsec, frame_id).  A ROS-free host (examples/vofod_replay.cpp)
 // writes exactly the bytes a subscriber of the reference's topics receives.

@@ -183,6 +183,33 @@ static void check_column_poses()
   CHECK(vofod_column_poses(ident, end, nullptr, nullptr, 2, two.get()) == VOFOD_ERR_INVALID_ARG);
 }
 
+static void check_pose_lattice()
+{
+  float tf[12];
+  pose_z(0.3, 1, 2, 3, tf);
+  const float step[3] = {0.25f, 0.5f, 1.0f};
+  // an exact allocation of 3 * 3 * 1 * 3 poses: x fastest, the yaw slowest, the centre candidate is tf itself
+  const int32_t n[3] = {3, 3, 1};
+  auto out = exact<float>(27 * 12);
+  CHECK(vofod_pose_lattice(tf, step, n, 0.1f, 3, out.get()) == VOFOD_OK);
+  for (int k = 0; k < 12; k++)
+    CHECK(out[13 * 12 + k] == tf[k]);
+  CHECK(near(out[3], 0.75, 1e-6) && near(out[12 + 3], 1.0, 1e-6) && near(out[7], 1.5, 1e-6) && near(out[3 * 12 + 7], 2.0, 1e-6) && out[11] == 3.0f);
+  CHECK(near(out[0], std::cos(0.3 - 0.1), 1e-6) && near(out[4], std::sin(0.3 - 0.1), 1e-6) && near(out[26 * 12], std::cos(0.3 + 0.1), 1e-6));
+  CHECK(out[9 * 12 + 3] == out[3] && out[18 * 12 + 7] == out[7]);  // (the yaw turns about the sensor's own origin: t stays)
+  // refusals: a count below 1, a product above 65 535 (also one that would overflow 32 bits), a step that is not finite, a NULL
+  const int32_t zero[3] = {3, 0, 1}, many[3] = {256, 256, 1}, huge[3] = {INT32_MAX, INT32_MAX, INT32_MAX};
+  const float bad[3] = {0.25f, NAN, 1.0f};
+  auto none = exact<float>(1);
+  CHECK(vofod_pose_lattice(tf, step, zero, 0.0f, 1, none.get()) == VOFOD_ERR_INVALID_ARG);
+  CHECK(vofod_pose_lattice(tf, step, many, 0.0f, 1, none.get()) == VOFOD_ERR_INVALID_ARG);
+  CHECK(vofod_pose_lattice(tf, step, huge, 0.0f, INT32_MAX, none.get()) == VOFOD_ERR_INVALID_ARG);
+  CHECK(vofod_pose_lattice(tf, step, n, 0.0f, 0, none.get()) == VOFOD_ERR_INVALID_ARG);
+  CHECK(vofod_pose_lattice(tf, bad, n, 0.0f, 1, none.get()) == VOFOD_ERR_INVALID_ARG);
+  CHECK(vofod_pose_lattice(tf, step, n, INFINITY, 1, none.get()) == VOFOD_ERR_INVALID_ARG);
+  CHECK(vofod_pose_lattice(tf, step, n, 0.0f, 1, nullptr) == VOFOD_ERR_INVALID_ARG);
+}
+
 // a serialiser at every capacity that matters: size query (no buffer), one byte short, exact
 template <class F>
 static std::unique_ptr<uint8_t[]> serialised(size_t want, F&& call)
@@ -272,6 +299,7 @@ int main()
   check_mask_layout();
   check_sensor_params();
   check_column_poses();
+  check_pose_lattice();
   check_serialisers();
   check_load_cloud();
   std::puts("api_host_check: ok");

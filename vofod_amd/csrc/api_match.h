@@ -1,0 +1,151 @@
+// vofod_map_match (included by vofod_hip.hip after api_render.h): the classes of one scan's returns under a list of candidate poses,
+// counted on the device by one map look-up per return and pose.  Contract: include/vofod.h, MAP MATCH; kernels and the account of
+// their three launches: map_match.h.
+#pragma once
+
+namespace
+{
+
+// VOFOD_MATCH_CHUNK=n (diagnostics, tools/map_match_bench.py, and the tests' way to make a small scan straddle chunks): the points per
+// block of k_match_score; unset or anything but a positive number: the one kept
+inline uint32_t match_chunk()
+{
+  if (const char* e = std::getenv("VOFOD_MATCH_CHUNK"))
+  {
+    const long v = std::atol(e);
+    if (v > 0 && v <= 0x7fffffffL)
+      return static_cast<uint32_t>(v);
+  }
+  return vmm::MM_CHUNK;
+}
+
+// VOFOD_MATCH_BURST=1|2|4|8 (diagnostics): the burst lengths measured beside the one kept
+inline int match_burst()
+{
+  if (const char* e = std::getenv("VOFOD_MATCH_BURST"))
+    return std::atoi(e);
+  return vmm::MM_BURST;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vofod_map_match(vofod_handle* h, const vofod_scan* scan, const float* tfs, size_t n_poses, float threshold, uint32_t* counts, int32_t* best)
+{
+  if (!h || !scan || !tfs || !counts || n_poses == 0 || n_poses > vmm::MM_MAX_POSES || std::isnan(threshold))
+    return VOFOD_ERR_INVALID_ARG;
+  const vofod_scan& s = *scan;
+  if (s.memspace != VOFOD_MEM_HOST && s.memspace != VOFOD_MEM_DEVICE)
+    return VOFOD_ERR_INVALID_ARG;
+  const int n_null = !s.x + !s.y + !s.z;
+  if (n_null == 1 || n_null == 2 || (n_null == 3 && !s.range))
+    return VOFOD_ERR_INVALID_ARG;
+  const bool is_range = n_null == 3, dev = s.memspace == VOFOD_MEM_DEVICE;
+  if (!is_range && s.col_tfs)
+    return VOFOD_ERR_INVALID_ARG;  // (whatever vofod_set_point_motion says: the call has no deskew step)
+  if (dev)
+  {
+    const uintptr_t cols = is_range ? reinterpret_cast<uintptr_t>(s.range) : reinterpret_cast<uintptr_t>(s.x) | reinterpret_cast<uintptr_t>(s.y) | reinterpret_cast<uintptr_t>(s.z);
+    if (((cols | s.stride_bytes) & 3) || (reinterpret_cast<uintptr_t>(s.col_tfs) & 3))
+      return VOFOD_ERR_INVALID_ARG;
+  }
+  if (s.height != h->sp.sensor_vrays || s.width != h->sp.sensor_hrays)
+    return VOFOD_ERR_SIZE_MISMATCH;
+  ApiLock lock(h);
+  // as vofod_map_render: the voxel map is read, nothing is written but this call's own workspace (host inputs are staged THERE, not
+  // in a ticket's workspace), so it is admitted with tickets in flight and with a raycast or sepclusters pass pending
+  VCHK(admit(h, NEEDS_NOTHING));
+  const uint32_t width = static_cast<uint32_t>(h->sp.sensor_hrays);
+  const uint32_t n = width * static_cast<uint32_t>(h->sp.sensor_vrays);
+  const uint32_t np = static_cast<uint32_t>(n_poses);
+  vmm::Workspace& w = h->match;
+  const size_t n_words = (h->mg.n + 63) / 64, n_out = vmm::MM_HEAD + 4 * n_poses;
+  HIPCHK(w.d_bits.reserve(n_words));
+  HIPCHK(w.d_points.reserve(n));
+  HIPCHK(w.d_poses.reserve(n_poses * 12));
+  HIPCHK(w.d_out.reserve(n_out));
+  // ---- the scan: device-resident columns and tables are read in place, host-resident ones are gathered and staged
+  vmm::ScanSource src{};
+  src.stride = dev ? s.stride_bytes : 4;
+  src.poses = s.col_tfs;
+  if (is_range && dev)
+    src.range = static_cast<const char*>(s.range);
+  else if (is_range)
+  {
+    HIPCHK(w.d_range.reserve(n));
+    w.h_range.resize(n);
+    for (uint32_t i = 0; i < n; i++)
+      std::memcpy(w.h_range.data() + i, static_cast<const char*>(s.range) + static_cast<size_t>(i) * s.stride_bytes, 4);
+    HIPCHK(hipMemcpyAsync(w.d_range, w.h_range.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    src.range = reinterpret_cast<const char*>(w.d_range.p);
+  }
+  else if (dev)
+    src.x = static_cast<const char*>(s.x), src.y = static_cast<const char*>(s.y), src.z = static_cast<const char*>(s.z);
+  else
+  {
+    HIPCHK(w.d_xyz.reserve(3 * static_cast<size_t>(n)));
+    w.h_xyz.resize(3 * static_cast<size_t>(n));
+    const void* cols[3] = {s.x, s.y, s.z};
+    for (int a = 0; a < 3; a++)
+      for (uint32_t i = 0; i < n; i++)
+        std::memcpy(w.h_xyz.data() + static_cast<size_t>(a) * n + i, static_cast<const char*>(cols[a]) + static_cast<size_t>(i) * s.stride_bytes, 4);
+    HIPCHK(hipMemcpyAsync(w.d_xyz, w.h_xyz.data(), w.h_xyz.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    src.x = reinterpret_cast<const char*>(w.d_xyz.p);
+    src.y = reinterpret_cast<const char*>(w.d_xyz.p + n);
+    src.z = reinterpret_cast<const char*>(w.d_xyz.p + 2 * static_cast<size_t>(n));
+  }
+  if (s.col_tfs && !dev)
+  {
+    HIPCHK(w.d_tab.reserve(12 * static_cast<size_t>(width)));
+    HIPCHK(hipMemcpyAsync(w.d_tab, s.col_tfs, sizeof(float) * 12 * width, hipMemcpyHostToDevice, h->stream));
+    src.poses = w.d_tab.p;
+  }
+  HIPCHK(hipMemcpyAsync(w.d_poses, tfs, n_poses * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(w.d_out, 0, n_out * sizeof(uint32_t), h->stream));  // n_live and every candidate's slots
+  // ---- the occupancy image of this threshold
+  KLAUNCH_AS(h, "k_match_bits", vmm::k_match_bits, dim3(static_cast<uint32_t>((h->mg.n + 255) / 256)), dim3(256), static_cast<const float*>(h->d_map.p), h->mg.n, threshold, w.d_bits.p);
+  HIPCHK(hipGetLastError());
+  // ---- the live list
+  vrd::MotionArgs ma{};
+  ma.shift = h->d_col_shift.p;
+  ma.width = width;
+  exclude_box(h, ma.lo, ma.hi);
+  const bool pose16 = (reinterpret_cast<uintptr_t>(src.poses) & 15) == 0;
+  auto points = !is_range ? vmm::k_match_points<vmm::SRC_POINTS, true>
+                : !src.poses ? vmm::k_match_points<vmm::SRC_RANGE, true>
+                : pose16     ? vmm::k_match_points<vmm::SRC_MOTION, true>
+                             : vmm::k_match_points<vmm::SRC_MOTION, false>;
+  KLAUNCH_AS(h, "k_match_points", points, dim3((n + 255) / 256), dim3(256), src, n, static_cast<const float*>(h->d_lut_dirs.p), static_cast<const float*>(h->d_lut_offs.p), ma, w.d_points.p,
+             w.d_out.p);
+  HIPCHK(hipGetLastError());
+  // ---- the counts: sized for width * height, the blocks beyond n_live leave at once (a chunk below n / 65535 is raised to it: gridDim.y)
+  const uint32_t chunk = std::max(match_chunk(), (n + vmm::MM_MAX_CHUNKS - 1) / vmm::MM_MAX_CHUNKS);
+  const vmm::ScoreParams sp{np, chunk, static_cast<float>(h->mg.sx), static_cast<float>(h->mg.sy), static_cast<float>(h->mg.sz)};
+  const dim3 grid((np + vmm::MM_THREADS - 1) / vmm::MM_THREADS, (n + chunk - 1) / chunk), block(vmm::MM_THREADS);
+  const int burst = match_burst();
+  auto score = burst == 1 ? vmm::k_match_score<1> : burst == 2 ? vmm::k_match_score<2> : burst == 4 ? vmm::k_match_score<4> : burst == 8 ? vmm::k_match_score<8> : vmm::k_match_score<vmm::MM_BURST>;
+  KLAUNCH_AS(h, "k_match_score", score, grid, block, sp, h->mg, reinterpret_cast<const uint32_t*>(w.d_bits.p), static_cast<const float4*>(w.d_points.p), static_cast<const float*>(w.d_poses.p),
+             w.d_out.p);
+  HIPCHK(hipGetLastError());
+  w.h_out.resize(n_out);
+  HIPCHK(hipMemcpyAsync(w.h_out.data(), w.d_out, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // (the call's only one: n_live and the counts arrive with it, and the staged inputs are free)
+  const uint32_t skipped = n - w.h_out[0];
+  uint32_t best_occ = 0;
+  int32_t best_k = 0;
+  for (uint32_t k = 0; k < np; k++)
+  {
+    const uint32_t* c = w.h_out.data() + vmm::MM_HEAD + 4 * static_cast<size_t>(k);
+    counts[4 * static_cast<size_t>(k)] = skipped;  // VOFOD_MATCH_SKIPPED: the same for every candidate
+    for (int a = 1; a < 4; a++)
+      counts[4 * static_cast<size_t>(k) + a] = c[a];
+    if (c[3] > best_occ)
+      best_occ = c[3], best_k = static_cast<int32_t>(k);
+  }
+  if (best)
+    *best = best_k;
+  return VOFOD_OK;
+}
+
+}  // extern "C"

@@ -40,6 +40,7 @@
 #include "detection_pixels.h"
 #include "map_shift.h"
 #include "map_render.h"
+#include "map_match.h"
 #include "world_store.h"
 #include "world_sync.h"
 
@@ -498,6 +499,7 @@ struct vofod_handle
   DevBuf<float> d_map, d_flags, d_ray;
   DevBuf<float> d_shift_spare;  // vofod_map_shift: destination of the out-of-place shift, swapped with the map it received (allocated on the first shift)
   vmr::Workspace render;  // vofod_map_render: pose table and host-output staging, grown to the largest n_views * w * h seen
+  vmm::Workspace match;  // vofod_map_match: the occupancy image of the call's threshold, the live list, pose table and counts, host-input staging
   vws::Store world;  // vofod_world_enable: the voxel map is a window onto it (world_store.h); indexed by world index, so no shift moves it
   vwy::State wsync;  // snapshots / deltas of the store (world_sync.h, world_sync_host.h): shadow pool, scratch and the two chains
   DevBuf<unsigned long long> d_mapbits;
@@ -1534,6 +1536,7 @@ int host_explore_frame(vofod_handle* h, std::vector<HostCluster>& cl, const vt::
 #include "driver_aux.h"
 #include "api_maps.h"
 #include "api_render.h"
+#include "api_match.h"
 #include "api_frames.h"
 #include "collective.h"
 #include "mapsync_host.h"

@@ -236,6 +236,20 @@ class VoFOD:
                                                    capi.ptr(r.what), capi.ptr(r.t_in_out), capi.ptr(r.verdict), capi.ptr(r.counts), capi.MEM_HOST), "vofod_map_render_scans", allow)
         return r if st == capi.OK else st
 
+    def map_match(self, scan: ScanData, tfs, threshold: float, allow: Sequence[int] = ()):
+        """Candidate poses scored against the map (vofod_map_match): `scan` (a range image, with or without `col_tfs`, or a point
+        scan) under every pose of `tfs` ([K, 3, 4] or one [3, 4]).  Returns a namespace of counts (uint32 [K, 4]: the pixels of each
+        capi.MATCH_* class per candidate) and best (the smallest k with the most OCCUPIED pixels).  A status in `allow` is returned in
+        place of the result."""
+        from types import SimpleNamespace
+
+        t = np.ascontiguousarray(tfs, dtype=np.float32).reshape(-1, 12)
+        cs = scan.as_c()
+        counts = np.zeros((t.shape[0], 4), dtype=np.uint32)
+        best = C.c_int32(-1)
+        st = self._check(self.lib.map_match(self.h, C.byref(cs), capi.ptr(t), t.shape[0], float(threshold), capi.ptr(counts), C.byref(best)), "vofod_map_match", allow)
+        return SimpleNamespace(counts=counts, best=int(best.value)) if st == capi.OK else st
+
     # ---- world store (include/vofod.h, WORLD STORE): the voxel map as a window onto a sparse map of a larger box
     def world_enable(self, margin_lo, margin_hi, max_tiles: int, allow: Sequence[int] = ()):
         """The box is [-margin_lo, map_size + margin_hi) in world indices (voxels, the window's origin K = 0 now); the pool holds
@@ -624,6 +638,20 @@ def column_poses(lib, tf_begin, tf_end, tf_ref, n: int, frac=None) -> np.ndarray
     st = lib.column_poses(capi.ptr(a), capi.ptr(b), capi.ptr(r), capi.ptr(fr), n, capi.ptr(out))
     if st != capi.OK:
         raise VofodError(st, "vofod_column_poses")
+    return out
+
+
+def pose_lattice(lib, tf, step, n, yaw_step: float = 0.0, n_yaw: int = 1) -> np.ndarray:
+    """vofod_pose_lattice: [n[0] * n[1] * n[2] * n_yaw, 3, 4] float32 candidate poses around `tf` - shifts of `step` along the world's
+    axes, x fastest, and yaws of `yaw_step` radians about the vertical through the sensor's origin, slowest; what VoFOD.map_match takes"""
+    t = np.ascontiguousarray(tf, dtype=np.float32).reshape(12)
+    s = np.ascontiguousarray(step, dtype=np.float32).reshape(3)
+    c = np.ascontiguousarray(n, dtype=np.int32).reshape(3)
+    total = int(np.prod(np.maximum(c.astype(np.int64), 0))) * max(int(n_yaw), 0)
+    out = np.zeros((min(total, 65535), 3, 4), dtype=np.float32)
+    st = lib.pose_lattice(capi.ptr(t), capi.ptr(s), capi.ptr(c), float(yaw_step), int(n_yaw), capi.ptr(out))
+    if st != capi.OK:
+        raise VofodError(st, "vofod_pose_lattice")
     return out
 
 
