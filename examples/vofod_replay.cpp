@@ -74,7 +74,7 @@ struct Cloud
 
 int main(int argc, char** argv)
 {
-  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0, render = 0, agree = 0, match = 0;
+  int n_scans = 40, rows = 32, cols = 1024, period_ms = 0, extents = 0, pixels = 0, render = 0, agree = 0, match = 0, field = 0;
   float voxel = 0.5f;
   std::string apriori;
   for (int i = 1; i + 1 < argc; i += 2)
@@ -102,6 +102,8 @@ int main(int argc, char** argv)
       agree = std::atoi(argv[i + 1]);
     else if (k == "--match")  // 1: before each scan's update, a 5 x 5 x 1 lattice of poses one voxel apart with 3 yaws around the scan's pose, scored against the map (vofod_map_match)
       match = std::atoi(argv[i + 1]);
+    else if (k == "--field")  // 1: every 10th scan the distance field of the map (vofod_map_distance, radius 8); before each scan's update --match's lattice scored by it (vofod_map_match_field) beside vofod_map_match
+      field = std::atoi(argv[i + 1]);
   }
   const float vfov = 45.0f * 3.14159265f / 180.0f;
   vofod_static_params sp;
@@ -184,6 +186,7 @@ int main(int argc, char** argv)
   float last_tf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 4};
   std::vector<uint8_t> msg_buf;
   const auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint16_t> d2;  // --field: the distance field of the map as it stood at the last scan that is a multiple of ten
   for (int k = 0; k < n_scans; k++)
   {
     auto c = std::make_shared<Cloud>();
@@ -242,6 +245,38 @@ int main(int argc, char** argv)
                     counts[VOFOD_MATCH_SKIPPED]);
       else
         std::fprintf(stderr, "map_match: %s\n", vofod_last_error_string(h));
+    }
+    if (field)
+    {
+      // the same 75 poses scored by the distance to the map's surfaces: a cost with a slope where vofod_map_match's count is a step.
+      // The field is rebuilt every 10th scan - a field a few scans old is what a matcher uses - and kept by the caller.  THIS EXAMPLE HAS NO
+      // HIP OF ITS OWN, so it keeps the field in host memory, and every vofod_map_match_field below copies all of it to the device
+      // again (2 bytes per voxel per scan).  A caller that can hold device memory passes a device buffer with VOFOD_MEM_DEVICE to
+      // both calls: it is then written and read in place, and nothing is copied.
+      const float step[3] = {voxel, voxel, voxel};
+      const int32_t cnt[3] = {5, 5, 1};
+      const float thr = static_cast<float>(dp.voxel_map__thresholds__new_obstacles);
+      float tfs[75 * 12];
+      uint32_t counts[75 * 4], occupied[75 * 4];
+      uint64_t cost[75];
+      int32_t best = -1, best_count = -1;
+      if (d2.empty())
+      {
+        vofod_status_info si;
+        vofod_get_status(h, &si);
+        d2.resize(static_cast<size_t>(si.map_size[0]) * si.map_size[1] * si.map_size[2]);
+      }
+      int st_f = VOFOD_OK;
+      if (k % 10 == 0)
+        st_f = vofod_map_distance(h, thr, 8, d2.data(), d2.size(), VOFOD_MEM_HOST);
+      if (st_f == VOFOD_OK && vofod_pose_lattice(c->tf, step, cnt, 0.01f, 3, tfs) == VOFOD_OK &&
+          vofod_map_match_field(h, &scan, tfs, 75, d2.data(), d2.size(), VOFOD_MEM_HOST, 0, 64, counts, cost, &best) == VOFOD_OK &&
+          vofod_map_match(h, &scan, tfs, 75, thr, occupied, &best_count) == VOFOD_OK)
+        std::printf("scan %3d scored by the field of scan %d under 75 poses: best %d (cost %llu, %u near, %u far, %u outside), the scan's own pose costs %llu; vofod_map_match's best %d\n", k,
+                    k - k % 10, best, static_cast<unsigned long long>(cost[best]), counts[4 * best + VOFOD_FIELD_NEAR], counts[4 * best + VOFOD_FIELD_FAR], counts[4 * best + VOFOD_FIELD_OUTSIDE],
+                    static_cast<unsigned long long>(cost[37]), best_count);
+      else
+        std::fprintf(stderr, "map_distance / map_match_field: %s\n", vofod_last_error_string(h));
     }
     vofod_detection dets[64];
     size_t n_det = 0;

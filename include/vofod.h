@@ -933,6 +933,59 @@ int vofod_map_match(vofod_handle* h, const vofod_scan* scan,
                     const float* tfs /* n_poses * 12, host */, size_t n_poses, float threshold,
                     uint32_t* counts /* n_poses * 4, host */, int32_t* best /* one value, host, nullable */);
 
+/* ------------------------------------------------- MAP DISTANCE (product library only)
+ *
+ * MAP DISTANCE.  The Euclidean distance transform of the voxel map - for every voxel, how far away is the nearest occupied one -
+ * and candidate poses scored by it.  MAP MATCH counts hits, a step function of the pose; the distance gives the score a slope: a
+ * likelihood field for a scan matcher, clearance for a planner, "how far from the background does this detection float" for a
+ * consumer.  Answered on the device (k_match_bits, k_dist_x, k_dist_y, k_dist_z, k_match_points, k_match_field;
+ * vofod_amd/csrc/map_distance.h); the CPU oracle does not have it.  Squared voxel distances are integers: both calls are exact,
+ * whatever the order anything was computed in.
+ *
+ * vofod_map_distance.  A voxel u is occupied when map[u] > threshold - the float compare of MAP MATCH: a NaN voxel is free, a +inf
+ * voxel is occupied, a voxel equal to the threshold is free; an infinite threshold is allowed.  With R = radius and
+ * v = (z * sy + y) * sx + x,
+ *     d2[v] = min(R * R,  min over occupied u of (dx * dx + dy * dy + dz * dz))          (dx, dy, dz: the voxel offsets from v to u)
+ * in voxels, an integer: an occupied voxel holds 0, a map with nothing occupied holds R * R everywhere.  Only voxels inside the box
+ * count, nothing wraps; with the world store on, the window is transformed.  The clamp at R * R is what lets a windowed search be
+ * exact - a true d2 <= R * R has every axis offset <= R - and it is the truncated-quadratic robust cost a matcher wants.
+ * R <= VOFOD_DIST_MAX_RADIUS = 255 keeps R * R <= 65025 within uint16_t.  The map is VOFOD_MAP_VOXELS as it stands when the call
+ * is serialised; d2 holds sx * sy * sz values in `memspace`.
+ * Refusals, decided before the lock, with nothing written.  VOFOD_ERR_INVALID_ARG: h or d2 NULL; a NaN threshold; radius < 1 or
+ * radius > 255; an unknown memspace; a device d2 that is not 2-byte aligned.  VOFOD_ERR_SIZE_MISMATCH: n is not the map's voxel
+ * count.  VOFOD_ERR_DEVICE as everywhere.
+ * Admission is MAP RENDER's: the call reads the voxel map only, keeps a workspace of its own on the handle, runs on the handle's
+ * stream, returns after one synchronisation, is admitted beside tickets in flight and beside a pending raycast (float or exact) or
+ * sepclusters pass, and changes nothing another call can observe.  The work grows with the radius where the map is empty
+ * (O(N * R) at worst; DESIGN.md 5.22 has the times).
+ *
+ * vofod_map_match_field.  The scan's point, SKIPPED, candidate k, the float bounds test and v are MAP MATCH's, word for word (that
+ * section; not restated here).  An inside pixel is NEAR when d2[v] <= near2 and FAR otherwise, and
+ *     cost[k] = (sum of d2[v] over the inside pixels) + outside_cost * OUTSIDE_k                           (64 bits, exact)
+ * counts[4k + c] is the number of pixels of class VOFOD_FIELD_* c under candidate k; the four slots of a candidate sum to
+ * width * height, slot 0 is the same for every k.  *best (nullable) is the smallest k with the smallest cost[k].  The field is an
+ * INPUT: any uint16_t values, sx * sy * sz of them in field_memspace - what vofod_map_distance wrote, or anything else.  The caller
+ * owns how fresh it is (a field a few scans old is what a matcher uses); the call reads d2 and the scan, not the voxel map.  With
+ * near2 = 0 and the field of vofod_map_distance, NEAR is MAP MATCH's OCCUPIED at the same threshold.  counts and cost are host
+ * memory.
+ * Refusals: all of MAP MATCH's but the threshold's, and VOFOD_ERR_INVALID_ARG also for d2 or cost NULL, an unknown field_memspace,
+ * a device d2 that is not 2-byte aligned, outside_cost > 65535; VOFOD_ERR_SIZE_MISMATCH also when n is not the map's voxel count.
+ * near2 is never refused: a value above the field's maximum makes every inside pixel NEAR.  Admission is MAP MATCH's; a host field
+ * is staged in the call's workspace, a device field is read in place.
+ *
+ * Out of scope: a feature transform (the nearest voxel's index: ties make it order-dependent), distances through the world store's
+ * tiles, a field patched incrementally by the map update, sub-voxel interpolation, a search loop, several scans per call. */
+enum { VOFOD_DIST_MAX_RADIUS = 255 };
+int vofod_map_distance(vofod_handle* h, float threshold, int32_t radius,
+                       uint16_t* d2 /* sx*sy*sz, memspace */, size_t n, int32_t memspace);
+enum { VOFOD_FIELD_SKIPPED = 0, VOFOD_FIELD_OUTSIDE = 1, VOFOD_FIELD_FAR = 2, VOFOD_FIELD_NEAR = 3 };
+int vofod_map_match_field(vofod_handle* h, const vofod_scan* scan,
+                          const float* tfs /* n_poses*12, host */, size_t n_poses,
+                          const uint16_t* d2 /* sx*sy*sz */, size_t n, int32_t field_memspace,
+                          uint32_t near2, uint32_t outside_cost,
+                          uint32_t* counts /* n_poses*4, host */, uint64_t* cost /* n_poses, host */,
+                          int32_t* best /* nullable */);
+
 /* ------------------------------------------------- WORLD STORE (product library only)
  *
  * vofod_map_shift alone forgets what leaves the box.  With the world store enabled the handle is a WINDOW onto a map larger than

@@ -125,6 +125,10 @@ for name, prefix in (("R30_MEASURED", "measured: "), ("R30_RESOURCES", "resource
 r31 = (P / "r31_map_match.txt").read_text().splitlines()
 for name, prefix in (("R31_MEASURED", "measured: "), ("R31_RESOURCES", "resources: "), ("R31_BENCH", "bench: "), ("R31_MUTATIONS", "mutations: ")):
     sub[name] = next(l for l in r31 if l.startswith(prefix)).removeprefix(prefix)
+# §5.22: the same four lines of profiles/r32_map_distance.txt
+r32 = (P / "r32_map_distance.txt").read_text().splitlines()
+for name, prefix in (("R32_MEASURED", "measured: "), ("R32_RESOURCES", "resources: "), ("R32_BENCH", "bench: "), ("R32_MUTATIONS", "mutations: ")):
+    sub[name] = next(l for l in r32 if l.startswith(prefix)).removeprefix(prefix)
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

@@ -43,6 +43,8 @@ RENDER_NOT_CAST, RENDER_HIT, RENDER_END, RENDER_LEFT = 0, 1, 2, 3  # vofod_map_r
 RENDER_NO_VOXEL = 0xFFFFFFFF
 VERDICT_NONE, VERDICT_AGREES, VERDICT_EMPTY, VERDICT_NEARER, VERDICT_THROUGH, VERDICT_MISSING, VERDICT_BEYOND = range(7)  # vofod_map_render_scans: `verdict` of a pixel
 MATCH_SKIPPED, MATCH_OUTSIDE, MATCH_FREE, MATCH_OCCUPIED = 0, 1, 2, 3  # vofod_map_match: the class of a pixel under a candidate pose
+FIELD_SKIPPED, FIELD_OUTSIDE, FIELD_FAR, FIELD_NEAR = 0, 1, 2, 3  # vofod_map_match_field: the same, by the distance field
+DIST_MAX_RADIUS = 255  # vofod_map_distance
 
 
 class StaticParams(C.Structure):
@@ -323,6 +325,8 @@ _SIGS = {
     "map_render_scans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "map_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
     "pose_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
+    "map_distance": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32]),
+    "map_match_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "set_column_shift": (C.c_int, [C.c_void_p, C.c_void_p]),
     "column_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "set_raycast_motion": (C.c_int, [C.c_void_p, C.c_int]),
@@ -341,7 +345,7 @@ _SIGS = {
 
 # entry points only the product library has to export (include/vofod.h says so)
 PRODUCT_ONLY = ("comm_unique_id", "comm_create", "comm_destroy", "comm_last_error", "allgather_detections", "detection_slot_bytes", "pack_detection_slots", "unpack_detection_slots", "serialize_detections", "serialize_status",
-                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "detection_pixels", "map_shift", "map_render", "map_render_scans", "map_match", "pose_lattice", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units",
+                "serialize_profiling_info", "map_export", "map_apply", "broadcast_map", "range_to_points", "detection_points", "detection_pixels", "map_shift", "map_render", "map_render_scans", "map_match", "pose_lattice", "map_distance", "map_match_field", "set_column_shift", "column_poses", "set_raycast_motion", "set_raycast_exact", "raycast_units",
                 "set_point_motion", "deskew_points", "world_enable", "world_disable", "world_status", "world_read", "world_export", "world_apply")
 
 

@@ -27,13 +27,11 @@ inline int match_burst()
   return vmm::MM_BURST;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vofod_map_match(vofod_handle* h, const vofod_scan* scan, const float* tfs, size_t n_poses, float threshold, uint32_t* counts, int32_t* best)
+// the refusals that the scan and the candidate list decide (include/vofod.h, MAP MATCH), before the lock: shared by vofod_map_match
+// and vofod_map_match_field (api_distance.h)
+inline int match_refusal(const vofod_handle* h, const vofod_scan* scan, const float* tfs, size_t n_poses, const uint32_t* counts)
 {
-  if (!h || !scan || !tfs || !counts || n_poses == 0 || n_poses > vmm::MM_MAX_POSES || std::isnan(threshold))
+  if (!h || !scan || !tfs || !counts || n_poses == 0 || n_poses > vmm::MM_MAX_POSES)
     return VOFOD_ERR_INVALID_ARG;
   const vofod_scan& s = *scan;
   if (s.memspace != VOFOD_MEM_HOST && s.memspace != VOFOD_MEM_DEVICE)
@@ -52,16 +50,19 @@ int vofod_map_match(vofod_handle* h, const vofod_scan* scan, const float* tfs, s
   }
   if (s.height != h->sp.sensor_vrays || s.width != h->sp.sensor_hrays)
     return VOFOD_ERR_SIZE_MISMATCH;
-  ApiLock lock(h);
-  // as vofod_map_render: the voxel map is read, nothing is written but this call's own workspace (host inputs are staged THERE, not
-  // in a ticket's workspace), so it is admitted with tickets in flight and with a raycast or sepclusters pass pending
-  VCHK(admit(h, NEEDS_NOTHING));
+  return VOFOD_OK;
+}
+
+// the live list of a scan that passed match_refusal, under the lock: device-resident columns and tables are read in place, host-resident
+// ones are gathered and staged in `w`; the candidates go to w.d_poses, n_live and every candidate's slots (w.d_out) are cleared on the
+// stream, and k_match_points fills w.d_points
+inline int match_live_list(vofod_handle* h, vmm::Workspace& w, const vofod_scan& s, const float* tfs, size_t n_poses)
+{
+  const int n_null = !s.x + !s.y + !s.z;
+  const bool is_range = n_null == 3, dev = s.memspace == VOFOD_MEM_DEVICE;
   const uint32_t width = static_cast<uint32_t>(h->sp.sensor_hrays);
   const uint32_t n = width * static_cast<uint32_t>(h->sp.sensor_vrays);
-  const uint32_t np = static_cast<uint32_t>(n_poses);
-  vmm::Workspace& w = h->match;
-  const size_t n_words = (h->mg.n + 63) / 64, n_out = vmm::MM_HEAD + 4 * n_poses;
-  HIPCHK(w.d_bits.reserve(n_words));
+  const size_t n_out = vmm::MM_HEAD + 4 * n_poses;
   HIPCHK(w.d_points.reserve(n));
   HIPCHK(w.d_poses.reserve(n_poses * 12));
   HIPCHK(w.d_out.reserve(n_out));
@@ -103,10 +104,6 @@ int vofod_map_match(vofod_handle* h, const vofod_scan* scan, const float* tfs, s
   }
   HIPCHK(hipMemcpyAsync(w.d_poses, tfs, n_poses * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemsetAsync(w.d_out, 0, n_out * sizeof(uint32_t), h->stream));  // n_live and every candidate's slots
-  // ---- the occupancy image of this threshold
-  KLAUNCH_AS(h, "k_match_bits", vmm::k_match_bits, dim3(static_cast<uint32_t>((h->mg.n + 255) / 256)), dim3(256), static_cast<const float*>(h->d_map.p), h->mg.n, threshold, w.d_bits.p);
-  HIPCHK(hipGetLastError());
-  // ---- the live list
   vrd::MotionArgs ma{};
   ma.shift = h->d_col_shift.p;
   ma.width = width;
@@ -119,6 +116,33 @@ int vofod_map_match(vofod_handle* h, const vofod_scan* scan, const float* tfs, s
   KLAUNCH_AS(h, "k_match_points", points, dim3((n + 255) / 256), dim3(256), src, n, static_cast<const float*>(h->d_lut_dirs.p), static_cast<const float*>(h->d_lut_offs.p), ma, w.d_points.p,
              w.d_out.p);
   HIPCHK(hipGetLastError());
+  return VOFOD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vofod_map_match(vofod_handle* h, const vofod_scan* scan, const float* tfs, size_t n_poses, float threshold, uint32_t* counts, int32_t* best)
+{
+  if (std::isnan(threshold))
+    return VOFOD_ERR_INVALID_ARG;
+  VCHK(match_refusal(h, scan, tfs, n_poses, counts));
+  const vofod_scan& s = *scan;
+  ApiLock lock(h);
+  // as vofod_map_render: the voxel map is read, nothing is written but this call's own workspace (host inputs are staged THERE, not
+  // in a ticket's workspace), so it is admitted with tickets in flight and with a raycast or sepclusters pass pending
+  VCHK(admit(h, NEEDS_NOTHING));
+  const uint32_t n = static_cast<uint32_t>(h->sp.sensor_hrays) * static_cast<uint32_t>(h->sp.sensor_vrays);
+  const uint32_t np = static_cast<uint32_t>(n_poses);
+  vmm::Workspace& w = h->match;
+  const size_t n_words = (h->mg.n + 63) / 64, n_out = vmm::MM_HEAD + 4 * n_poses;
+  HIPCHK(w.d_bits.reserve(n_words));
+  // ---- the occupancy image of this threshold
+  KLAUNCH_AS(h, "k_match_bits", vmm::k_match_bits, dim3(static_cast<uint32_t>((h->mg.n + 255) / 256)), dim3(256), static_cast<const float*>(h->d_map.p), h->mg.n, threshold, w.d_bits.p);
+  HIPCHK(hipGetLastError());
+  // ---- the live list
+  VCHK(match_live_list(h, w, s, tfs, n_poses));
   // ---- the counts: sized for width * height, the blocks beyond n_live leave at once (a chunk below n / 65535 is raised to it: gridDim.y)
   const uint32_t chunk = std::max(match_chunk(), (n + vmm::MM_MAX_CHUNKS - 1) / vmm::MM_MAX_CHUNKS);
   const vmm::ScoreParams sp{np, chunk, static_cast<float>(h->mg.sx), static_cast<float>(h->mg.sy), static_cast<float>(h->mg.sz)};

@@ -41,6 +41,7 @@
 #include "map_shift.h"
 #include "map_render.h"
 #include "map_match.h"
+#include "map_distance.h"
 #include "world_store.h"
 #include "world_sync.h"
 
@@ -500,6 +501,7 @@ struct vofod_handle
   DevBuf<float> d_shift_spare;  // vofod_map_shift: destination of the out-of-place shift, swapped with the map it received (allocated on the first shift)
   vmr::Workspace render;  // vofod_map_render: pose table and host-output staging, grown to the largest n_views * w * h seen
   vmm::Workspace match;  // vofod_map_match: the occupancy image of the call's threshold, the live list, pose table and counts, host-input staging
+  vmd::Workspace dist;  // vofod_map_distance: its occupancy image and the passes' two fields; vofod_map_match_field: a host field's staging, the sums
   vws::Store world;  // vofod_world_enable: the voxel map is a window onto it (world_store.h); indexed by world index, so no shift moves it
   vwy::State wsync;  // snapshots / deltas of the store (world_sync.h, world_sync_host.h): shadow pool, scratch and the two chains
   DevBuf<unsigned long long> d_mapbits;
@@ -1537,6 +1539,7 @@ int host_explore_frame(vofod_handle* h, std::vector<HostCluster>& cl, const vt::
 #include "api_maps.h"
 #include "api_render.h"
 #include "api_match.h"
+#include "api_distance.h"
 #include "api_frames.h"
 #include "collective.h"
 #include "mapsync_host.h"

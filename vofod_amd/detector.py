@@ -250,6 +250,40 @@ class VoFOD:
         st = self._check(self.lib.map_match(self.h, C.byref(cs), capi.ptr(t), t.shape[0], float(threshold), capi.ptr(counts), C.byref(best)), "vofod_map_match", allow)
         return SimpleNamespace(counts=counts, best=int(best.value)) if st == capi.OK else st
 
+    def map_distance(self, threshold: float, radius: int, device=False, allow: Sequence[int] = ()):
+        """The squared distance, in voxels, from every voxel to the nearest one above `threshold`, clamped at radius * radius
+        (vofod_map_distance): uint16 [sz, sy, sx].  `device` = a device address on the handle's device (2-byte aligned, n_voxels
+        uint16): the field is written in place and None comes back.  A status in `allow` is returned in place of the result."""
+        if device is not False and device is not None:
+            st = self._check(self.lib.map_distance(self.h, float(threshold), int(radius), C.c_void_p(int(device)), self.n_voxels, capi.MEM_DEVICE), "vofod_map_distance", allow)
+            return None if st == capi.OK else st
+        out = np.zeros(self.n_voxels, dtype=np.uint16)
+        st = self._check(self.lib.map_distance(self.h, float(threshold), int(radius), capi.ptr(out), out.size, capi.MEM_HOST), "vofod_map_distance", allow)
+        sx, sy, sz = self.map_size
+        return out.reshape(sz, sy, sx) if st == capi.OK else st
+
+    def map_match_field(self, scan: ScanData, tfs, d2, near2: int = 0, outside_cost: int = 0, allow: Sequence[int] = ()):
+        """Candidate poses scored by a distance field (vofod_map_match_field): `scan` and `tfs` as for map_match; `d2` is a uint16
+        array of n_voxels values (what map_distance returned, or any other field) or a device address of one.  Returns a namespace
+        of counts (uint32 [K, 4]: the pixels of each capi.FIELD_* class per candidate), cost (uint64 [K]: the sum of d2 over the
+        inside pixels plus outside_cost per OUTSIDE pixel) and best (the smallest k with the smallest cost).  A status in `allow` is
+        returned in place of the result."""
+        from types import SimpleNamespace
+
+        t = np.ascontiguousarray(tfs, dtype=np.float32).reshape(-1, 12)
+        cs = scan.as_c()
+        counts = np.zeros((t.shape[0], 4), dtype=np.uint32)
+        cost = np.zeros(t.shape[0], dtype=np.uint64)
+        best = C.c_int32(-1)
+        if isinstance(d2, np.ndarray):
+            field = np.ascontiguousarray(d2, dtype=np.uint16).reshape(-1)
+            f_ptr, f_n, f_mem = capi.ptr(field), field.size, capi.MEM_HOST
+        else:
+            f_ptr, f_n, f_mem = C.c_void_p(int(d2)), self.n_voxels, capi.MEM_DEVICE
+        st = self._check(self.lib.map_match_field(self.h, C.byref(cs), capi.ptr(t), t.shape[0], f_ptr, f_n, f_mem, int(near2), int(outside_cost), capi.ptr(counts), capi.ptr(cost),
+                                                  C.byref(best)), "vofod_map_match_field", allow)
+        return SimpleNamespace(counts=counts, cost=cost, best=int(best.value)) if st == capi.OK else st
+
     # ---- world store (include/vofod.h, WORLD STORE): the voxel map as a window onto a sparse map of a larger box
     def world_enable(self, margin_lo, margin_hi, max_tiles: int, allow: Sequence[int] = ()):
         """The box is [-margin_lo, map_size + margin_hi) in world indices (voxels, the window's origin K = 0 now); the pool holds
