@@ -129,6 +129,10 @@ for name, prefix in (("R31_MEASURED", "measured: "), ("R31_RESOURCES", "resource
 r32 = (P / "r32_map_distance.txt").read_text().splitlines()
 for name, prefix in (("R32_MEASURED", "measured: "), ("R32_RESOURCES", "resources: "), ("R32_BENCH", "bench: "), ("R32_MUTATIONS", "mutations: ")):
     sub[name] = next(l for l in r32 if l.startswith(prefix)).removeprefix(prefix)
+# §5.23: the same four lines of profiles/r33_map_queries.txt
+r33 = (P / "r33_map_queries.txt").read_text().splitlines()
+for name, prefix in (("R33_MEASURED", "measured: "), ("R33_RESOURCES", "resources: "), ("R33_BENCH", "bench: "), ("R33_MUTATIONS", "mutations: ")):
+    sub[name] = next(l for l in r33 if l.startswith(prefix)).removeprefix(prefix)
 text = Path(sys.argv[1]).read_text()
 for name, val in sub.items():
     text = text.replace("{{" + name + "}}", val)

@@ -3,6 +3,8 @@
 - beside what a caller had before: vofod_read_map plus scipy.ndimage.distance_transform_edt on the host, timed once per map.  Both
 numbers are stated, no ratio is asked of them.  The field match: k_match_field beside k_match_score of the same library for 1 / 64
 / 1024 / 4096 candidate poses (the same lattices, the field of radius 8 in device memory), and k_match_field by chunk and by burst.
+With --parent-lib (a libvofod_hip.so built from the parent commit, as tools/map_match_bench.py takes one) the field-match table is
+taken from that library too, on the same map, field, scan and poses, the parent before this tree at every candidate count.
 Writes profiles/r32_map_distance.txt (first line: the summary DESIGN.md quotes, then one JSON line per shape) - or to --out.
 
 OS1-128 at 0.25 m on bench.py's warmed map, then OS2-128 x 2048 at 0.1 m (--big 0 leaves it out); threshold = thresholds/new_obstacles.
@@ -27,7 +29,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tools"))
 
 import vofod_amd  # noqa: E402
-from map_match_bench import LATTICES, prof, set_env, stats  # noqa: E402
+from map_match_bench import LATTICES, older_library, prof, set_env, stats  # noqa: E402
 from vofod_amd import capi, synth  # noqa: E402
 from vofod_amd.detector import ScanData, VoFOD, default_params, pose_lattice  # noqa: E402
 
@@ -63,14 +65,18 @@ def timed(det, names, call, args):
     return {**{k: stats(v) for k, v in per.items()}, "host_call": stats(host), "rounds": rounds}
 
 
-def measure(args, sensor, voxel_size, warm_scans, pool, torch, dev):
+def measure(args, sensor, voxel_size, warm_scans, pool, torch, dev, parent=None):
     lib = vofod_amd.library()
     h, w, vfov_deg, _ = synth.SENSORS[sensor]
     n_px = h * w
-    sp, dp = default_params(lib)
-    sp.voxel_size, sp.sensor_hrays, sp.sensor_vrays, sp.max_batch_frames = voxel_size, w, h, 1
-    sp.sensor_vfov = F(np.deg2rad(vfov_deg))
-    det = VoFOD(lib, sp, dp)
+
+    def make(lb):
+        sp, dp = default_params(lb)
+        sp.voxel_size, sp.sensor_hrays, sp.sensor_vrays, sp.max_batch_frames = voxel_size, w, h, 1
+        sp.sensor_vfov = F(np.deg2rad(vfov_deg))
+        return VoFOD(lb, sp, dp)
+
+    det = make(lib)
     scene = synth.bench_scene()
     synth.warm_map(det, scene, sensor, warm_scans, pmap=pool.map)
     frame = synth.bench_frames(scene, sensor, 1, 0, pmap=pool.map)[0]
@@ -119,7 +125,7 @@ def measure(args, sensor, voxel_size, warm_scans, pool, torch, dev):
         cnt, n_yaw = LATTICES[k]
         return pose_lattice(lib, tf, (voxel_size,) * 3, cnt, 0.01, n_yaw)
 
-    def field_call(tfs, counts, cost, best):
+    def field_call(tfs, counts, cost, best, lib=lib, det=det):
         t = np.ascontiguousarray(tfs, F).reshape(-1)
 
         def call():
@@ -129,7 +135,7 @@ def measure(args, sensor, voxel_size, warm_scans, pool, torch, dev):
 
         return call
 
-    def score_call(tfs, counts, best):
+    def score_call(tfs, counts, best, lib=lib, det=det):
         t = np.ascontiguousarray(tfs, F).reshape(-1)
 
         def call():
@@ -152,16 +158,30 @@ def measure(args, sensor, voxel_size, warm_scans, pool, torch, dev):
         set_env(None, u)
         res["burst_table"][str(u)] = timed(det, FIELD_KERNELS, field_call(tfs, counts, cost, best), args)["k_match_field"]
     set_env(None, None)  # the kept chunk and burst
+    ref = None
+    if parent is not None:  # the parent's library on the same map: it reads the same field, scan and poses
+        ref = make(parent)
+        ref.write_map(capi.MAP_VOXELS, det.read_map())
     for k in LATTICES:
         tfs = lattice(k)
         counts, cost, best = np.zeros((k, 4), np.uint32), np.zeros(k, np.uint64), C.c_int32(-1)
+        before = None
+        if ref is not None:
+            before = timed(ref, FIELD_KERNELS, field_call(tfs, counts, cost, best, parent, ref), args)
+            before["score"] = timed(ref, SCORE_KERNELS, score_call(tfs, np.zeros((k, 4), np.uint32), best, parent, ref), args)["k_match_score"]
+            was = counts.copy(), cost.copy()
         per = timed(det, FIELD_KERNELS, field_call(tfs, counts, cost, best), args)
+        if before is not None:
+            assert (counts == was[0]).all() and (cost == was[1]).all()  # (the two libraries answer alike)
+            per["parent"] = before
         assert (counts.sum(axis=1) == n_px).all() and (counts[:, 0] == counts[0, 0]).all()
         per.update(n_live=n_px - int(counts[0, 0]), best=int(best.value), cost_best=int(cost[best.value]))
         occ = np.zeros((k, 4), np.uint32)
         per["score"] = timed(det, SCORE_KERNELS, score_call(tfs, occ, best), args)["k_match_score"]
         res["poses"][str(k)] = per
     det.close()
+    if ref is not None:
+        ref.close()
     return res
 
 
@@ -174,7 +194,9 @@ def summary(results):
                           f"the C call {p['host_call']['median_ms']:.2f} ms on the host clock (medians of {p['rounds']} calls)" for R, p in r["radii"].items())
         host = (f"; before: `vofod_read_map` {r['host']['read_map_ms']:.0f} ms plus `scipy.ndimage.distance_transform_edt` {r['host']['edt_ms']:.0f} ms on the host, timed once ({r['host']['occupied']} voxels occupied; "
                 "the device's field at radius 255 equals that transform, clamped)") if "host" in r else "; the host transform was not timed on this map"
-        poses = "; ".join(f"{k} pose{'s' if k != '1' else ''}: `k_match_field` {us(p['k_match_field']):.1f} us beside `k_match_score` {us(p['score']):.1f} us, the C call {us(p['host_call']):.0f} us" for k, p in r["poses"].items())
+        was = lambda p: (f" (the parent's library: {us(p['parent']['k_match_field']):.1f} us, {us(p['parent']['score']):.1f} us, {us(p['parent']['host_call']):.0f} us)" if "parent" in p else "")
+        poses = "; ".join(f"{k} pose{'s' if k != '1' else ''}: `k_match_field` {us(p['k_match_field']):.1f} us beside `k_match_score` {us(p['score']):.1f} us, the C call {us(p['host_call']):.0f} us" + was(p)
+                          for k, p in r["poses"].items())
         row = lambda t: " / ".join(f"{us(v):.1f}" for v in t.values())
         tab = ("; `k_match_field` by chunk " + " / ".join(map(str, CHUNKS)) + ": " + "; ".join(f"at {k} poses {row(t)} us" for k, t in r["chunk_table"].items()) + "; by burst "
                + " / ".join(r["burst_table"]) + f" at 1024 poses and the kept chunk: {row(r['burst_table'])} us")
@@ -191,6 +213,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--slow-ms", type=float, default=200.0, help="a call slower than this is measured over three rounds")
     ap.add_argument("--host-edt-max-voxels", type=int, default=400_000_000, help="maps above this are not transformed on the host")
+    ap.add_argument("--parent-lib", default=None, help="libvofod_hip.so built from the parent commit: the field-match table is taken from it too, the parent first")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "r32_map_distance.txt"))
     args = ap.parse_args()
     import torch
@@ -201,12 +224,13 @@ def main():
     dev = torch.device("cuda", 0)
     torch.zeros(1, device=dev)
     os.environ.setdefault("OPENBLAS_NUM_THREADS", "1")
+    parent = older_library(args.parent_lib) if args.parent_lib else None
     pool = ProcessPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0)))), mp_context=multiprocessing.get_context("spawn"))
     keep = "".join(l + "\n" for l in Path(args.out).read_text().splitlines() if l.startswith(("resources: ", "bench: ", "mutations: "))) if Path(args.out).exists() else ""
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     results = []
     for shape in [("os1-128", 0.25, args.map_warm_scans)] + ([("os2-128x2048", 0.1, args.big_warm_scans)] if args.big else []):
-        results.append(measure(args, *shape, pool, torch, dev))
+        results.append(measure(args, *shape, pool, torch, dev, parent))
         Path(args.out).write_text(summary(results) + keep)  # (after every shape: the second one is long)
     pool.shutdown()
     sys.stdout.write(summary(results) + keep)

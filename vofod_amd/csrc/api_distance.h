@@ -1,7 +1,10 @@
 // vofod_map_distance and vofod_map_match_field (included by vofod_hip.hip after api_match.h): the squared distance, in voxels, from
 // every voxel of the map to the nearest occupied one, and candidate poses scored by such a field.  Contract: include/vofod.h, MAP
-// DISTANCE; kernels and the account of their launches: map_distance.h.  The scan's refusals and its live list are api_match.h's.
+// DISTANCE; kernels and the account of their launches: map_distance.h.  The scan's refusals, its live list, the occupancy image and the
+// scoring launch with its read-back are api_match.h's (match_refusal, match_live_list, match_bits, match_score).
 #pragma once
+
+#include "api_match.h"
 
 namespace
 {
@@ -31,17 +34,15 @@ int vofod_map_distance(vofod_handle* h, float threshold, int32_t radius, uint16_
   // sepclusters pass pending
   VCHK(admit(h, NEEDS_NOTHING));
   vmd::Workspace& w = h->dist;
-  HIPCHK(w.d_bits.reserve((n + 63) / 64));
   HIPCHK(w.d_a.reserve(n));
   HIPCHK(w.d_b.reserve(n));
   const uint32_t sx = static_cast<uint32_t>(h->mg.sx), sy = static_cast<uint32_t>(h->mg.sy), sz = static_cast<uint32_t>(h->mg.sz), R = static_cast<uint32_t>(radius);
   uint32_t gy = 0, gz = 0;
   // ---- the occupancy image of this threshold
-  KLAUNCH_AS(h, "k_match_bits", vmm::k_match_bits, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), static_cast<const float*>(h->d_map.p), h->mg.n, threshold, w.d_bits.p);
-  HIPCHK(hipGetLastError());
+  VCHK(match_bits(h, threshold));
   // ---- along x: bits -> A
   fold_grid(sy * sz, gy, gz);
-  KLAUNCH_AS(h, "k_dist_x", vmd::k_dist_x, dim3((sx + 255) / 256, gy, gz), dim3(256), static_cast<const unsigned long long*>(w.d_bits.p), sx, sy * sz, R, w.d_a.p);
+  KLAUNCH_AS(h, "k_dist_x", vmd::k_dist_x, dim3((sx + 255) / 256, gy, gz), dim3(256), static_cast<const unsigned long long*>(h->match.d_bits.p), sx, sy * sz, R, w.d_a.p);
   HIPCHK(hipGetLastError());
   // ---- along y: A -> B, by the instantiation whose LDS tile has rows for R either side
   const uint32_t y_tiles = (sy + vmd::MD_TY - 1) / vmd::MD_TY;
@@ -78,7 +79,6 @@ int vofod_map_match_field(vofod_handle* h, const vofod_scan* scan, const float* 
   const uint32_t np = static_cast<uint32_t>(n_poses);
   vmm::Workspace& w = h->match;  // (the scan's staging, the live list, the candidates and the counts: one call at a time holds the lock)
   vmd::Workspace& d = h->dist;
-  const size_t n_out = vmm::MM_HEAD + 4 * n_poses;
   HIPCHK(d.d_cost.reserve(n_poses));
   const uint16_t* field = d2;
   if (!field_on_device)
@@ -90,19 +90,8 @@ int vofod_map_match_field(vofod_handle* h, const vofod_scan* scan, const float* 
   HIPCHK(hipMemsetAsync(d.d_cost, 0, n_poses * sizeof(unsigned long long), h->stream));
   // ---- the live list
   VCHK(match_live_list(h, w, *scan, tfs, n_poses));
-  // ---- counts and sums: the launch of k_match_score, chunk and burst read per call
-  const uint32_t chunk = std::max(match_chunk(), (n_px + vmm::MM_MAX_CHUNKS - 1) / vmm::MM_MAX_CHUNKS);
-  const vmm::ScoreParams sp{np, chunk, static_cast<float>(h->mg.sx), static_cast<float>(h->mg.sy), static_cast<float>(h->mg.sz)};
-  const dim3 grid((np + vmm::MM_THREADS - 1) / vmm::MM_THREADS, (n_px + chunk - 1) / chunk), block(vmm::MM_THREADS);
-  const int burst = match_burst();
-  auto score = burst == 1 ? vmd::k_match_field<1> : burst == 2 ? vmd::k_match_field<2> : burst == 4 ? vmd::k_match_field<4> : burst == 8 ? vmd::k_match_field<8> : vmd::k_match_field<vmm::MM_BURST>;
-  KLAUNCH_AS(h, "k_match_field", score, grid, block, sp, h->mg, field, near2, static_cast<const float4*>(w.d_points.p), static_cast<const float*>(w.d_poses.p), w.d_out.p, d.d_cost.p);
-  HIPCHK(hipGetLastError());
-  w.h_out.resize(n_out);
-  d.h_cost.resize(n_poses);
-  HIPCHK(hipMemcpyAsync(w.h_out.data(), w.d_out, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(d.h_cost.data(), d.d_cost, n_poses * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (the call's only one)
+  // ---- counts and sums
+  VCHK(match_score(h, "k_match_field", vmm::LookField{field, near2, d.d_cost.p}, n_poses));
   const uint32_t n_live = w.h_out[0];
   int32_t best_k = 0;
   for (uint32_t k = 0; k < np; k++)

@@ -3,29 +3,10 @@
 // their three launches: map_match.h.
 #pragma once
 
+#include "api_query.h"
+
 namespace
 {
-
-// VOFOD_MATCH_CHUNK=n (diagnostics, tools/map_match_bench.py, and the tests' way to make a small scan straddle chunks): the points per
-// block of k_match_score; unset or anything but a positive number: the one kept
-inline uint32_t match_chunk()
-{
-  if (const char* e = std::getenv("VOFOD_MATCH_CHUNK"))
-  {
-    const long v = std::atol(e);
-    if (v > 0 && v <= 0x7fffffffL)
-      return static_cast<uint32_t>(v);
-  }
-  return vmm::MM_CHUNK;
-}
-
-// VOFOD_MATCH_BURST=1|2|4|8 (diagnostics): the burst lengths measured beside the one kept
-inline int match_burst()
-{
-  if (const char* e = std::getenv("VOFOD_MATCH_BURST"))
-    return std::atoi(e);
-  return vmm::MM_BURST;
-}
 
 // the refusals that the scan and the candidate list decide (include/vofod.h, MAP MATCH), before the lock: shared by vofod_map_match
 // and vofod_map_match_field (api_distance.h)
@@ -54,54 +35,21 @@ inline int match_refusal(const vofod_handle* h, const vofod_scan* scan, const fl
 }
 
 // the live list of a scan that passed match_refusal, under the lock: device-resident columns and tables are read in place, host-resident
-// ones are gathered and staged in `w`; the candidates go to w.d_poses, n_live and every candidate's slots (w.d_out) are cleared on the
+// ones are staged; the candidates go to w.d_poses, n_live and every candidate's slots (w.d_out) are cleared on the
 // stream, and k_match_points fills w.d_points
 inline int match_live_list(vofod_handle* h, vmm::Workspace& w, const vofod_scan& s, const float* tfs, size_t n_poses)
 {
   const int n_null = !s.x + !s.y + !s.z;
-  const bool is_range = n_null == 3, dev = s.memspace == VOFOD_MEM_DEVICE;
+  const bool is_range = n_null == 3;
   const uint32_t width = static_cast<uint32_t>(h->sp.sensor_hrays);
   const uint32_t n = width * static_cast<uint32_t>(h->sp.sensor_vrays);
   const size_t n_out = vmm::MM_HEAD + 4 * n_poses;
   HIPCHK(w.d_points.reserve(n));
   HIPCHK(w.d_poses.reserve(n_poses * 12));
   HIPCHK(w.d_out.reserve(n_out));
-  // ---- the scan: device-resident columns and tables are read in place, host-resident ones are gathered and staged
-  vmm::ScanSource src{};
-  src.stride = dev ? s.stride_bytes : 4;
-  src.poses = s.col_tfs;
-  if (is_range && dev)
-    src.range = static_cast<const char*>(s.range);
-  else if (is_range)
-  {
-    HIPCHK(w.d_range.reserve(n));
-    w.h_range.resize(n);
-    for (uint32_t i = 0; i < n; i++)
-      std::memcpy(w.h_range.data() + i, static_cast<const char*>(s.range) + static_cast<size_t>(i) * s.stride_bytes, 4);
-    HIPCHK(hipMemcpyAsync(w.d_range, w.h_range.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    src.range = reinterpret_cast<const char*>(w.d_range.p);
-  }
-  else if (dev)
-    src.x = static_cast<const char*>(s.x), src.y = static_cast<const char*>(s.y), src.z = static_cast<const char*>(s.z);
-  else
-  {
-    HIPCHK(w.d_xyz.reserve(3 * static_cast<size_t>(n)));
-    w.h_xyz.resize(3 * static_cast<size_t>(n));
-    const void* cols[3] = {s.x, s.y, s.z};
-    for (int a = 0; a < 3; a++)
-      for (uint32_t i = 0; i < n; i++)
-        std::memcpy(w.h_xyz.data() + static_cast<size_t>(a) * n + i, static_cast<const char*>(cols[a]) + static_cast<size_t>(i) * s.stride_bytes, 4);
-    HIPCHK(hipMemcpyAsync(w.d_xyz, w.h_xyz.data(), w.h_xyz.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    src.x = reinterpret_cast<const char*>(w.d_xyz.p);
-    src.y = reinterpret_cast<const char*>(w.d_xyz.p + n);
-    src.z = reinterpret_cast<const char*>(w.d_xyz.p + 2 * static_cast<size_t>(n));
-  }
-  if (s.col_tfs && !dev)
-  {
-    HIPCHK(w.d_tab.reserve(12 * static_cast<size_t>(width)));
-    HIPCHK(hipMemcpyAsync(w.d_tab, s.col_tfs, sizeof(float) * 12 * width, hipMemcpyHostToDevice, h->stream));
-    src.poses = w.d_tab.p;
-  }
+  // ---- the scan: device-resident columns and tables are read in place, host-resident ones are staged (stage_scans, api_query.h)
+  VCHK(stage_scans(h, &s, 1, vss::WANT_TABLES | (is_range ? vss::WANT_RANGE : vss::WANT_POINTS)));
+  const vmm::ScanSource& src = h->qstage.at[0];
   HIPCHK(hipMemcpyAsync(w.d_poses, tfs, n_poses * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemsetAsync(w.d_out, 0, n_out * sizeof(uint32_t), h->stream));  // n_live and every candidate's slots
   vrd::MotionArgs ma{};
@@ -116,6 +64,45 @@ inline int match_live_list(vofod_handle* h, vmm::Workspace& w, const vofod_scan&
   KLAUNCH_AS(h, "k_match_points", points, dim3((n + 255) / 256), dim3(256), src, n, static_cast<const float*>(h->d_lut_dirs.p), static_cast<const float*>(h->d_lut_offs.p), ma, w.d_points.p,
              w.d_out.p);
   HIPCHK(hipGetLastError());
+  return VOFOD_OK;
+}
+
+// the occupancy image of `threshold` in h->match.d_bits (k_match_bits): vofod_map_match scores by it, vofod_map_distance starts from it
+inline int match_bits(vofod_handle* h, float threshold)
+{
+  vmm::Workspace& w = h->match;
+  HIPCHK(w.d_bits.reserve((h->mg.n + 63) / 64));
+  KLAUNCH_AS(h, "k_match_bits", vmm::k_match_bits, dim3(static_cast<uint32_t>((h->mg.n + 255) / 256)), dim3(256), static_cast<const float*>(h->d_map.p), h->mg.n, threshold, w.d_bits.p);
+  HIPCHK(hipGetLastError());
+  return VOFOD_OK;
+}
+
+// the scoring walk over the live list of match_live_list, by either policy, under its profiler label, and what it leaves: the launch
+// is sized for width * height, the blocks beyond n_live leave at once (a chunk below n / 65535 is raised to it: gridDim.y); chunk and
+// burst are read per call.  n_live and the counts arrive in h->match.h_out - and the field's sums in h->dist.h_cost - with the call's
+// only synchronisation, behind which the staged inputs are free.
+template <class Look>
+inline int match_score(vofod_handle* h, const char* label, const Look& look, size_t n_poses)
+{
+  vmm::Workspace& w = h->match;
+  const uint32_t n = static_cast<uint32_t>(h->sp.sensor_hrays) * static_cast<uint32_t>(h->sp.sensor_vrays), np = static_cast<uint32_t>(n_poses);
+  const size_t n_out = vmm::MM_HEAD + 4 * n_poses;
+  const uint32_t chunk = std::max(env_int("VOFOD_MATCH_CHUNK", vmm::MM_CHUNK), (n + vmm::MM_MAX_CHUNKS - 1) / vmm::MM_MAX_CHUNKS);
+  const vmm::ScoreParams sp{np, chunk, static_cast<float>(h->mg.sx), static_cast<float>(h->mg.sy), static_cast<float>(h->mg.sz)};
+  const dim3 grid((np + vmm::MM_THREADS - 1) / vmm::MM_THREADS, (n + chunk - 1) / chunk), block(vmm::MM_THREADS);
+  with_burst<vmm::MM_BURST>(env_int("VOFOD_MATCH_BURST", vmm::MM_BURST), [&](auto U) {
+    auto kern = vmm::k_match<decltype(U)::value, Look>;
+    KLAUNCH_AS(h, label, kern, grid, block, sp, h->mg, look, static_cast<const float4*>(w.d_points.p), static_cast<const float*>(w.d_poses.p), w.d_out.p);
+  });
+  HIPCHK(hipGetLastError());
+  w.h_out.resize(n_out);
+  HIPCHK(hipMemcpyAsync(w.h_out.data(), w.d_out, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  if constexpr (std::is_same_v<Look, vmm::LookField>)
+  {
+    h->dist.h_cost.resize(n_poses);
+    HIPCHK(hipMemcpyAsync(h->dist.h_cost.data(), look.cost, n_poses * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
   return VOFOD_OK;
 }
 
@@ -136,25 +123,9 @@ int vofod_map_match(vofod_handle* h, const vofod_scan* scan, const float* tfs, s
   const uint32_t n = static_cast<uint32_t>(h->sp.sensor_hrays) * static_cast<uint32_t>(h->sp.sensor_vrays);
   const uint32_t np = static_cast<uint32_t>(n_poses);
   vmm::Workspace& w = h->match;
-  const size_t n_words = (h->mg.n + 63) / 64, n_out = vmm::MM_HEAD + 4 * n_poses;
-  HIPCHK(w.d_bits.reserve(n_words));
-  // ---- the occupancy image of this threshold
-  KLAUNCH_AS(h, "k_match_bits", vmm::k_match_bits, dim3(static_cast<uint32_t>((h->mg.n + 255) / 256)), dim3(256), static_cast<const float*>(h->d_map.p), h->mg.n, threshold, w.d_bits.p);
-  HIPCHK(hipGetLastError());
-  // ---- the live list
+  VCHK(match_bits(h, threshold));
   VCHK(match_live_list(h, w, s, tfs, n_poses));
-  // ---- the counts: sized for width * height, the blocks beyond n_live leave at once (a chunk below n / 65535 is raised to it: gridDim.y)
-  const uint32_t chunk = std::max(match_chunk(), (n + vmm::MM_MAX_CHUNKS - 1) / vmm::MM_MAX_CHUNKS);
-  const vmm::ScoreParams sp{np, chunk, static_cast<float>(h->mg.sx), static_cast<float>(h->mg.sy), static_cast<float>(h->mg.sz)};
-  const dim3 grid((np + vmm::MM_THREADS - 1) / vmm::MM_THREADS, (n + chunk - 1) / chunk), block(vmm::MM_THREADS);
-  const int burst = match_burst();
-  auto score = burst == 1 ? vmm::k_match_score<1> : burst == 2 ? vmm::k_match_score<2> : burst == 4 ? vmm::k_match_score<4> : burst == 8 ? vmm::k_match_score<8> : vmm::k_match_score<vmm::MM_BURST>;
-  KLAUNCH_AS(h, "k_match_score", score, grid, block, sp, h->mg, reinterpret_cast<const uint32_t*>(w.d_bits.p), static_cast<const float4*>(w.d_points.p), static_cast<const float*>(w.d_poses.p),
-             w.d_out.p);
-  HIPCHK(hipGetLastError());
-  w.h_out.resize(n_out);
-  HIPCHK(hipMemcpyAsync(w.h_out.data(), w.d_out, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // (the call's only one: n_live and the counts arrive with it, and the staged inputs are free)
+  VCHK(match_score(h, "k_match_score", vmm::LookBits{reinterpret_cast<const uint32_t*>(w.d_bits.p)}, n_poses));
   const uint32_t skipped = n - w.h_out[0];
   uint32_t best_occ = 0;
   int32_t best_k = 0;

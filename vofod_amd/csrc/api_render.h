@@ -3,6 +3,8 @@
 // measured return.  Contracts: include/vofod.h, MAP RENDER and SCANS AGAINST THE MAP; kernel and the account of its bursts: map_render.h.
 #pragma once
 
+#include "api_query.h"
+
 namespace
 {
 
@@ -56,14 +58,6 @@ inline int render_origins_inside(vofod_handle* h, const float* tfs, size_t n_vie
   return VOFOD_OK;
 }
 
-// VOFOD_RENDER_BURST (diagnostics, tools/map_render_bench.py): the burst lengths measured beside the one kept
-inline int render_burst()
-{
-  if (const char* e = std::getenv("VOFOD_RENDER_BURST"))
-    return std::atoi(e);
-  return vmr::MR_BURST;
-}
-
 }  // namespace
 
 extern "C" {
@@ -90,10 +84,11 @@ int vofod_map_render(vofod_handle* h, const float* tfs, size_t n_views, float th
   HIPCHK(hipMemcpyAsync(w.d_poses, tfs, n_views * 12 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   const vmr::RenderParams rp{threshold, max_distance, n};
   const dim3 grid((n + vmr::MR_THREADS - 1) / vmr::MR_THREADS, static_cast<uint32_t>(n_views)), block(vmr::MR_THREADS);
-  const int burst = render_burst();
-  auto kern = burst == 1 ? vmr::k_map_render<1> : burst == 2 ? vmr::k_map_render<2> : burst == 8 ? vmr::k_map_render<8> : burst == 4 ? vmr::k_map_render<4> : vmr::k_map_render<vmr::MR_BURST>;
-  KLAUNCH_AS(h, "k_map_render", kern, grid, block, rp, h->mg, static_cast<const float*>(h->d_map.p), static_cast<const float*>(h->d_lut_dirs.p), static_cast<const float*>(h->d_lut_offs.p),
-             static_cast<const float*>(w.d_poses.p), out);
+  with_burst<vmr::MR_BURST>(env_int("VOFOD_RENDER_BURST", vmr::MR_BURST), [&](auto K) {
+    auto kern = vmr::k_map_render<decltype(K)::value>;
+    KLAUNCH_AS(h, "k_map_render", kern, grid, block, rp, h->mg, static_cast<const float*>(h->d_map.p), static_cast<const float*>(h->d_lut_dirs.p),
+               static_cast<const float*>(h->d_lut_offs.p), static_cast<const float*>(w.d_poses.p), out);
+  });
   HIPCHK(hipGetLastError());
   if (!on_device)
     VCHK(render_outputs_to_host(h, w, total, range, voxel, what, t_in_out));
@@ -111,7 +106,6 @@ int vofod_map_render_scans(vofod_handle* h, const vofod_scan* scans, const float
   if (on_device && (((reinterpret_cast<uintptr_t>(range) | reinterpret_cast<uintptr_t>(voxel)) & 3) || (reinterpret_cast<uintptr_t>(t_in_out) & 7)))
     return VOFOD_ERR_INVALID_ARG;
   const bool compare = verdict || counts;  // the scans' ranges are read
-  size_t n_host_tabs = 0, n_host_ranges = 0;
   for (size_t v = 0; v < n_scans; v++)
   {
     const vofod_scan& s = scans[v];
@@ -124,8 +118,6 @@ int vofod_map_render_scans(vofod_handle* h, const vofod_scan* scans, const float
       return VOFOD_ERR_INVALID_ARG;
     if (dev && (reinterpret_cast<uintptr_t>(s.col_tfs) & 3))
       return VOFOD_ERR_INVALID_ARG;
-    n_host_tabs += !dev && s.col_tfs;
-    n_host_ranges += !dev && compare;
   }
   for (size_t v = 0; v < n_scans; v++)
     if (scans[v].height != h->sp.sensor_vrays || scans[v].width != h->sp.sensor_hrays)
@@ -142,8 +134,6 @@ int vofod_map_render_scans(vofod_handle* h, const vofod_scan* scans, const float
   vmr::RenderOut out{};
   VCHK(render_outputs(h, w, on_device, total, range, voxel, what, t_in_out, out));
   HIPCHK(w.d_views.reserve(n_scans));
-  HIPCHK(w.d_tabs.reserve(n_host_tabs * 12 * width));
-  HIPCHK(w.d_ranges.reserve(n_host_ranges * n));
   uint8_t* d_verdict = verdict;
   if (verdict && !on_device)
   {
@@ -152,50 +142,26 @@ int vofod_map_render_scans(vofod_handle* h, const vofod_scan* scans, const float
   }
   if (counts)
     HIPCHK(w.d_counts.reserve(n_scans * 8));
-  // the view table, and the host scans' tables and ranges gathered behind one another (a table is width * 48 bytes: every staged
-  // table is 16-byte aligned; a staged range column has stride 4)
+  // the host scans' tables and, where they are compared, their range columns; then the view table
+  VCHK(stage_scans(h, scans, n_scans, vss::WANT_TABLES | (compare ? vss::WANT_RANGE : 0u)));
   w.h_views.resize(n_scans);
-  w.h_tabs.resize(n_host_tabs * 12 * width);
-  w.h_ranges.resize(n_host_ranges * n);
-  size_t i_tab = 0, i_range = 0;
   for (size_t v = 0; v < n_scans; v++)
   {
-    const vofod_scan& s = scans[v];
-    const bool dev = s.memspace == VOFOD_MEM_DEVICE;
-    vmr::ViewEntry& e = w.h_views[v];
-    std::memcpy(e.tf, tfs + 12 * v, sizeof(e.tf));
-    e.poses = s.col_tfs;
-    if (s.col_tfs && !dev)
-    {
-      std::memcpy(w.h_tabs.data() + i_tab * 12 * width, s.col_tfs, sizeof(float) * 12 * width);
-      e.poses = w.d_tabs.p + i_tab++ * 12 * width;
-    }
-    e.range = nullptr, e.stride = 4;
-    if (compare && dev)
-      e.range = static_cast<const char*>(s.range), e.stride = s.stride_bytes;
-    else if (compare)
-    {
-      uint32_t* dst = w.h_ranges.data() + i_range * n;
-      for (uint32_t i = 0; i < n; i++)
-        std::memcpy(dst + i, static_cast<const char*>(s.range) + static_cast<size_t>(i) * s.stride_bytes, 4);
-      e.range = reinterpret_cast<const char*>(w.d_ranges.p + i_range++ * n);
-    }
+    const vss::Staged& e = h->qstage.at[v];
+    w.h_views[v] = vmr::ViewEntry{{}, e.poses, e.range, e.range ? e.stride : 4};  // (no range to compare: the stride is not read, and is 4 as it was)
+    std::memcpy(w.h_views[v].tf, tfs + 12 * v, sizeof(w.h_views[v].tf));
   }
   HIPCHK(hipMemcpyAsync(w.d_views, w.h_views.data(), n_scans * sizeof(vmr::ViewEntry), hipMemcpyHostToDevice, h->stream));
-  if (n_host_tabs)
-    HIPCHK(hipMemcpyAsync(w.d_tabs, w.h_tabs.data(), w.h_tabs.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (n_host_ranges)
-    HIPCHK(hipMemcpyAsync(w.d_ranges, w.h_ranges.data(), w.h_ranges.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   if (counts)
     HIPCHK(hipMemsetAsync(w.d_counts, 0, n_scans * 8 * sizeof(uint32_t), h->stream));
   const vmr::RenderParams rp{threshold, max_distance, n};
   const vmr::ScanViews views{w.d_views.p, h->d_col_shift.p, h->d_mask.p, width, tolerance, d_verdict, counts ? w.d_counts.p : nullptr};
   const dim3 grid((n + vmr::MR_THREADS - 1) / vmr::MR_THREADS, static_cast<uint32_t>(n_scans)), block(vmr::MR_THREADS);
-  const int burst = render_burst();
-  using SV = vmr::ScanViews;
-  auto kern = burst == 1 ? vmr::k_map_render<1, SV> : burst == 2 ? vmr::k_map_render<2, SV> : burst == 8 ? vmr::k_map_render<8, SV> : burst == 4 ? vmr::k_map_render<4, SV> : vmr::k_map_render<vmr::MR_BURST, SV>;
-  KLAUNCH_AS(h, "k_map_render_scans", kern, grid, block, rp, h->mg, static_cast<const float*>(h->d_map.p), static_cast<const float*>(h->d_lut_dirs.p),
-             static_cast<const float*>(h->d_lut_offs.p), views, out);
+  with_burst<vmr::MR_BURST>(env_int("VOFOD_RENDER_BURST", vmr::MR_BURST), [&](auto K) {
+    auto kern = vmr::k_map_render<decltype(K)::value, vmr::ScanViews>;
+    KLAUNCH_AS(h, "k_map_render_scans", kern, grid, block, rp, h->mg, static_cast<const float*>(h->d_map.p), static_cast<const float*>(h->d_lut_dirs.p),
+               static_cast<const float*>(h->d_lut_offs.p), views, out);
+  });
   HIPCHK(hipGetLastError());
   if (!on_device)
     VCHK(render_outputs_to_host(h, w, total, range, voxel, what, t_in_out));

@@ -23,16 +23,13 @@
 // outside an allocation is ever formed: every window is clamped to its axis BEFORE an address is made, nothing is loaded and
 // discarded.  The work is O(N * R) in the worst case (open space far from everything at a large R); times: tools/map_distance_bench.py, DESIGN.md 5.22.
 //
-//   k_match_field<U>   k_match_score's shape (map_match.h): the lanes are the candidates, the live list of k_match_points is staged
-//              in LDS tiles, the walk goes in bursts of U look-ups whose addresses never depend on a loaded value, an OUTSIDE lane
-//              loads element 0 and ignores it.  One 2-byte load per look-up from the field in place of a bit word.  A lane keeps
-//              two counters and a sum; THE SUM MUST NOT WRAP: a tile of 1024 points x 65535 < 2^32, so the tile's sum is 32 bits
-//              wide and is flushed into a 64-bit one behind every tile.  At the end one 64-bit atomicAdd and at most two 32-bit
-//              ones per candidate (OUTSIDE and NEAR; FAR is what is left of the live list), into slots cleared on the stream.
+// Scoring by the field (vofod_map_match_field, profiler label k_match_field) is map_match.h's one walk, vmm::k_match<U, LookField>:
+// the policy there says what a look-up of the field counts and why its sum cannot wrap.  Nothing of that walk is restated here.
 // Out of scope: a feature transform (the nearest voxel's index), an O(N) lower-envelope scan, a field patched by the map update.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <vector>
 
 #include "device_mem.h"
@@ -47,10 +44,9 @@ constexpr uint32_t MD_NOT_FOUND = 256;    // k_dist_x: an x distance beyond ever
 constexpr uint32_t MD_TX = 64, MD_TY = 32, MD_YSTEP = 4;  // k_dist_y: columns and rows of a block's tile; 256 threads = 64 x 4
 constexpr uint32_t MD_MAX_GRID = 65535;   // gridDim.y: a longer list of rows / tiles / planes folds into gridDim.z
 
-// the workspace of the two calls, owned by the handle and grown to the largest seen
+// the workspace of the two calls, owned by the handle and grown to the largest seen (the occupancy image is vmm::Workspace's)
 struct Workspace
 {
-  DevBuf<unsigned long long> d_bits;  // vofod_map_distance: ceil(n_voxels / 64) words
   DevBuf<uint16_t> d_a, d_b;          // the passes' intermediate fields, n_voxels each; d_a is also the staging of a host output
   DevBuf<uint16_t> d_field;           // vofod_map_match_field: a host field
   DevBuf<unsigned long long> d_cost;  // one sum per candidate
@@ -156,86 +152,6 @@ __global__ __launch_bounds__(256) void k_dist_z(const uint16_t* __restrict__ in,
       best = min(best, col[(z + d) * plane] + d * d);
   }
   out[z * plane + p] = static_cast<uint16_t>(best);
-}
-
-template <int U>
-__global__ __launch_bounds__(vmm::MM_THREADS) void k_match_field(const vmm::ScoreParams sp, const MapGeom mg, const uint16_t* __restrict__ d2, uint32_t near2,
-                                                                const float4* __restrict__ points, const float* __restrict__ poses, uint32_t* __restrict__ out,
-                                                                unsigned long long* __restrict__ cost)
-{
-  __shared__ float4 s_pts[vmm::MM_TILE];
-  const uint32_t n_live = out[0];
-  const uint32_t begin = blockIdx.y * sp.chunk;
-  if (begin >= n_live)
-    return;
-  const uint32_t end = min(begin + sp.chunk, n_live);
-  const uint32_t cand = blockIdx.x * vmm::MM_THREADS + threadIdx.x;
-  const bool alive = cand < sp.n_poses;
-  const float* T = poses + 12u * static_cast<size_t>(alive ? cand : sp.n_poses - 1u);
-  const float r00 = T[0], r01 = T[1], r02 = T[2], t0 = T[3];
-  const float r10 = T[4], r11 = T[5], r12 = T[6], t1 = T[7];
-  const float r20 = T[8], r21 = T[9], r22 = T[10], t2 = T[11];
-  const uint32_t sx = static_cast<uint32_t>(mg.sx), sy = static_cast<uint32_t>(mg.sy);
-  uint32_t n_in = 0, n_near = 0;  // the chunk's points inside the map, and those of them that are NEAR
-  unsigned long long sum = 0;
-  for (uint32_t tile = begin; tile < end; tile += vmm::MM_TILE)
-  {
-    const uint32_t cnt = min(vmm::MM_TILE, end - tile);
-    __syncthreads();  // (the tile before this one has been walked by every lane)
-    for (uint32_t j = threadIdx.x; j < cnt; j += vmm::MM_THREADS)
-      s_pts[j] = points[tile + j];
-    __syncthreads();
-    uint32_t tile_sum = 0;  // at most MM_TILE * 65535 = 67 107 840: no wrap
-    // (2-byte values tempt the loop vectoriser to walk two bursts side by side in packed halves: twice the registers, nothing gained)
-#pragma clang loop vectorize(disable) interleave(disable)
-    for (uint32_t j = 0; j < cnt; j += U)
-    {
-      // ---- the burst: U addresses, nothing read.  A step behind the tile's end looks at the tile's last point again and counts nothing.
-      uint32_t v[U], inside = 0;  // (bit u: burst step u lies in the map)
-#pragma unroll
-      for (int u = 0; u < U; u++)
-      {
-        const float4 p = s_pts[min(j + u, cnt - 1u)];  // (the same address in all 64 lanes: a broadcast)
-        const float w0 = __fadd_rn(__fmul_rn(r00, p.x), __fadd_rn(__fmul_rn(r01, p.y), __fadd_rn(__fmul_rn(r02, p.z), t0)));
-        const float w1 = __fadd_rn(__fmul_rn(r10, p.x), __fadd_rn(__fmul_rn(r11, p.y), __fadd_rn(__fmul_rn(r12, p.z), t1)));
-        const float w2 = __fadd_rn(__fmul_rn(r20, p.x), __fadd_rn(__fmul_rn(r21, p.y), __fadd_rn(__fmul_rn(r22, p.z), t2)));
-        const float f0 = floorf(__fmul_rn(__fsub_rn(w0, mg.off[0]), mg.vs_inv));
-        const float f1 = floorf(__fmul_rn(__fsub_rn(w1, mg.off[1]), mg.vs_inv));
-        const float f2 = floorf(__fmul_rn(__fsub_rn(w2, mg.off[2]), mg.vs_inv));
-        // compared as floats BEFORE the conversion: a NaN or infinite w is OUTSIDE, and only floats of [0, size) are converted
-        const bool in = f0 >= 0.0f && f0 < sp.fsx && f1 >= 0.0f && f1 < sp.fsy && f2 >= 0.0f && f2 < sp.fsz;
-        const uint32_t x = static_cast<uint32_t>(in ? f0 : 0.0f), y = static_cast<uint32_t>(in ? f1 : 0.0f), z = static_cast<uint32_t>(in ? f2 : 0.0f);
-        v[u] = (z * sy + y) * sx + x;  // (an OUTSIDE lane: voxel 0)
-        inside |= in && j + u < cnt ? 1u << u : 0u;  // (a step behind the tile's end is neither inside nor outside)
-      }
-      // ---- the U loads, together (every index is a voxel of the field)
-      uint32_t f[U];
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        f[u] = d2[v[u]];
-      // ---- the tests
-#pragma unroll
-      for (int u = 0; u < U; u++)
-      {
-        const bool in = (inside >> u) & 1u;
-        n_near += in && f[u] <= near2 ? 1u : 0u;
-        tile_sum += in ? f[u] : 0u;
-      }
-      n_in += static_cast<uint32_t>(__popc(inside));
-    }
-    sum += tile_sum;
-  }
-  if (alive)
-  {
-    uint32_t* slot = out + vmm::MM_HEAD + 4u * static_cast<size_t>(cand);
-    const uint32_t n_out = (end - begin) - n_in;
-    if (n_out)
-      atomicAdd(slot + 1, n_out);  // VOFOD_FIELD_OUTSIDE
-    if (n_near)
-      atomicAdd(slot + 3, n_near);  // VOFOD_FIELD_NEAR (FAR: the host's n_live - OUTSIDE - NEAR)
-    if (sum)
-      atomicAdd(cost + cand, sum);
-  }
 }
 
 }  // namespace vmd

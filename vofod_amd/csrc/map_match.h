@@ -12,40 +12,48 @@
 //                   prefix) into a list of 16-byte points.  THE ORDER OF THE LIST IS ARBITRARY - it depends on which wave's atomic
 //                   arrives first - and that is fine: everything computed from it is an integer count, exact in any order.
 //                   n_live stays on the device: the next launch is sized for width * height and its blocks beyond n_live leave at once.
-//   k_match_score   the lanes are the CANDIDATES.  blockIdx.x is a group of 256 candidates, blockIdx.y a chunk of the live list.  A
-//                   lane loads its own pose once (12 VGPRs; a lane beyond n_poses takes pose n_poses - 1 and adds nothing at the
-//                   end), the block stages its chunk into LDS tile by tile, and every lane walks the tile: the point is the same
-//                   LDS address for all 64 lanes - a broadcast read, no bank conflict.  Three rows in __fmul_rn / __fadd_rn (PCL's
-//                   association, rd_row), the float bounds test, the bit's word address, one 4-byte load.  The address never depends
+//   k_match<U, Look>  the scoring walk (profiler label k_match_score).  The lanes are the CANDIDATES.  blockIdx.x is a group of 256
+//                   candidates, blockIdx.y a chunk of the live list.  A lane loads its own pose once (12 VGPRs; a lane beyond
+//                   n_poses takes pose n_poses - 1 and adds nothing at the end), the block stages its chunk into LDS tile by tile,
+//                   and every lane walks the tile: the point is the same LDS address for all 64 lanes - a broadcast read, no bank
+//                   conflict.  Three rows in __fmul_rn / __fadd_rn (PCL's
+//                   association, rd_row), the float bounds test, the voxel's element address, one load.  The address never depends
 //                   on a loaded value, so - as in k_map_render - the walk goes in BURSTS of U points: U addresses, U loads issued
 //                   together, then U tests; per-step arrays are indexed by unrolled constants, the state is in scalar locals.  An
-//                   OUTSIDE lane loads word 0 and ignores it: no index outside the image is ever formed, and no float outside
+//                   OUTSIDE lane loads element 0 and ignores it: no index outside the image is ever formed, and no float outside
 //                   [0, size) is ever converted.  The counters live in registers for the whole chunk - the point loop has no
 //                   reduction - and at the end each live lane issues up to three atomicAdds into its candidate's slots, cleared on
 //                   the stream before the launch.  Neighbouring candidates sit in neighbouring lanes: a wave's 64 look-ups of one
 //                   point fall into a handful of cache lines.
+//                   WHAT is looked up is the policy Look, as Acc is k_raycast_t's and Views k_map_render's: LookBits reads the
+//                   bit image as 32-bit words (word v >> 5, bit v & 31) and counts OUTSIDE / FREE / OCCUPIED; LookField
+//                   (vofod_map_match_field, label k_match_field) reads a distance field, one uint16_t per voxel, and keeps OUTSIDE,
+//                   NEAR and a cost sum.  The walk, its bounds rule and its tile rule are one text for both.
 //
 // The chunk (points per block) and U are host-side choices.  Measured (profiles/r31_map_match.txt; OS1-128 at 0.25 m,
 // 38 947 live returns): k_match_score at 1024 poses 51.8 / 57.6 / 78.1 / 132.3 / 488.2 us for chunks of 64 / 128 / 256 / 512 / 2048
 // points, at 4096 poses 155.7 / 156.4 / 171.8 / 194.0 / 491.7 us - a block walks its chunk one burst behind the other, so what
 // counts is how many blocks there are to hide one another's latency; U = 1 / 2 / 4 / 8 at 1024 poses and chunk 64: 53.8 / 52.6 /
-// 50.0 / 49.0 us.  MM_CHUNK = 64 and MM_BURST = 8 are kept (48 VGPRs, no scratch, 8 waves per SIMD); OS2-128 x 2048 at 0.1 m orders
-// them the same way.  VOFOD_MATCH_CHUNK and VOFOD_MATCH_BURST select others per call (diagnostics, and the tests' way to make a
-// small scan straddle chunks).
+// 50.0 / 49.0 us.  MM_CHUNK = 64 and MM_BURST = 8 are kept (48 VGPRs with LookBits, 51 with LookField, no scratch, 8 waves per
+// SIMD); OS2-128 x 2048 at 0.1 m orders them the same way.  VOFOD_MATCH_CHUNK and VOFOD_MATCH_BURST select others per call
+// (diagnostics, and the tests' way to make a small scan straddle chunks).
 // Out of scope: reuse of the image between calls or of d_mapbits, a NEAR class, several scans per call.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <vector>
 
+#include "common.h"
 #include "device_mem.h"
 #include "range_decode.h"
+#include "scan_stage.h"
 
 namespace vmm
 {
 using namespace vk;
 
-constexpr int MM_THREADS = 256;            // k_match_score: candidates per group
+constexpr int MM_THREADS = 256;            // k_match: candidates per group
 constexpr uint32_t MM_MAX_POSES = 65535;
 constexpr uint32_t MM_TILE = 1024;         // points staged into LDS at a time (16 KiB)
 constexpr uint32_t MM_CHUNK = 64;          // points per block of the production launch (VOFOD_MATCH_CHUNK=n selects another)
@@ -53,31 +61,18 @@ constexpr int MM_BURST = 8;                // look-ups per burst of the producti
 constexpr uint32_t MM_MAX_CHUNKS = 65535;  // gridDim.y
 constexpr uint32_t MM_HEAD = 4;            // words in front of the device counts: [0] n_live, the rest padding (the counts stay 16-byte aligned)
 
-// the workspace of the call, owned by the handle and grown to the largest seen; h_*: where host inputs are gathered and where the
-// one copy out lands
+// the workspace of the match calls and of vofod_map_distance's image, owned by the handle and grown to the largest seen; h_out: where
+// the one copy out lands (a host scan is staged by the query calls' one ScanStage, scan_stage.h)
 struct Workspace
 {
   DevBuf<unsigned long long> d_bits;  // ceil(n_voxels / 64) words
   DevBuf<float4> d_points;            // the live list, width * height entries
   DevBuf<float> d_poses;              // n_poses * 12
   DevBuf<uint32_t> d_out;             // MM_HEAD + n_poses * 4
-  DevBuf<uint32_t> d_range;           // a host range image, packed
-  DevBuf<float> d_xyz;                // a host point scan: three packed columns
-  DevBuf<float> d_tab;                // a host pose table
-  std::vector<uint32_t> h_range, h_out;
-  std::vector<float> h_xyz;
+  std::vector<uint32_t> h_out;
 };
 
-// the scan as k_match_points reads it
-struct ScanSource
-{
-  const char* range;   // range image: uint32 millimetres, pixel i at range + i * stride
-  const char* x;       // point scan: floats at x / y / z + i * stride
-  const char* y;
-  const char* z;
-  uint64_t stride;
-  const float* poses;  // the scan's col_tfs on the device, nullptr: none
-};
+using ScanSource = vss::Staged;  // the scan as k_match_points reads it: where stage_scans (api_query.h) put it, or where the caller has it
 
 __global__ __launch_bounds__(256) void k_match_bits(const float* __restrict__ map, uint64_t n, float threshold, unsigned long long* __restrict__ bits)
 {
@@ -146,9 +141,71 @@ struct ScoreParams
   float fsx, fsy, fsz;  // the map's size as floats: the bounds of the float test
 };
 
-template <int U>
-__global__ __launch_bounds__(MM_THREADS) void k_match_score(const ScoreParams sp, const MapGeom mg, const uint32_t* __restrict__ bits, const float4* __restrict__ points,
-                                                           const float* __restrict__ poses, uint32_t* __restrict__ out)
+// ---- the two policies of k_match.  A policy goes to the kernel by value and is the lane's private state from then on.
+
+// vofod_map_match: the bit image of k_match_bits, read as 32-bit words
+struct LookBits
+{
+  using Elem = uint32_t;
+  const Elem* image;
+  uint32_t n_out = 0, n_occ = 0;
+  __device__ __forceinline__ uint32_t index(uint32_t v) const { return v >> 5; }
+  __device__ __forceinline__ void tile_begin() {}
+  __device__ __forceinline__ void take(bool counted, bool in, uint32_t word, uint32_t v)
+  {
+    n_out += counted && !in ? 1u : 0u;
+    n_occ += counted && in ? (word >> (v & 31u)) & 1u : 0u;
+  }
+  __device__ __forceinline__ void tile_end() {}
+  __device__ __forceinline__ void finish(uint32_t* slot, uint32_t, uint32_t n_points) const
+  {
+    const uint32_t n_free = n_points - n_out - n_occ;
+    if (n_out)
+      atomicAdd(slot + 1, n_out);  // VOFOD_MATCH_OUTSIDE
+    if (n_free)
+      atomicAdd(slot + 2, n_free);  // VOFOD_MATCH_FREE
+    if (n_occ)
+      atomicAdd(slot + 3, n_occ);  // VOFOD_MATCH_OCCUPIED
+  }
+};
+
+// vofod_map_match_field: a distance field (map_distance.h), one 2-byte value per voxel.  Two counters (inside, NEAR) and a sum; THE
+// SUM MUST NOT WRAP: a tile of MM_TILE = 1024 points x 65535 = 67 107 840 < 2^32, so the tile's sum is 32 bits wide and is flushed
+// into a 64-bit one behind every tile.  At the end one 64-bit atomicAdd and at most two 32-bit ones (OUTSIDE and NEAR; FAR is what
+// the host has left of the live list).
+struct LookField
+{
+  using Elem = uint16_t;
+  const Elem* image;
+  uint32_t near2;
+  unsigned long long* cost;  // one sum per candidate, cleared on the stream before the launch
+  uint32_t n_in = 0, n_near = 0, tile_sum = 0;  // (the chunk's points inside the map, and those of them that are NEAR)
+  unsigned long long sum = 0;
+  __device__ __forceinline__ uint32_t index(uint32_t v) const { return v; }
+  __device__ __forceinline__ void tile_begin() { tile_sum = 0; }
+  __device__ __forceinline__ void take(bool counted, bool in, uint32_t d2, uint32_t)
+  {
+    const bool inside = counted && in;  // (one lane mask decides all three)
+    n_in += inside ? 1u : 0u;
+    n_near += inside && d2 <= near2 ? 1u : 0u;
+    tile_sum += inside ? d2 : 0u;
+  }
+  __device__ __forceinline__ void tile_end() { sum += tile_sum; }
+  __device__ __forceinline__ void finish(uint32_t* slot, uint32_t cand, uint32_t n_points) const
+  {
+    const uint32_t n_out = n_points - n_in;
+    if (n_out)
+      atomicAdd(slot + 1, n_out);  // VOFOD_FIELD_OUTSIDE
+    if (n_near)
+      atomicAdd(slot + 3, n_near);  // VOFOD_FIELD_NEAR (FAR: the host's n_live - OUTSIDE - NEAR)
+    if (sum)
+      atomicAdd(cost + cand, sum);
+  }
+};
+
+template <int U, class Look>
+__global__ __launch_bounds__(MM_THREADS) void k_match(const ScoreParams sp, const MapGeom mg, Look look, const float4* __restrict__ points, const float* __restrict__ poses,
+                                                     uint32_t* __restrict__ out)
 {
   __shared__ float4 s_pts[MM_TILE];
   const uint32_t n_live = out[0];
@@ -163,7 +220,7 @@ __global__ __launch_bounds__(MM_THREADS) void k_match_score(const ScoreParams sp
   const float r10 = T[4], r11 = T[5], r12 = T[6], t1 = T[7];
   const float r20 = T[8], r21 = T[9], r22 = T[10], t2 = T[11];
   const uint32_t sx = static_cast<uint32_t>(mg.sx), sy = static_cast<uint32_t>(mg.sy);
-  uint32_t n_out = 0, n_occ = 0;
+  const typename Look::Elem* __restrict__ image = look.image;
   for (uint32_t tile = begin; tile < end; tile += MM_TILE)
   {
     const uint32_t cnt = min(MM_TILE, end - tile);
@@ -171,11 +228,14 @@ __global__ __launch_bounds__(MM_THREADS) void k_match_score(const ScoreParams sp
     for (uint32_t j = threadIdx.x; j < cnt; j += MM_THREADS)
       s_pts[j] = points[tile + j];
     __syncthreads();
+    look.tile_begin();
+    // (2-byte values tempt the loop vectoriser to walk two bursts side by side in packed halves: twice the registers, nothing gained)
+#pragma clang loop vectorize(disable) interleave(disable)
     for (uint32_t j = 0; j < cnt; j += U)
     {
       // ---- the burst: U addresses, nothing read.  A step behind the tile's end looks at the tile's last point again and counts nothing.
-      uint32_t word[U], bit[U];
-      bool in[U];
+      uint32_t v[U];
+      bool in[U];  // (a lane mask each: scalar registers, where a bit per step in a vector register costs a shift and a test per step)
 #pragma unroll
       for (int u = 0; u < U; u++)
       {
@@ -189,36 +249,22 @@ __global__ __launch_bounds__(MM_THREADS) void k_match_score(const ScoreParams sp
         // compared as floats BEFORE the conversion: a NaN or infinite w is OUTSIDE, and only floats of [0, size) are converted
         in[u] = f0 >= 0.0f && f0 < sp.fsx && f1 >= 0.0f && f1 < sp.fsy && f2 >= 0.0f && f2 < sp.fsz;
         const uint32_t x = static_cast<uint32_t>(in[u] ? f0 : 0.0f), y = static_cast<uint32_t>(in[u] ? f1 : 0.0f), z = static_cast<uint32_t>(in[u] ? f2 : 0.0f);
-        const uint32_t v = (z * sy + y) * sx + x;  // (an OUTSIDE lane: voxel 0, word 0)
-        word[u] = v >> 5;
-        bit[u] = v & 31u;
+        v[u] = (z * sy + y) * sx + x;  // (an OUTSIDE lane: voxel 0, element 0 - no index outside the image is ever formed)
       }
-      // ---- the U loads, together (every index is a word of the image)
+      // ---- the U loads, together (every index is an element of the image)
       uint32_t m[U];
 #pragma unroll
       for (int u = 0; u < U; u++)
-        m[u] = bits[word[u]];
-      // ---- the tests
+        m[u] = image[look.index(v[u])];
+      // ---- the tests: an OUTSIDE lane ignores what it loaded, a step behind the tile's end counts as nothing (wave-uniform)
 #pragma unroll
       for (int u = 0; u < U; u++)
-      {
-        const bool counted = j + u < cnt;  // (wave-uniform)
-        n_out += counted && !in[u] ? 1u : 0u;
-        n_occ += counted && in[u] ? (m[u] >> bit[u]) & 1u : 0u;
-      }
+        look.take(j + u < cnt, in[u], m[u], v[u]);
     }
+    look.tile_end();
   }
   if (alive)
-  {
-    uint32_t* slot = out + MM_HEAD + 4u * static_cast<size_t>(cand);
-    const uint32_t n_free = (end - begin) - n_out - n_occ;
-    if (n_out)
-      atomicAdd(slot + 1, n_out);  // VOFOD_MATCH_OUTSIDE
-    if (n_free)
-      atomicAdd(slot + 2, n_free);  // VOFOD_MATCH_FREE
-    if (n_occ)
-      atomicAdd(slot + 3, n_occ);  // VOFOD_MATCH_OCCUPIED
-  }
+    look.finish(out + MM_HEAD + 4u * static_cast<size_t>(cand), cand, end - begin);
 }
 
 }  // namespace vmm

@@ -39,8 +39,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <vector>
 
+#include "column_pose.h"
+#include "common.h"
 #include "device_mem.h"
 #include "kernels_raycast.h"
 
@@ -97,8 +100,9 @@ struct ScanViews
 };
 
 // the workspace of the two calls, owned by the handle and grown to the largest seen: the pose table and, for host outputs, the
-// staging the kernel writes; for vofod_map_render_scans the view table, the host scans' pose tables and range columns (h_*: where
-// they are gathered, d_*: where the kernel reads them), the verdicts and the counts
+// staging the kernel writes; for vofod_map_render_scans the view table (h_views: where it is written, d_views: where the kernel
+// reads it), the verdicts and the counts.  The host scans' pose tables and range columns are staged by the query calls' one
+// ScanStage (scan_stage.h).
 struct Workspace
 {
   DevBuf<float> d_poses;
@@ -106,13 +110,9 @@ struct Workspace
   DevBuf<uint8_t> d_what;
   DevBuf<float2> d_tio;
   DevBuf<ViewEntry> d_views;
-  DevBuf<float> d_tabs;
-  DevBuf<uint32_t> d_ranges;
   DevBuf<uint8_t> d_verdict;
   DevBuf<uint32_t> d_counts;
   std::vector<ViewEntry> h_views;
-  std::vector<float> h_tabs;
-  std::vector<uint32_t> h_ranges;
 };
 
 // the sensor's millimetres of the middle of the piece [t_in, t_out], ties to even, never the 0 of "no return"

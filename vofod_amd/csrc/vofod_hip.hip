@@ -39,6 +39,7 @@
 #include "detection_points.h"
 #include "detection_pixels.h"
 #include "map_shift.h"
+#include "scan_stage.h"
 #include "map_render.h"
 #include "map_match.h"
 #include "map_distance.h"
@@ -500,8 +501,10 @@ struct vofod_handle
   DevBuf<float> d_map, d_flags, d_ray;
   DevBuf<float> d_shift_spare;  // vofod_map_shift: destination of the out-of-place shift, swapped with the map it received (allocated on the first shift)
   vmr::Workspace render;  // vofod_map_render: pose table and host-output staging, grown to the largest n_views * w * h seen
-  vmm::Workspace match;  // vofod_map_match: the occupancy image of the call's threshold, the live list, pose table and counts, host-input staging
-  vmd::Workspace dist;  // vofod_map_distance: its occupancy image and the passes' two fields; vofod_map_match_field: a host field's staging, the sums
+  vmm::Workspace match;  // vofod_map_match: the live list, pose table and counts; and the occupancy image of a call's threshold (vofod_map_distance's too)
+  vmd::Workspace dist;  // vofod_map_distance: the passes' two fields; vofod_map_match_field: a host field's staging, the sums
+  vss::ScanStage qstage;  // the query calls' host-resident scans (scan_stage.h): the block they are gathered into
+  DevBuf<uint32_t> d_qstage;  // ... and where it stands on the device
   vws::Store world;  // vofod_world_enable: the voxel map is a window onto it (world_store.h); indexed by world index, so no shift moves it
   vwy::State wsync;  // snapshots / deltas of the store (world_sync.h, world_sync_host.h): shadow pool, scratch and the two chains
   DevBuf<unsigned long long> d_mapbits;
@@ -941,8 +944,7 @@ int stage_host_column(vofod_handle* h, void* dst, const void* src, size_t stride
   if (stride != 4)
   {
     tmp.resize(n);
-    for (size_t i = 0; i < n; i++)
-      std::memcpy(&tmp[i], static_cast<const char*>(src) + i * stride, 4);
+    vss::gather4(tmp.data(), src, stride, n);
     src = tmp.data();
   }
   HIPCHK(hipMemcpyAsync(dst, src, n * 4, hipMemcpyHostToDevice, h->stream));
